@@ -7,8 +7,13 @@ One "step" = one batch of `--batch` synthetic partial clouds taken through the w
 grid -> UNet3D + Upsampler -> fused SDF query on the 128^3 lattice -> sigmoid occupancy.
 Inputs are resident in HBM before the timed region; weights are hash-generated (no checkpoints ship).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs: set up, warm up, time K steps, print one JSON line.  --full adds the stage /
+AR-loop breakdown, the in-situ roofline, the token CRC check, per-kernel timings, the sub-records of BASELINE configs 2-5
+and the CPU baselines.  --dump-outputs DIR writes what the last timed step returned (dump_outputs).
 
 Multi-GPU: shapes are independent -> each rank processes its own batch, no data-path collective
 ("weak" scaling); only the timing barrier / max-over-ranks uses RCCL.
@@ -65,13 +70,22 @@ def parse():
     ap.add_argument("--train-fused-opt", type=int, default=1, help="--mode train: 1 = AdamW per bucket inside the backward pass (default), 0 = one AdamW launch after it")
     ap.add_argument("--train-lc", type=int, default=200)
     ap.add_argument("--train-lz", type=int, default=300)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: stage / AR-loop breakdown, in-situ roofline, token CRC check, "
+                         "per-kernel timings, sub-records (BASELINE configs 2-5), CPU baselines (each can still be dropped with its --no-* option). "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB; rank 0)")
+    a = ap.parse_args()
+    if not a.full:
+        a.no_roofline = a.no_kernels = a.no_subrecords = a.no_cpu_baseline = True
+    return a
 
 
 def launch_ranks(a):
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks ourselves (one process per GPU,
-    rendezvous on 127.0.0.1) and hand over to them.  Under torchrun (WORLD_SIZE set) this is a no-op; a WORLD_SIZE that
-    disagrees with --gpus, or fewer visible GPUs than ranks, is an error - never a silent 1-rank run."""
+    rendezvous on 127.0.0.1) in a child launcher and exit with its status.  Under torchrun (WORLD_SIZE set) this is a no-op; a
+    WORLD_SIZE that disagrees with --gpus, or fewer visible GPUs than ranks, is an error - never a silent 1-rank run."""
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         if int(env_world) != a.gpus:
@@ -89,7 +103,9 @@ def launch_ranks(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    os.execvpe(sys.executable, cmd, env)
+    # a fresh child, not exec: this process has already asked the HIP runtime for the device count
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def ev_time(fn, n, warm=2):
@@ -563,6 +579,40 @@ def token_checksums(r, B, a, seed=None):
     return out
 
 
+DUMP_BYTES = 60 * 10 ** 6      # payload; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(d, r):
+    """--dump-outputs: what the last timed step's caller received from ShapeCompletion.complete, as DIR/<name>.npy.  Integer arrays
+    (tokens, positions, code indices, lengths: all < 2^24) are written as float32, exactly.  The occupancy (3.2 GB at 384 shapes x
+    128^3) does not fit the 64 MB: every shape's mean over its whole lattice (float64), and the whole lattices of a fixed, seeded
+    choice of shapes (`occupancy_rows`); when one lattice alone is over the budget, a fixed, seeded choice of its points
+    (`occupancy_points`).  The inputs of a run depend only on its arguments, so two builds compare output for output."""
+    os.makedirs(d, exist_ok=True)
+    st = r["state"]
+    out = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in (
+        ("c_ind", r["c_ind"]), ("Lc", r["Lc"]), ("empty_index", r["empty_index"]), ("tokens", st["seq"]), ("tokens_len", st["len"]),
+        ("dense", r["dense"]), ("log_prob", r["log_prob"]))}
+    occ = r["occupancy"]                                   # (B, Q^3)
+    B, P = occ.shape
+    out["occupancy_mean"] = torch.cat([occ[i:i + 64].double().mean(1) for i in range(0, B, 64)]).cpu().numpy()
+    room = (DUMP_BYTES - sum(v.nbytes for v in out.values())) // 4 - 2 * B      # float32 slots left (row ids are float64)
+    if room < 4096:
+        raise SystemExit(f"bench.py: --dump-outputs: the outputs of {B} shapes leave no room for the occupancy sample in {DUMP_BYTES // 10 ** 6} MB")
+    rng = np.random.default_rng(0)
+    rows = np.sort(rng.choice(B, min(B, max(1, room // P)), replace=False))
+    sel = occ[torch.from_numpy(rows).to(occ.device)]
+    out["occupancy_rows"] = rows.astype(np.float64)
+    if rows.size * P > room:                               # one lattice alone is over the budget: a sample of its points
+        pts = np.sort(rng.choice(P, room // 3, replace=False))     # 4 B value + 8 B float64 id per point
+        sel = sel[:, torch.from_numpy(pts).to(occ.device)]
+        out["occupancy_points"] = pts.astype(np.float64)
+    out["occupancy"] = sel.cpu().numpy().astype(np.float32)
+    assert sum(v.nbytes for v in out.values()) <= DUMP_BYTES
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def synth_tokens(seed, B, Lc, Lz):
     """(pos,val) rows like the representer emits: ascending positions, end-token padded (representers.py:79-103)."""
     rs = np.random.RandomState(seed)
@@ -609,6 +659,9 @@ def main_train(a, rank, world, dev, dist):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     losses.append(float(loss.item()))
+    if a.dump_outputs and rank == 0:         # what training_step returned in the last timed step
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "loss.npy"), np.array([loss.item()], np.float64))
     wait_ms = tr.buckets.wait_ms()        # mean stall of the compute stream in GradBuckets.finish() over the timed steps
     gather_ms = tr.buckets.gather_ms()    # rs_ag: mean wait for the all-gather of the updated parameters
     if rank == 0:
@@ -721,6 +774,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert int(r["steps"]) == a.ar_steps, f"only {r['steps']} of {a.ar_steps} AR steps were run"
+    if a.dump_outputs and rank == 0:      # before any further pass re-uses the sampler's buffers
+        dump_outputs(a.dump_outputs, r)
     rank_crcs = None
     if a.rank_crcs:      # every rank's tokens of the fixed-seed pass (no data-path collective: each rank's result is its single-process result)
         tc = token_checksums(step(CHECK_SEED), B, a)
@@ -746,7 +801,7 @@ def main():
                        "weights": "hash-generated (no checkpoints ship)",
                        "input_selection": (f"synthetic partial clouds whose condition length L_c <= {gpt.Lmax - a.ar_steps} (so that all {a.ar_steps} steps fit "
                                            "the 812-token block; biases the cached length down)"),
-                       "other_batches": "--batch 320 = the round-2 workload (4 x 80-row chains); --batch 192 = round 1 (4 x 48); --batch 16 = BASELINE config 3's batch (one 16-row chain, also measured in this run: config3)"},
+                       "other_batches": "--batch 320 = the round-2 workload (4 x 80-row chains); --batch 192 = round 1 (4 x 48); --batch 16 = BASELINE config 3's batch (one 16-row chain, also measured with --full: config3)"},
             "sanity": sanity,
         }
         if rank_crcs is not None:

@@ -99,15 +99,15 @@ def test_yaml_loader_and_plugin_resolution(tmp_path):
     assert P.load_object("shapeformer.data.partial.VirtualScanSelector") is D.VirtualScanSelector
     with pytest.raises(NotImplementedError):
         P.load_object("shapeformer.data.ar_datasets.imnet_datasets.Imnet2LowResDataset_AR")
-    # the shipped YAMLs resolve unchanged when the reference tree is present (build container only)
-    ref = "/root/reference/configs/shapeformer/shapenet_scale.yaml"
-    if os.path.exists(ref):
-        o = P.get_opt(ref)
-        kw = o["pl_model_opt"]["kwargs"]
-        assert P.load_object(o["pl_model_opt"]["class"]) is P.ShapeFormerModel
-        assert kw["transformer_opt"]["kwargs"]["n_layers"] == [20, 4] and kw["block_size"] == 812
-        d = P.get_opt("/root/reference/configs/demo/demo_vqdif.yaml")
-        assert d["pl_model_opt"]["kwargs"] == P.default_vqdif_kwargs(16) | {"optim_opt": d["pl_model_opt"]["kwargs"]["optim_opt"]}
+    # the shipped YAMLs resolve unchanged: their merged model options as committed fixtures (oracle/make_golden_configs.py,
+    # oracle/make_golden_demo.py)
+    gold = os.path.join(ROOT, "tests", "golden")
+    o = P.get_opt(os.path.join(gold, "shapenet_scale_opt.yaml"))
+    kw = o["pl_model_opt"]["kwargs"]
+    assert P.load_object(o["pl_model_opt"]["class"]) is P.ShapeFormerModel
+    assert kw["transformer_opt"]["kwargs"]["n_layers"] == [20, 4] and kw["block_size"] == 812
+    d = P.get_opt(os.path.join(gold, "demo_ds", "demo_vqdif.yaml"))
+    assert d["pl_model_opt"]["kwargs"] == P.default_vqdif_kwargs(16) | {"optim_opt": d["pl_model_opt"]["kwargs"]["optim_opt"]}
 
 
 def test_rank_striding_matches_reference_rule():
@@ -293,6 +293,39 @@ def test_bench_refuses_inconsistent_rank_environment(monkeypatch):
         with pytest.raises(SystemExit) as e:
             bench.launch_ranks(argparse.Namespace(gpus=2, share_device=False))
         assert f"only {torch.cuda.device_count()} GPU" in str(e.value)
+
+
+def test_bench_plain_run_options_and_output_dump(monkeypatch, tmp_path):
+    """bench.py: a plain run turns every extra measurement off, --full turns them back on (each --no-* option still applies);
+    --dump-outputs writes float32 / float64 arrays within the budget - whole lattices of seeded rows, or seeded points of one
+    lattice when a lattice alone is over it (fake outputs, budget shrunk, no GPU needed)."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert a.steps == 3 and not a.full and a.no_roofline and a.no_kernels and a.no_subrecords and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-kernels"])
+    a = bench.parse()
+    assert a.full and not (a.no_roofline or a.no_subrecords or a.no_cpu_baseline) and a.no_kernels
+    monkeypatch.setattr(bench, "DUMP_BYTES", 400_000)
+    g = torch.Generator().manual_seed(0)
+    for B, P, n_rows, sampled in ((6, 20_000, 3, False), (2, 200_000, 1, True)):
+        ri = lambda hi, *shape: torch.randint(0, hi, shape, generator=g, dtype=torch.int32)
+        r = dict(c_ind=ri(4097, B, 40, 2), Lc=ri(40, B), empty_index=ri(4096, B), dense=ri(4097, B, 16, 16, 16).long(),
+                 log_prob=torch.randn(B, 32, 2, generator=g), occupancy=torch.randn(B, P, generator=g),
+                 state=dict(seq=ri(4097, B, 50, 2), len=ri(50, B)))
+        d = tmp_path / f"B{B}_P{P}"
+        bench.dump_outputs(str(d), r)
+        out = {f.stem: np.load(f) for f in d.iterdir()}
+        assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+        assert sum(v.nbytes for v in out.values()) <= bench.DUMP_BYTES
+        assert np.array_equal(out["tokens"], r["state"]["seq"].numpy()) and np.array_equal(out["dense"], r["dense"].numpy())
+        assert np.allclose(out["occupancy_mean"], r["occupancy"].double().mean(1).numpy(), rtol=0, atol=1e-12)
+        rows = out["occupancy_rows"].astype(np.int64)
+        ref = r["occupancy"].numpy()[rows]
+        assert rows.size == n_rows and ("occupancy_points" in out) == sampled
+        if sampled:
+            ref = ref[:, out["occupancy_points"].astype(np.int64)]
+        assert np.array_equal(out["occupancy"], ref)
 
 
 def test_oracle_frozen_branch_hooks_reproduce_the_natural_forward():
