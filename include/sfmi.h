@@ -375,6 +375,24 @@ int sfmi_mc_count_f32(const float* occ, float iso, int B, int Q, void* workspace
 int sfmi_mc_emit_f32(const float* occ, float iso, int B, int Q, const void* workspace, const int* offsets, float lo0, float lo1,
                      float lo2, float hi0, float hi1, float hi2, float* verts, int* faces, void* stream);
 
+/* ---- Completion metrics (csrc/pointdist.hip): exact nearest neighbours and surface sampling on the device.
+ *      xgutils/geoutil.py:362-377 (points_dist, chamfer_dist: scipy cKDTree.query, k = 1), shapeformer/models/vqdif/common.py:39-122
+ *      (chamfer_distance, batched kd-tree / naive), xgutils/geoutil.py:236-253 (sampleMesh: igl.random_points_on_mesh). -------------- */
+size_t sfmi_nn_dist_workspace_bytes(int B, long long N, long long M);
+/* Ragged sets: P (N,3), Q (M,3) f32; poff / qoff (B+1) int64 exclusive offsets (poff[B] == N, qoff[B] == M, M_b < 2^31).
+ * d2[i] = min over Q_b of fmaf(dz,dz,fmaf(dy,dy,dx*dx)) for query i of P_b (squared Euclidean, direct form); idx (N) int32 or NULL:
+ * that point's index local to Q_b, the lowest index among equal f32 distances.  Deterministic, no atomics.  A query of a set with
+ * M_b == 0 gets (+inf, -1). */
+int sfmi_nn_dist_f32(const float* P, const float* Q, const long long* poff, const long long* qoff, int B, long long N, long long M,
+                     float* d2, int* idx, void* workspace, void* stream);
+size_t sfmi_mesh_sample_workspace_bytes(int B, long long T);
+/* verts (V,3) f32, faces (T,3) int32 with indices local to each shape; voff / toff (B+1) int64 exclusive offsets.  n area-weighted
+ * surface points per shape -> out (B*n,3) f32, face_out (B*n) int32 local face index or NULL; status (B) int32: 0 ok, 1 no faces,
+ * zero / non-finite total area or a vertex index outside the shape (its points are NaN, face -1).  Sample k of a shape depends on
+ * (seed, k) and the mesh only: a batch equals per-shape calls. */
+int sfmi_mesh_sample_f32(const float* verts, const int* faces, const long long* voff, const long long* toff, int B, long long T,
+                         long long n, unsigned long long seed, void* workspace, float* out, int* face_out, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,11 @@ PROTOTYPES = {
     "sfmi_adamw_bias_corrections": (i32, [f32, f32, i32, c_ptr]),
     "sfmi_adamw_multi_shard_bc_f32": (i32, [c_ptr] * 6 + [i32, c_ptr, c_ptr, c_ptr, f32, f32, f32, f32, i32, c_ptr, c_ptr, c_ptr]),
     "sfmi_unflatten_multi_f32": (i32, [c_ptr] * 5 + [i32, c_ptr, c_ptr]),
+    # completion metrics (csrc/pointdist.hip)
+    "sfmi_nn_dist_workspace_bytes": (sz, [i32, i64, i64]),
+    "sfmi_nn_dist_f32": (i32, [c_ptr] * 4 + [i32, i64, i64] + [c_ptr] * 4),
+    "sfmi_mesh_sample_workspace_bytes": (sz, [i32, i64]),
+    "sfmi_mesh_sample_f32": (i32, [c_ptr] * 4 + [i32, i64, i64, C.c_ulonglong] + [c_ptr] * 5),
 }
 
 

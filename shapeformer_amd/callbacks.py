@@ -155,8 +155,12 @@ class VisShapeFormer(VisCallback):
     def __init__(self, temperature=1, sample_n=10, top_k=300, top_p=.9, depth=5, decode_res=128, sample_max_step=512,
                  render_samples=64, end_tokens=None, mask_invalid=True, mask_invalid_completion=False,
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
-                 thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, **kw):
+                 thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
+                 eval_points=10 ** 5, **kw):
         super().__init__(**kw)
+        # eval_metrics: visualize_batch also scores the completions on the device (metrics.evaluate: UHD / TMD against Xct, CD /
+        # F-score at eval_tau against Xbd) from eval_points surface samples per completion mesh -> eval/<name>_metrics.json
+        self.eval_metrics, self.eval_tau, self.eval_points = eval_metrics, eval_tau, eval_points
         # shard_sample_n: a torch.distributed module / process group holder -> the sample_n sequences of the ONE shape are split over
         # its ranks (single-shape option; dist.sample_n_sharded) instead of every rank completing whole shapes
         self.shard_sample_n = shard_sample_n
@@ -239,8 +243,10 @@ class VisShapeFormer(VisCallback):
         for j, (_, t) in enumerate(sets):
             dense[j, t[:, 0]] = t[:, 1]                                      # batch_sparse2dense (common.py:171-189)
         occ = vq.decode_index(torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev), grid_Q=Q, sigmoid=True)["logits"]
-        v, f, voff, toff = mcubes.marching_cubes_dev(occ.reshape(len(sets), Q, Q, Q), self.thresh)
-        v, f = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
+        vd, fd, voff, toff = mcubes.marching_cubes_dev(occ.reshape(len(sets), Q, Q, Q), self.thresh)
+        if self.eval_metrics:
+            out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir))
+        v, f = vd.cpu().numpy().astype(np.float64), fd.cpu().numpy().astype(int)
         eval_pcs = []
         for j, (key, _) in enumerate(sets):
             vert, face = v[voff[j]:voff[j + 1]], f[toff[j]:toff[j + 1]]
@@ -258,3 +264,27 @@ class VisShapeFormer(VisCallback):
                 ed[f"recon_{i}"] = pc
             np.savez(os.path.join(data_dir, "eval", f"{input_name}.npz"), **ed)
         return out
+
+    def _score(self, computed, sets, vd, fd, voff, toff, input_name, data_dir):
+        """eval_metrics: the completion meshes that are exported (key s<i>, >= 10 vertices) sampled on the device with their own
+        counter-hash stream (seed = self.seed; the numpy RNG is untouched), scored against Xct (and Xbd) in the mesh frame
+        (bbox (-1,1)^3, as vis_ind).  -> {"metrics": dict, "metrics_pc": (k, eval_points, 3) device samples}."""
+        import json
+        from . import metrics
+        keep = [j for j, (key, _) in enumerate(sets) if key[0] == "s" and voff[j + 1] - voff[j] >= 10 and toff[j + 1] > toff[j]]
+        if not keep:
+            return {}
+        vs = torch.cat([vd[int(voff[j]):int(voff[j + 1])] for j in keep])
+        fs = torch.cat([fd[int(toff[j]):int(toff[j + 1])] for j in keep])
+        vo = np.concatenate([[0], np.cumsum([voff[j + 1] - voff[j] for j in keep])])
+        to = np.concatenate([[0], np.cumsum([toff[j + 1] - toff[j] for j in keep])])
+        pts, _ = metrics.sample_mesh_dev(vs, fs, vo, to, self.eval_points, seed=self.seed)
+        pc = pts.reshape(len(keep), self.eval_points, 3)
+        batch = computed["batch"]
+        Xbd = batch["Xbd"][0] if "Xbd" in batch else None
+        res = metrics.evaluate(batch["Xct"][0], pc, Xbd=Xbd, tau=self.eval_tau)
+        res["keys"] = [sets[j][0] for j in keep]
+        os.makedirs(os.path.join(data_dir, "eval"), exist_ok=True)
+        with open(os.path.join(data_dir, "eval", f"{input_name}_metrics.json"), "w") as fh:
+            json.dump(res, fh, indent=1)
+        return {"metrics": res, "metrics_pc": pc}
