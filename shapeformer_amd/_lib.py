@@ -160,6 +160,11 @@ PROTOTYPES = {
     "sfmi_nn_dist_f32": (i32, [c_ptr] * 4 + [i32, i64, i64] + [c_ptr] * 4),
     "sfmi_mesh_sample_workspace_bytes": (sz, [i32, i64]),
     "sfmi_mesh_sample_f32": (i32, [c_ptr] * 4 + [i32, i64, i64, C.c_ulonglong] + [c_ptr] * 5),
+    # mesh signed distance and occupancy (csrc/meshsdf.hip)
+    "sfmi_mesh_sdf_workspace_bytes": (sz, [i32, i64, i64]),
+    "sfmi_mesh_sdf_f32": (i32, [c_ptr] * 6 + [i32, i64, i64] + [c_ptr] * 7),
+    "sfmi_mesh_occupancy_f32": (i32, [c_ptr] * 4 + [i32, i64, i32] + [c_ptr] * 6),
+    "sfmi_sdf_jitter_f32": (i32, [c_ptr, i32, i64, i64, f32, f32, C.c_ulonglong, c_ptr, c_ptr]),
 }
 
 
