@@ -178,6 +178,8 @@ int sfmi_skinny16_pack_weight(const float* W, int N, int K, float* out); /* [hos
 int sfmi_ln_fold_pack_f32(const float* W, const float* gamma, const float* beta, const float* bias, float* Wp, float* c1, float* c2, int N,
                           int K, void* stream);
 size_t sfmi_decode_gemm_slab_floats(int M, int N, int S);
+/* out_packed == 0: out (and resid) are row-major (M, ldo); each row is written in float4s up to round_up(N, 4) columns, so ldo >= N and
+ * ldo % 4 == 0 (else SFMI_EINVAL) and out 16-byte aligned; rows >= M are not written.  K % S == 0 and K / S a multiple of 16. */
 int sfmi_decode_gemm_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out,
                          int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt, void* stream);
 /* the same with in-situ launch timing (bench.py `roofline`; no reference counterpart): prof = 3 device u64 {earliest start (armed as

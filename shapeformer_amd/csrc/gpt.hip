@@ -1198,16 +1198,22 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
                               unsigned long long* prof, void* stream) {
   if (!x || !Wp16 || !out || M <= 0 || M > 192 || S <= 0 || K % S || (ln && !c1)) return SFMI_EINVAL;   // larger batches: several chains (gpt.py)
   if (out_packed && N % 16) return SFMI_EINVAL;
+  if (!out_packed && (ldo < N || ldo % 4)) return SFMI_EINVAL;   // row-major rows are written as float4s up to round_up(N, 4)
   if (S > 1 && (!slab || !cnt)) return SFMI_EINVAL;
   if (prof && !pblk) return SFMI_EINVAL;
   const int kslice = K / S;
   // up to 6 row tiles per workgroup; more rows = row groups (grid.z), each of MT tiles: the packed operands must hold groups * MT * 16 rows
-  const int tiles = (M + 15) / 16, groups = (tiles + 5) / 6, MT = (tiles + groups - 1) / groups;
+  const int tiles = (M + 15) / 16;
+  int groups = (tiles + 5) / 6, MT = (tiles + groups - 1) / groups;
   int NWv = (kslice >= 2048 && MT <= 4) ? 16 : 8;
   const int knob_nw = g_tune.dgemm_nw;     // 0 = the rule above; 4 / 8 / 16 k-parts per workgroup where the shape allows it
   if ((knob_nw == 4 || knob_nw == 8 || knob_nw == 16) && kslice % (16 * knob_nw) == 0 && MT <= (knob_nw == 8 ? 6 : 4)) NWv = knob_nw;
   if (kslice % (16 * NWv)) NWv = kslice % 64 == 0 ? 4 : 1;   // narrow models (K-slice not a multiple of 128): fewer k-parts
   if (kslice % (16 * NWv)) return SFMI_EINVAL;
+  // the narrow forms have instances for fewer row tiles (NW = 4: 4, NW = 1: 1): more, smaller row groups instead.  The rows stay within
+  // sfmi_decode_gemm_padded_rows (the two-n-tile form's groups of 3 already pad at least as far: tests/test_decode_ref_cpu.py)
+  const int mt_cap = NWv == 1 ? 1 : NWv == 4 ? 4 : 6;
+  if (MT > mt_cap) { groups = (tiles + mt_cap - 1) / mt_cap; MT = (tiles + groups - 1) / groups; }
   DGemmArgs a;
   a.x = x; a.Wp = Wp16; a.c1 = c1; a.c2 = c2; a.resid = resid; a.out = out; a.M = M; a.N = N; a.K = K; a.ldo = ldo; a.ln = ln; a.act = act;
   a.out_packed = out_packed; a.slab = slab; a.cnt = cnt; a.pblk = pblk; a.prof = prof; a.prio = g_tune.dgemm_prio;
@@ -1220,7 +1226,7 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
     const int g2 = (tiles + 2) / 3, MT2 = (tiles + g2 - 1) / g2;
     dim3 grid2(((N + 15) / 16 + 1) / 2, S, g2);
 #define DG2(MT_) hipLaunchKernelGGL((dgemm_kernel<MT_, 8, 2, 2, P>), grid2, dim3(512), 0, st, a)
-    if (MT2 == 1) DG2(1); else if (MT2 == 2) DG2(2); else DG2(3);
+    if (MT2 == 2) DG2(2); else DG2(3);      // tiles >= 3: MT2 is 2 (4 tiles) or 3, never 1
 #undef DG2
     SFMI_CHECK_LAUNCH();
     return SFMI_OK;
@@ -1229,6 +1235,7 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
   const int steps = kslice / NWv / 16;
   int un = MT == 1 ? 8 : (MT == 2 ? 4 : (MT <= 5 ? 2 : 1));   // UN weight + UN*MT activation float4 loads in flight per wave (5 row tiles: 128 VGPRs; 6: 138 with two)
   if (g_tune.dgemm_un > 0 && g_tune.dgemm_un < un) un = g_tune.dgemm_un;   // the knob can only lower it (deeper forms would spill)
+  while (un & (un - 1)) un &= un - 1;   // a power of two: the instances load UN = 8 / 4 / 2 / 1 steps per batch, and UN must divide steps
   while (un > 1 && steps % un) un >>= 1;
 #define DG(MT_, NW_, UN_) hipLaunchKernelGGL((dgemm_kernel<MT_, NW_, UN_, 1, P>), grid, dim3(64 * NW_), 0, st, a)
 #define DGU8(MT_, NW_) do { if (un >= 8) DG(MT_, NW_, 8); else if (un >= 4) DG(MT_, NW_, 4); else if (un >= 2) DG(MT_, NW_, 2); else DG(MT_, NW_, 1); } while (0)
@@ -1239,10 +1246,9 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
   else if (NWv == 4) {
     if (MT == 1) DG(1, 4, 1); else if (MT == 2) DG(2, 4, 1);
     else if (MT == 3) DGU2(3, 4);
-    else if (MT == 4) DGU2(4, 4);
-    else return SFMI_EINVAL;
+    else DGU2(4, 4);                     // MT <= mt_cap = 4
   }
-  else if (NWv == 1) { if (MT == 1) DG(1, 1, 1); else return SFMI_EINVAL; }
+  else if (NWv == 1) DG(1, 1, 1);        // MT == 1: one row tile per group
   else if (MT == 1) DGU8(1, 8);
   else if (MT == 2) DGU4(2, 8);
   else if (MT <= 5) { if (MT == 3) DGU2(3, 8); else if (MT == 4) DGU2(4, 8); else DGU2(5, 8); }   // 65..96 rows: still the 8-wave kernel

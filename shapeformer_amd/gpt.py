@@ -58,6 +58,12 @@ class CondTupleGPT:
     def __init__(self, state_dict=None, n_embd=1024, n_head=16, n_layers=(20, 4), block_size=812,
                  vocab_sizes=(4097, 4097), extra_vocab_sizes=(4097,), end_tokens=(4096, 4096), device="cuda:0",
                  tuple_n=2, embd_pdrop=0.0, resid_pdrop=0.0, attn_pdrop=0.0, **_ignored):
+        # hyper-parameters outside what the kernels are built for name the limit here, not as an SfmiError from inside a decode step
+        if n_head <= 0 or n_embd % n_head:
+            raise ValueError(f"CondTupleGPT: n_embd={n_embd} must be a multiple of n_head={n_head}")
+        if n_embd // n_head not in (16, 32, 64):
+            raise ValueError(f"CondTupleGPT: head dim n_embd/n_head={n_embd // n_head} (n_embd={n_embd}, n_head={n_head}); "
+                             "the attention kernels (csrc/gpt.hip) are built for head dims 16, 32 and 64")
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise L.SfmiError("CondTupleGPT needs a HIP device (no CPU fallback)")
