@@ -71,12 +71,17 @@ int sfmi_encode_points_down_f32(const float* cloud, const float* wpack, const fl
 /* ---- Conv3d / GroupNorm / pooling: updown.py:79-132 (Downsampler, Upsampler), unet3d.py:79-144,195-293,449-474 -- */
 int sfmi_conv_pack_weight(const float* w, int Cout, int Cin, int KS, float* out); /* [host] (Cout,Cin,k,k,k)->[tap][Cout][Cin] */
 /* nn.Conv3d with fused input GroupNorm-apply (in_scale/in_shift (B,Cin) or NULL), nearest-x2 input upsample (up=1),
- * bias, activation (relu: 0 none, 1 ReLU, 2 GELU-erf).  x (B,Di,Hi,Wi,Cin) -> y (B,Do,Ho,Wo,Cout). */
+ * bias, activation (relu: 0 none, 1 ReLU, 2 GELU-erf).  x (B,Di,Hi,Wi,Cin) -> y (B,Do,Ho,Wo,Cout), Do = ((Di << up) + 2 pad - KS) / stride + 1.
+ * Accepted (anything else: SFMI_EINVAL, nothing launched): B >= 1; Di, Hi, Wi in 1 .. 2^20; Cin a positive multiple of 16; Cout a positive
+ * multiple of 32; KS 1, 2 or 3; stride >= 1; pad 0 .. 2^20; up 0 or 1; every output extent >= 1 ((Di << up) + 2 pad >= KS, likewise H, W);
+ * in_scale and in_shift both given or both NULL. */
 int sfmi_conv3d_cl_f32(const float* x, const float* wT, const float* in_scale, const float* in_shift, const float* bias,
                        float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int KS, int stride, int pad, int up,
                        int relu, void* stream);
 /* Conv3d(k3,p1) of a nearest-x2-upsampled grid as 8 parity-wise 2^3 convolutions of the low-resolution grid with pre-summed
- * weights (8/27 of the FLOPs; updown.py:119-132 Upsample + conv): [host] packer + launcher.  x (B,Di,Hi,Wi,Cin) -> y (B,2Di,..,Cout) */
+ * weights (8/27 of the FLOPs; updown.py:119-132 Upsample + conv): [host] packer + launcher.  x (B,Di,Hi,Wi,Cin) -> y (B,2Di,..,Cout).
+ * Accepted (else SFMI_EINVAL, nothing launched): B >= 1; Di, Hi, Wi in 1 .. 2^20; Cin a positive multiple of 16; Cout a positive multiple
+ * of 32; in_scale and in_shift both given or both NULL. */
 int sfmi_conv_pack_weight_subpixel(const float* w, int Cout, int Cin, float* out);   /* out: 64*Cout*Cin floats */
 int sfmi_conv3d_up2_cl_f32(const float* x, const float* wsub, const float* in_scale, const float* in_shift, const float* bias,
                            float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int relu, void* stream);
@@ -84,7 +89,7 @@ int sfmi_conv3d_up2_cl_f32(const float* x, const float* wsub, const float* in_sc
  * statistics pass over y disappears): partial (B, *splits, Cout, 2) f64 {sum, sum of squares} per shape and tile, consumed by
  * sfmi_groupnorm_coeffs_partial_f32 (V = voxels of y per shape).  Return SFMI_EINVAL BEFORE launching anything when the geometry has no
  * statistics-capable instance (64- or 32-channel stride-1 x-reuse forms): the caller then uses the plain entry + sfmi_groupnorm_coeffs_f32.
- * y is bit-identical to the plain entries'. */
+ * y is bit-identical to the plain entries'.  Argument ranges as for the plain entries; partial and splits both given or both NULL. */
 int sfmi_conv3d_cl_stats_f32(const float* x, const float* wT, const float* in_scale, const float* in_shift, const float* bias, float* y, int B,
                              int Di, int Hi, int Wi, int Cin, int Cout, int KS, int stride, int pad, int up, int relu, double* partial, int* splits,
                              void* stream);
@@ -93,7 +98,8 @@ int sfmi_conv3d_up2_cl_stats_f32(const float* x, const float* wsub, const float*
 int sfmi_groupnorm_coeffs_partial_f32(const double* partial, const float* gamma, const float* beta, float* scale, float* shift, int B, int V, int C,
                                       int S, int groups, float eps, void* stream);
 int sfmi_gn_splits(int V);
-/* nn.GroupNorm statistics -> scale/shift (B,C) with GN(x) == x*scale+shift; partial: B*sfmi_gn_splits(V)*C*2 doubles */
+/* nn.GroupNorm statistics -> scale/shift (B,C) with GN(x) == x*scale+shift; partial: B*sfmi_gn_splits(V)*C*2 doubles.
+ * Accepted by both forms (else SFMI_EINVAL, nothing launched): B, V (and S) >= 1; C a multiple of 4 in 4 .. 1024; groups in 1 .. 64 dividing C. */
 int sfmi_groupnorm_coeffs_f32(const float* x, const float* gamma, const float* beta, float* scale, float* shift,
                               double* partial, int B, int V, int C, int groups, float eps, void* stream);
 int sfmi_affine_cl_f32(const float* x, const float* scale, const float* shift, float* y, int B, long long V, int C, void* stream);
@@ -119,7 +125,10 @@ int sfmi_ar_n_extra_i32(const int* c_pos, const int* z_pos, int* extra, int B, i
 /* ---- CondTupleGPT: transformer/mingpt.py:46-111 (Block), :256-310 (embeddings, two-stage tuple head),
  *      shapeformer.py:54-123 (sample_indices), representers.py:120-155,188-196,432-442, models/common.py:260-299 ---- */
 /* prefill: rows (b,t), t < P, either as a (B,P) rectangle (rowoff NULL; t >= nval[b] is padding) or PACKED back to back
- * (rowoff (B+1) exclusive offsets, M = rowoff[B] rows: no work on padding).  Plain GEMM y[remap(m)] = act(x W^T + bias) + resid */
+ * (rowoff (B+1) exclusive offsets, M = rowoff[B] rows: no work on padding).  Plain GEMM y[remap(m)] = act(x W^T + bias) + resid[remap(m)],
+ * remap(m) = (m / out_group) * out_group_stride + m % out_group (out_group 0: no remap).  Accepted (else SFMI_EINVAL, nothing launched):
+ * M in 1 .. 2^31 - 1; K a positive multiple of 16; N a positive multiple of 32; act 0 none / 1 ReLU / 2 GELU-erf; out_group >= 0, and
+ * out_group_stride >= out_group when out_group > 0 (a smaller stride would map two rows onto one). */
 int sfmi_gemm_f32(const float* x, const float* W, const float* bias, const float* resid, float* y, long long M, int N, int K,
                   int act, long long out_group, long long out_group_stride, void* stream);
 /* plain large GEMMs through rocBLAS, bound lazily with dlopen (csrc/blas.hip): row-major C = alpha op(A) op(B) + beta C;

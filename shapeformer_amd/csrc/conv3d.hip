@@ -637,8 +637,12 @@ int sfmi_conv3d_cl_stats_f32(const float* x, const float* wT, const float* in_sc
                              int Di, int Hi, int Wi, int Cin, int Cout, int KS, int stride, int pad, int up, int relu, double* partial, int* splits,
                              void* stream) {
   if ((partial == nullptr) != (splits == nullptr)) return SFMI_EINVAL;
-  if (!x || !wT || !y || B <= 0 || Cin % KC || Cout % 32 || (KS != 1 && KS != 2 && KS != 3)) return SFMI_EINVAL;
+  if (!x || !wT || !y || B <= 0 || Cin < KC || Cin % KC || Cout < 32 || Cout % 32 || (KS != 1 && KS != 2 && KS != 3)) return SFMI_EINVAL;
   if ((in_scale == nullptr) != (in_shift == nullptr)) return SFMI_EINVAL;
+  // geometry: everything below divides by `stride`, shifts by `up` and casts the tile count to unsigned
+  if (stride < 1 || pad < 0 || (up != 0 && up != 1) || Di < 1 || Hi < 1 || Wi < 1 || Di > (1 << 20) || Hi > (1 << 20) || Wi > (1 << 20) ||
+      pad > (1 << 20)) return SFMI_EINVAL;
+  if ((Di << up) + 2 * pad < KS || (Hi << up) + 2 * pad < KS || (Wi << up) + 2 * pad < KS) return SFMI_EINVAL;   // an output extent < 1
   ConvArgs a;
   a.x = x; a.wT = wT; a.in_scale = in_scale; a.in_shift = in_shift; a.bias = bias; a.y = y;
   a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.KS = KS; a.stride = stride; a.pad = pad;
@@ -661,7 +665,8 @@ int sfmi_conv3d_cl_stats_f32(const float* x, const float* wT, const float* in_sc
 // used by the transformer PREFILL (mingpt.py:46-111 Linear layers at M = B*L_c rows).
 int sfmi_gemm_f32(const float* x, const float* W, const float* bias, const float* resid, float* y, long long M, int N,
                   int K, int act, long long out_group, long long out_group_stride, void* stream) {
-  if (!x || !W || !y || M <= 0 || K % KC || N % 32 || M > 0x7fffffffLL) return SFMI_EINVAL;
+  if (!x || !W || !y || M <= 0 || K < KC || K % KC || N < 32 || N % 32 || M > 0x7fffffffLL) return SFMI_EINVAL;
+  if (out_group < 0 || (out_group > 0 && out_group_stride < out_group)) return SFMI_EINVAL;   // a remap must not fold rows onto each other
   ConvArgs a;
   a.x = x; a.wT = W; a.in_scale = nullptr; a.in_shift = nullptr; a.bias = bias; a.y = y; a.resid = resid;
   a.out_group = out_group; a.out_group_stride = out_group_stride;
@@ -712,8 +717,9 @@ int sfmi_conv3d_up2_cl_f32(const float* x, const float* wsub, const float* in_sc
 // launched when this geometry has no statistics-capable instance (the caller then takes sfmi_conv3d_up2_cl_f32 + sfmi_groupnorm_coeffs_f32).
 int sfmi_conv3d_up2_cl_stats_f32(const float* x, const float* wsub, const float* in_scale, const float* in_shift, const float* bias,
                                  float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int relu, double* partial, int* splits, void* stream) {
-  if (!x || !wsub || !y || B <= 0 || Cin % KC || Cout % 32 || ((partial == nullptr) != (splits == nullptr))) return SFMI_EINVAL;
+  if (!x || !wsub || !y || B <= 0 || Cin < KC || Cin % KC || Cout < 32 || Cout % 32 || ((partial == nullptr) != (splits == nullptr))) return SFMI_EINVAL;
   if ((in_scale == nullptr) != (in_shift == nullptr)) return SFMI_EINVAL;
+  if (Di < 1 || Hi < 1 || Wi < 1 || Di > (1 << 20) || Hi > (1 << 20) || Wi > (1 << 20)) return SFMI_EINVAL;
   int tps = 0;
   for (int par = partial ? -1 : 0; par < 8; ++par) {      // par = -1: dry pass that only asks whether the statistics instance exists
     ConvArgs a;
@@ -744,7 +750,8 @@ int sfmi_gn_splits(int V) { return V >= 32768 ? 64 : (V >= 4096 ? 16 : (V >= 512
 // GN(x) == x*scale + shift.  partial: workspace of B*sfmi_gn_splits(V)*C*2 doubles.
 int sfmi_groupnorm_coeffs_f32(const float* x, const float* gamma, const float* beta, float* scale, float* shift,
                               double* partial, int B, int V, int C, int groups, float eps, void* stream) {
-  if (!x || !gamma || !beta || !scale || !shift || !partial || C % 4 || C > 1024 || C % groups || groups > 64) return SFMI_EINVAL;
+  if (!x || !gamma || !beta || !scale || !shift || !partial || B < 1 || V < 1 || C < 4 || C % 4 || C > 1024 || groups < 1 || groups > 64 || C % groups)
+    return SFMI_EINVAL;      // (groups = 0 was a division by zero on the host)
   hipStream_t st = (hipStream_t)stream;
   const int S = sfmi_gn_splits(V);
   hipLaunchKernelGGL(chan_stats_kernel, dim3(S, B), dim3(256), 0, st, x, partial, V, C, S);
@@ -756,7 +763,8 @@ int sfmi_groupnorm_coeffs_f32(const float* x, const float* gamma, const float* b
 // GroupNorm coefficients from statistics partials a convolution left behind (sfmi_conv3d_*_stats_f32): partial (B, S, C, 2) f64, V voxels per shape
 int sfmi_groupnorm_coeffs_partial_f32(const double* partial, const float* gamma, const float* beta, float* scale, float* shift, int B, int V, int C,
                                       int S, int groups, float eps, void* stream) {
-  if (!partial || !gamma || !beta || !scale || !shift || B <= 0 || V <= 0 || S <= 0 || C % 4 || C > 1024 || C % groups || groups > 64) return SFMI_EINVAL;
+  if (!partial || !gamma || !beta || !scale || !shift || B <= 0 || V <= 0 || S <= 0 || C < 4 || C % 4 || C > 1024 || groups < 1 || groups > 64 || C % groups)
+    return SFMI_EINVAL;
   hipLaunchKernelGGL(gn_coeffs_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, partial, gamma, beta, scale, shift, V, C, S, groups, eps);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

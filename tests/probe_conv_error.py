@@ -1,8 +1,6 @@
-"""Where the fp32 noise of the HIP decoder comes from (not a pytest file; GPU box:  python tests/probe_conv_error.py).
-
-The float64 evaluation of the oracle is the rounding-free value.  Per UNet3D layer (GroupNorm -> conv3 -> ReLU), on the float64
-layer INPUT rounded to fp32:  rms error relative to rms(output) of (a) torch-CPU fp32, (b) the HIP layer per conv_xreuse form.
-Then the whole chain: HIP grid vs float64 grid, float64 SDF query on the HIP grid vs float64 logits (conv-stack share), HIP logits."""
+"""Whole-chain fp32 noise of the HIP decoder against the float64 oracle (not a pytest file; GPU box:  python tests/probe_conv_error.py).
+The per-layer figures it prints are asserted by tests/test_conv_kernels_gpu.py::test_unet3d_accumulation_rms_gate; what remains
+probe-only is the chain: HIP grid and logits per conv_xreuse form against the float64 evaluation of the oracle."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
