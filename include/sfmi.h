@@ -234,6 +234,12 @@ int sfmi_set_len_i32(int* len, const int* src, int B, int delta, void* stream);
 
 /* ---- Training step of the transformer (csrc/train.hip): shapeformer.py:26-46,132-207 (forward/loss/AdamW groups),
  *      backward of mingpt.py:46-111; GEMM-shaped gradients reuse sfmi_gemm_f32 on transposed operands ------------------- */
+/* Argument ranges (anything else: SFMI_EINVAL before any launch).  transpose: R, C > 0, ldin >= C, Rpad >= R (out is (C, Rpad), columns
+ * R .. Rpad-1 zero).  colsum / colsum_ws: M, N > 0, ld >= N.  col_reduce: 1 <= njobs <= 8, M > 0, per job N > 0, N % 4 == 0, ld % 4 == 0,
+ * ld >= N.  ce_fwd_bwd: M > 0, V > 0, ld >= V, L > 0 (row m is position m % L), t0 >= 0.  attn_bwd / attn_bwd_lse / attn_train_fwd_small:
+ * B, L, H > 0, D == 64 * H (attn_bwd_lse: also 64 % H == 0), 0 <= attn_drop_p < 1.  layernorm_bwd_rows*: M, D > 0, 0 <= drop_p < 1; with
+ * dx2 != NULL and D not in {128, 256, 512, 1024} also (M * D) % 4 == 0 (the dropout is then its own float4 launch).  dropout: n > 0,
+ * n % 4 == 0, 0 <= p < 1.  adamw*: step > 0 (or bc_dev != NULL). */
 int sfmi_transpose_f32(const float* in, float* out, int R, int C, int ldin, int Rpad, void* stream);
 int sfmi_colsum_f32(const float* x, float* out, int M, int N, int ld, int accumulate, void* stream);          /* bias gradients */
 int sfmi_colsum_slices(int M, int N);

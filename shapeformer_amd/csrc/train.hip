@@ -969,13 +969,13 @@ __global__ __launch_bounds__(256) void unflatten_multi_kernel(float* const* p, c
 extern "C" {
 
 int sfmi_transpose_f32(const float* in, float* out, int R, int C, int ldin, int Rpad, void* stream) {
-  if (!in || !out || R <= 0 || C <= 0 || Rpad < R) return SFMI_EINVAL;
+  if (!in || !out || R <= 0 || C <= 0 || Rpad < R || ldin < C) return SFMI_EINVAL;
   hipLaunchKernelGGL(transpose_kernel, dim3((C + 31) / 32, (Rpad + 31) / 32), dim3(256), 0, (hipStream_t)stream, in, out, R, C, ldin, Rpad);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
 int sfmi_colsum_f32(const float* x, float* out, int M, int N, int ld, int accumulate, void* stream) {
-  if (!x || !out || M <= 0 || N <= 0) return SFMI_EINVAL;
+  if (!x || !out || M <= 0 || N <= 0 || ld < N) return SFMI_EINVAL;
   hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, x, out, M, N, ld, accumulate);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -990,7 +990,7 @@ int sfmi_colsum_slices(int M, int N) {
 }
 // same result contract as sfmi_colsum_f32 (fixed summation order), with scratch of sfmi_colsum_slices(M,N)*N floats
 int sfmi_colsum_ws_f32(const float* x, float* out, int M, int N, int ld, int accumulate, float* scratch, void* stream) {
-  if (!x || !out || !scratch || M <= 0 || N <= 0) return SFMI_EINVAL;
+  if (!x || !out || !scratch || M <= 0 || N <= 0 || ld < N) return SFMI_EINVAL;
   const int RS = sfmi_colsum_slices(M, N), rows_per = (M + RS - 1) / RS;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(colsum_part_kernel, dim3((N + 63) / 64, RS), dim3(256), 0, st, x, scratch, M, N, ld, rows_per);
@@ -1033,6 +1033,8 @@ int sfmi_layernorm_bwd_f32(const float* dy, const float* x, const float* gamma, 
 int sfmi_layernorm_bwd_rows_drop_sd_f32(const float* dy, const float* x, const float* gamma, const float* dres, float* dx, float* stats,
                                         float* dx2, float drop_p, unsigned drop_seed, const unsigned* drop_seed_dev, int M, int D, void* stream) {
   if (!dy || !x || !gamma || !dx || !stats || M <= 0 || D <= 0 || drop_p < 0.f || drop_p >= 1.f) return SFMI_EINVAL;
+  const bool wave_form = D == 1024 || D == 512 || D == 256 || D == 128;
+  if (!wave_form && dx2 && ((long long)M * D) % 4) return SFMI_EINVAL;      // the separate dropout launch moves float4s
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((M + 3) / 4);
   if (D == 1024) hipLaunchKernelGGL(ln_bwd_rows_wave_kernel<16>, grid, dim3(256), 0, st, dy, x, gamma, dres, dx, stats, dx2, M, drop_p, drop_seed, drop_seed_dev);
@@ -1043,7 +1045,6 @@ int sfmi_layernorm_bwd_rows_drop_sd_f32(const float* dy, const float* x, const f
     hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3(M), dim3(256), 0, st, dy, x, gamma, dres, dx, stats, D);
     if (dx2) {
       const long long n = (long long)M * D;
-      if (n % 4) return SFMI_EINVAL;
       hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, dx, dx2, n / 4, drop_p, 1.0f / (1.0f - drop_p), drop_seed, drop_seed_dev);
     }
   }
@@ -1071,7 +1072,7 @@ int sfmi_col_reduce_f32(int njobs, const int* kind, const float* const* a, const
   ColJobs J;
   int blk = 0;
   for (int i = 0; i < njobs; ++i) {
-    if (!a[i] || !out[i] || N[i] <= 0 || N[i] % 4 || ld[i] % 4 || (kind[i] != 0 && kind[i] != 1)) return SFMI_EINVAL;
+    if (!a[i] || !out[i] || N[i] <= 0 || N[i] % 4 || ld[i] % 4 || ld[i] < N[i] || (kind[i] != 0 && kind[i] != 1)) return SFMI_EINVAL;
     if (kind[i] == 1 && (!x || !stats || !out2 || !x[i] || !stats[i] || !out2[i])) return SFMI_EINVAL;
     J.j[i].a = a[i]; J.j[i].x = x ? x[i] : nullptr; J.j[i].stats = stats ? stats[i] : nullptr; J.j[i].out = out[i];
     J.j[i].out2 = out2 ? out2[i] : nullptr; J.j[i].N = N[i]; J.j[i].ld = ld[i]; J.j[i].kind = kind[i]; J.j[i].blk0 = blk;
@@ -1087,7 +1088,7 @@ int sfmi_col_reduce_f32(int njobs, const int* kind, const float* const* a, const
 // F.cross_entropy forward + backward over rows m=(b,t), active for t >= t0 (shapeformer.py:132-140)
 int sfmi_ce_fwd_bwd_f32(const float* logits, const int* target, float* loss_rows, float* dlogits, int M, int V, int ld, int L,
                         int t0, float scale, void* stream) {
-  if (!logits || !target || !loss_rows || !dlogits || M <= 0) return SFMI_EINVAL;
+  if (!logits || !target || !loss_rows || !dlogits || M <= 0 || V <= 0 || ld < V || L <= 0 || t0 < 0) return SFMI_EINVAL;
   hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, logits, target, loss_rows, dlogits, V, ld, L, t0, scale);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -1097,7 +1098,7 @@ int sfmi_ce_fwd_bwd_f32(const float* logits, const int* target, float* loss_rows
 // the forward's log-sum-exps; then the fused dQ | dK/dV launch.
 int sfmi_attn_bwd_f32(const float* qkv, const float* y, const float* dy, float* lse, float* dqkv, int B, int L, int D, int H,
                       float drop_p, unsigned drop_seed, void* stream) {
-  if (!qkv || !y || !dy || !lse || !dqkv || D / H != 64 || D % H || drop_p < 0.f || drop_p >= 1.f) return SFMI_EINVAL;
+  if (!qkv || !y || !dy || !lse || !dqkv || B <= 0 || L <= 0 || H <= 0 || D != 64 * H || drop_p < 0.f || drop_p >= 1.f) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int nqb = (L + 63) / 64;
   float* delta = lse + (size_t)B * H * L;
@@ -1110,7 +1111,7 @@ int sfmi_attn_bwd_f32(const float* qkv, const float* y, const float* dy, float* 
 // + the fused launch.  H must divide 64 (head dim 64: D = 64 H).
 int sfmi_attn_bwd_lse_sd_f32(const float* qkv, const float* y, const float* dy, const float* lse, float* delta, float* dqkv, int B, int L,
                              int D, int H, float drop_p, unsigned drop_seed, const unsigned* drop_seed_dev, void* stream) {
-  if (!qkv || !y || !dy || !lse || !delta || !dqkv || H <= 0 || D != 64 * H || 64 % H || drop_p < 0.f || drop_p >= 1.f) return SFMI_EINVAL;
+  if (!qkv || !y || !dy || !lse || !delta || !dqkv || B <= 0 || L <= 0 || H <= 0 || D != 64 * H || 64 % H || drop_p < 0.f || drop_p >= 1.f) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)(((long long)B * L + 3) / 4)), dim3(256), 0, st, y, dy, delta, B, L, D, H);
   attn_bwd_fused_launch(st, qkv, dy, lse, delta, dqkv, B, L, D, H, drop_p, drop_seed, drop_seed_dev);

@@ -1,13 +1,33 @@
 """GPU parity: training step of CondTupleGPT (forward loss, every parameter gradient, AdamW update) through the C ABI
 vs the CPU oracle's autograd (oracle/gpt_oracle.py is pinned to the reference forward/loss)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import train_ref as R   # noqa: E402
+
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
+# Gradient gate of a whole step, per trainer tensor (max-normalised): GATE_X times the error of the oracle's OWN fp32 CPU autograd against
+# the oracle in float64 (train_ref.step_ratios; that error floored at U = 2^-24).  The project's single-kernel gates sit at 2 - 4 x CPU
+# fp32 (convolution rms 2.4 x, sgemm 2e-6 .. 4e-6); a gradient passes through about a dozen such kernels whose errors add in quadrature:
+# 2.4 sqrt(12) ~ 8.  Measured on one MI355X (largest ratio over the tensors): eval 1.5, train mode 1.2, 1396 rows 2.6 on the project's GEMM and
+# 6.9 on the library GEMM (L0.wqkv; its next tensors 4.9 and 4.7).  The former 2e-3 is kept nowhere.
+GATE_X = 8.0
+
+
+def _assert_grads(tr, sd, cfg, c, z, dropout, what, oracle=None):
+    """every gradient of `tr` against the float64 oracle under the GATE_X rule; returns the float64 loss"""
+    l64, rows = R.step_ratios(sd, cfg, c, z, dropout, _map(tr, cfg), lambda name: tr.grad[name].cpu(), oracle)
+    for name, e_gpu, e_cpu, ratio in rows:
+        print(f"[{what}] {name:14s} gpu {e_gpu:.2e}  cpu fp32 {e_cpu:.2e}  ratio {ratio:.2f}")
+    bad = [(name, round(ratio, 2)) for name, _, _, ratio in rows if not ratio <= GATE_X]
+    assert not bad, (what, bad)
+    return l64
 
 
 def _setup(dev):
@@ -60,17 +80,8 @@ def test_loss_and_every_gradient_vs_oracle_autograd(dev):
     tr = GPTTrainer(g)
     tr.debug_poison_grads = True      # every gradient outside the embedding tables must be WRITTEN by the backward pass (the step only zeroes those)
     loss = tr.loss_and_grad(c, z).item()
-    want_loss, og, _ = _oracle_grads(sd, cfg, c, z)
+    want_loss = _assert_grads(tr, sd, cfg, c, z, None, "eval 128")
     assert abs(loss - want_loss) < 1e-5 * max(1.0, abs(want_loss))
-    worst = 0.0
-    for name, keys in _map(tr, cfg).items():
-        want = torch.cat([og[k].reshape(-1, og[k].shape[-1]) if og[k].dim() > 1 else og[k] for k in keys], 0)
-        got = tr.grad[name].cpu().reshape(want.shape)
-        scale = want.abs().max().item() + 1e-12
-        err = (got - want).abs().max().item() / scale
-        worst = max(worst, err)
-        assert err < 2e-3, (name, err, scale)   # fp32 reassociation across ~1e3-term reductions; typical 1e-5
-    print(f"worst relative gradient error {worst:.2e}")
     # bit-reproducible gradients (fixed-order reductions / fixed-point atomics)
     g1 = tr.flat_grad.clone()
     tr.loss_and_grad(c, z)
@@ -87,16 +98,8 @@ def test_train_mode_dropout_loss_and_every_gradient_vs_oracle_autograd(dev):
     tr = GPTTrainer(g, pdrop=pd)
     l_eval = tr.loss_and_grad(c, z).item()
     loss = tr.loss_and_grad(c, z, dropout_key="k7").item()
-    want_loss, og, _ = _oracle_grads(sd, cfg, c, z, dropout=dict(key="k7", p=pd))
+    want_loss = _assert_grads(tr, sd, cfg, c, z, dict(key="k7", p=pd), "train 128")
     assert abs(loss - want_loss) < 1e-5 * max(1.0, abs(want_loss)) and abs(loss - l_eval) > 1e-3      # the masks are live
-    worst = 0.0
-    for name, keys in _map(tr, cfg).items():
-        want = torch.cat([og[k].reshape(-1, og[k].shape[-1]) if og[k].dim() > 1 else og[k] for k in keys], 0)
-        got = tr.grad[name].cpu().reshape(want.shape)
-        err = (got - want).abs().max().item() / (want.abs().max().item() + 1e-12)
-        worst = max(worst, err)
-        assert err < 2e-3, (name, err)
-    print(f"train mode (dropout {pd}): worst relative gradient error {worst:.2e}")
     # another key -> other masks; training_step draws a fresh key per step and still trains
     assert abs(tr.loss_and_grad(c, z, dropout_key="k8").item() - loss) > 1e-4
     tr2 = GPTTrainer(g, lr=1e-3, pdrop=(0.01, 0.01, 0.01))
@@ -175,7 +178,7 @@ def test_library_gemm_binding_and_large_row_training_path(dev, monkeypatch):
             out[bb, :n, 1] = rs.randint(0, 4096, n)
         return torch.from_numpy(out)
     c, z = rows(150), rows(200)
-    want_loss, og, _ = _oracle_grads(sd, cfg, c, z)
+    oracle = R.oracle_pair(sd, cfg, c, z, None)
     # default: every GEMM of the step on csrc/sgemm.hip (forward, dX = dY W, dW = dY^T X with split-K); SFMI_ROCBLAS=1: library
     for use_lib in (False, True):
         if use_lib:
@@ -183,12 +186,8 @@ def test_library_gemm_binding_and_large_row_training_path(dev, monkeypatch):
         tr = GPTTrainer(g)
         assert tr._blas() == use_lib
         loss = tr.loss_and_grad(c, z).item()
+        want_loss = _assert_grads(tr, sd, cfg, c, z, None, f"1396 rows, library GEMM {use_lib}", oracle)
         assert abs(loss - want_loss) < 1e-5 * max(1.0, abs(want_loss))
-        for name, keys in _map(tr, cfg).items():
-            want = torch.cat([og[k].reshape(-1, og[k].shape[-1]) if og[k].dim() > 1 else og[k] for k in keys], 0)
-            got = tr.grad[name].cpu().reshape(want.shape)
-            err = (got - want).abs().max().item() / (want.abs().max().item() + 1e-12)
-            assert err < 2e-3, (name, use_lib, err)
 
 
 @pytest.mark.parametrize("B,L,H", [(1, 499, 16), (2, 150, 2), (3, 64, 4), (1, 33, 2), (4, 300, 16)])
