@@ -440,6 +440,31 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
 int sfmi_sdf_jitter_f32(const float* X, int B, long long n, long long n_near, float near_std, float far_std, unsigned long long seed,
                         float* out, void* stream);
 
+/* ---- Hidden-point removal (csrc/hpr.hip): which points of a cloud a camera sees, by vertex membership in the convex hull of the
+ *      spherically flipped cloud plus the viewpoint.  xgutils/geoutil.py:58-74 (hidden_point_removal: spherical flip, then
+ *      scipy.spatial.ConvexHull), shapeformer/data/partial.py:127-146 (VirtualScanSelector: camera on a sphere, resample, jitter). -- */
+size_t sfmi_hpr_workspace_bytes(int B, long long N);
+/* Ragged clouds X (N,3) f32 (is_f64 = 0) or f64 (is_f64 = 1) with off (B+1) int64 exclusive offsets (N < 2^31); cam (B,3) f64 [device];
+ * param: the flip sphere has radius max|x - cam| * 10^param (the reference uses pi).  Flip and linear programs in f64.
+ * order (N) int32 or NULL: per shape a permutation of its local indices, the order in which the linear programs take their constraints
+ *           (performance only: neighbours in it should lie on nearby view rays; NULL = index order).  It must depend on the shape and its
+ *           camera only for the batch = per-shape guarantee to hold.
+ *   visible (N) uint8: 1 where the point is a vertex of the hull of {flipped points} + {viewpoint}; of a class of bitwise-equal points
+ *           only the LOWEST index can be 1;  count (B) int32: visible points per shape;
+ *   status (B) int32: 0 ok, 1 fewer than 4 points, 2 a non-finite coordinate, 3 a point at the camera; such a shape's mask is all 0;
+ *   evals (N,2) uint32 or NULL: constraint evaluations spent on each point, in the scan and in the re-solves (for tools/kbench_hpr.py).
+ * Deterministic, no atomics; a shape's mask depends on that shape and its camera only (a batch equals per-shape calls bitwise). */
+int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const double* cam, const int* order, int B, long long N, double param,
+                     unsigned char* visible, int* count, int* status, unsigned* evals, void* workspace, void* stream);
+/* The selector's resample: out (B, context_N, 3) f32, row k of shape b = the floor(u * count[b])-th visible point in ascending index order
+ * (count[b] <= 2: the floor(u * N_b)-th point of the whole cloud, the reference's fallback), u the counter-hash uniform of the library
+ * keyed by (seed, shape0 + b) at index k.  prefix (N) int32: exclusive prefix sum of `visible` over the whole ragged batch.
+ * noise > 0: plus noise * a hash normal per coordinate, clipped to [-1, 1] (partial.py's _jitter).  Touches no global RNG; shape b of a
+ * batch equals a single-shape call with shape0 + b.  A shape without points gives NaN rows. */
+int sfmi_hpr_resample_f32(const void* X, int is_f64, const unsigned char* visible, const int* prefix, const long long* off,
+                          const int* count, int B, long long N, int context_N, unsigned seed, int shape0, float noise, float* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

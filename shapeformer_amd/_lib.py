@@ -165,6 +165,10 @@ PROTOTYPES = {
     "sfmi_mesh_sdf_f32": (i32, [c_ptr] * 6 + [i32, i64, i64] + [c_ptr] * 7),
     "sfmi_mesh_occupancy_f32": (i32, [c_ptr] * 4 + [i32, i64, i32] + [c_ptr] * 6),
     "sfmi_sdf_jitter_f32": (i32, [c_ptr, i32, i64, i64, f32, f32, C.c_ulonglong, c_ptr, c_ptr]),
+    # hidden-point removal (csrc/hpr.hip)
+    "sfmi_hpr_workspace_bytes": (sz, [i32, i64]),
+    "sfmi_hpr_visible": (i32, [c_ptr, i32, c_ptr, c_ptr, c_ptr, i32, i64, C.c_double] + [c_ptr] * 6),
+    "sfmi_hpr_resample_f32": (i32, [c_ptr, i32] + [c_ptr] * 4 + [i32, i64, i32, C.c_uint, i32, f32, c_ptr, c_ptr]),
 }
 
 

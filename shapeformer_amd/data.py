@@ -13,8 +13,9 @@ same points):
   collate_to_device                       GPU-side batching: stack on the host once, one H2D copy per key
 
 This is host-side numpy/scipy like the reference (its DataLoader workers never touch the GPU); the device work starts
-at `collate_to_device`.  h5py is not part of this image: Imnet2LowResDataset imports it lazily and also accepts the
-same arrays as a directory of .npy files (`<dataset>/<split>/{Xbd,Ytg,cate_*}.npy`).
+at `collate_to_device`.  The one opt-in exception: `DataModule.batches(..., partial="device")` defers the virtual scans
+(VirtualScanSelector's hidden-point removal, qhull on the host by default) to hpr.virtual_scan_dev on the device.
+h5py is not part of this image: Imnet2LowResDataset imports it lazily and also accepts the same arrays as a directory of .npy files (`<dataset>/<split>/{Xbd,Ytg,cate_*}.npy`).
 """
 from __future__ import annotations
 
@@ -91,8 +92,12 @@ class VirtualScanSelector:
     def __init__(self, radius=10, context_N=512, noise=0., manual_cameras=None):
         self.radius, self.context_N, self.noise, self.manual_cameras = radius, context_N, noise, manual_cameras or {}
 
+    def draw_camera(self):
+        """The camera of the next scan: the numpy draw `__call__` starts with."""
+        return sample_sphere(1)[0] * self.radius
+
     def __call__(self, Xbd, index=None, **_):
-        cam = sample_sphere(1)[0] * self.radius
+        cam = self.draw_camera()
         Xct = hidden_point_removal(Xbd, cam)
         if Xct.shape[0] <= 2:
             Xct = Xbd
@@ -168,11 +173,13 @@ class TransformDataset:
     def __getitem__(self, ind):
         item = self.dset[ind]
         if "Xbd" in item:
-            ys = {k: item[k].copy() for k in ("Xbd", "Xct") if k in item}
+            # Xsrc / cam: a deferred virtual scan (Imnet2LowResDataset(defer_partial=True)).  Visibility is invariant under a
+            # similarity applied to the cloud and the camera jointly, so the pair goes through the same transform as Xbd.
+            ys = {k: item[k].copy() for k in ("Xbd", "Xct", "Xsrc", "cam") if k in item}
             if self.apply_Xtg and "Xtg" in item:
                 ys["Xtg"] = item["Xtg"].copy()
             for k, v in apply_random_transforms(item["Xbd"].copy(), ys, self.mode, self.max_voxels, self.voxel_dim).items():
-                item[k] = v.astype(np.float32)
+                item[k] = v.astype(np.float64 if k == "cam" else np.float32)
         return item
 
 
@@ -249,8 +256,13 @@ def balanced_sampling2(Xbd, Xtg, Ytg, target_N=4096, x_dim=3, random_scale=.1):
 class Imnet2LowResDataset:
     def __init__(self, dataset="IMNet2_64", cate="all", zoomfac=1, duplicate_size=1, split="train", boundary_N=2048,
                  target_N=-1, grid_dim=64, weighted_sampling=False, Xbd_as_Xct=False, Xct_as_Xbd=False, partial_opt=None,
-                 root="datasets"):
+                 root="datasets", defer_partial=False):
+        """defer_partial=True with a VirtualScanSelector: the item carries `Xsrc` (the stored cloud, f32) and `cam` ((1,3) f64, the
+        selector's camera draw) in place of `Xct`, and no hull is computed: hpr.virtual_scan_dev makes Xct on the device
+        (DataModule.batches(partial="device")).  The selector's resample / jitter draws are then not taken from numpy's
+        global stream, so the draws after the camera differ from the host path's."""
         self.weighted_sampling = bool(weighted_sampling)
+        self.defer_partial = bool(defer_partial)
         self.store = _ArrayStore(os.path.join(root, dataset, f"{split}.hdf5"))
         n = self.store.length("Xbd")
         if isinstance(cate, str):
@@ -272,7 +284,11 @@ class Imnet2LowResDataset:
         o_ind = index % self.length
         src = self.subset[o_ind]
         Xbd = self.store.get("Xbd", src)
-        Xct = np.float32(Xbd if self.Xbd_as_Xct else self.partial_selector(Xbd, index=o_ind))
+        deferred = self.defer_partial and not self.Xbd_as_Xct and isinstance(self.partial_selector, VirtualScanSelector)
+        if deferred:
+            Xsrc, cam = np.float32(Xbd), np.asarray(self.partial_selector.draw_camera(), np.float64)[None]
+        else:
+            Xct = np.float32(Xbd if self.Xbd_as_Xct else self.partial_selector(Xbd, index=o_ind))
         Xbd = Xbd[np.random.choice(Xbd.shape[0], self.boundary_N, replace=True)]
         Ytg = np.unpackbits(self.store.get("Ytg", src), axis=-1)[..., None]      # bit-packed occupancy of the grid_dim^3 lattice
         Xtg = self.all_Xtg
@@ -281,6 +297,8 @@ class Imnet2LowResDataset:
         elif self.target_N != -1 and not all_target:
             pick = np.random.choice(Xtg.shape[0], self.target_N, replace=True)
             Xtg, Ytg = Xtg[pick], Ytg[pick]
+        if deferred:                     # Xct_as_Xbd is applied where Xct is made (DataModule.batches)
+            return dict(Xsrc=Xsrc, cam=cam, Xbd=Xbd.astype(np.float32), Xtg=Xtg.astype(np.float32), Ytg=Ytg.astype(np.float32))
         if self.Xct_as_Xbd:
             Xbd = Xct
         return dict(Xct=Xct.astype(np.float32), Xbd=Xbd.astype(np.float32), Xtg=Xtg.astype(np.float32), Ytg=Ytg.astype(np.float32))
@@ -363,9 +381,40 @@ class DataModule:
     def visual_dataloader(self, shuffle=False):
         return self._loader(self.visual_set, 1, False, workers=1)
 
-    def batches(self, split, device, batch_size=None, indices=None):
+    def batches(self, split, device, batch_size=None, indices=None, partial="host", seed=0):
+        """Device-resident batches of the split.  partial="host" (default): the items as the datasets make them.
+        partial="device": the virtual scans run on the device (hpr.virtual_scan_dev).  The Imnet2LowResDataset at the bottom of
+        the `.dset` chain defers its VirtualScanSelector (items carry the stored cloud `Xsrc` and the camera `cam`, transformed
+        together with Xbd by a TransformDataset), the cameras stay f64, and Xct = virtual_scan_dev(Xsrc, cams=cam) with the
+        selector's context_N / noise; item p of the index list is seeded by (seed, p).  The batch has the host path's keys.
+        In this mode the resample and jitter draws are counter hashes, not draws from numpy's global stream: under one numpy
+        seed the first item's camera is the host path's, every later numpy draw differs from it."""
         ds = getattr(self, f"{split}_set")
         bs = batch_size or (self.batch_size if split == "train" else self.test_batch_size)
         idx = list(range(len(ds))) if indices is None else list(indices)
-        for i in range(0, len(idx), bs):
-            yield collate_to_device([ds[j] for j in idx[i:i + bs]], device)
+        if partial == "host":
+            for i in range(0, len(idx), bs):
+                yield collate_to_device([ds[j] for j in idx[i:i + bs]], device)
+            return
+        if partial != "device":
+            raise ValueError(f"partial must be 'host' or 'device', got {partial!r}")
+        from . import hpr
+        base = ds
+        while not isinstance(base, Imnet2LowResDataset) and hasattr(base, "dset"):
+            base = base.dset
+        if not isinstance(base, Imnet2LowResDataset) or not isinstance(base.partial_selector, VirtualScanSelector) or base.Xbd_as_Xct:
+            raise ValueError('partial="device" needs an Imnet2LowResDataset with a VirtualScanSelector at the bottom of the dataset chain')
+        sel, before = base.partial_selector, base.defer_partial
+        base.defer_partial = True
+        try:
+            for i in range(0, len(idx), bs):
+                items = [ds[j] for j in idx[i:i + bs]]
+                out = collate_to_device(items, device, keys=[k for k, v in items[0].items() if isinstance(v, np.ndarray) and k != "cam"])
+                cams = np.concatenate([it["cam"] for it in items]).astype(np.float64)      # collate_to_device casts to f32
+                out["Xct"] = hpr.virtual_scan_dev(out.pop("Xsrc"), sel.context_N, radius=sel.radius, noise=sel.noise, seed=seed,
+                                                  cams=cams, shape0=i)[0]
+                if base.Xct_as_Xbd:
+                    out["Xbd"] = out["Xct"]
+                yield out
+        finally:
+            base.defer_partial = before
