@@ -342,6 +342,11 @@ int sfmi_sdf_query_grid_slab_f32(const float* axis, int Q, int x0, int x1, const
  * (B,32) is applied to the interpolated features inside the kernel (the trilinear weights of the 'border' gather sum to one); both NULL: final grid */
 int sfmi_sdf_query_grid_aff_f32(const float* axis, int Q, int x0, int x1, const float* grid_cl, const float* aff_scale, const float* aff_shift,
                                 const float* wpack, float* out, int B, int G, int apply_sigmoid, void* stream);
+/* keyed lattice points, the third input form (the whole-lattice queries it thins out: shapeformer.py:382-391, vqdif.py:60-76,
+ * marched by xgutils/geoutil.py:175-233): keys (n_keys) int32 shape-local fine indices p = (ix*Q+iy)*Q+iz, ascending per shape; koff (B+1)
+ * int32 [device] exclusive offsets, koff[B] == n_keys.  out[j] equals the whole-lattice value of shape b's point keys[j] bit for bit. */
+int sfmi_sdf_query_keys_f32(const float* axis, int Q, const int* keys, const int* koff, long long n_keys, const float* grid_cl,
+                            const float* wpack, float* out, int B, int G, int apply_sigmoid, void* stream);
 /* nputil.sigmoid over stored logits (vqdif.py:262, shapeformer.py:388): y = 1 / (1 + exp(-x)), the fused epilogue's expression; may alias */
 int sfmi_sigmoid_f32(const float* x, float* y, long long n, void* stream);
 
@@ -464,6 +469,63 @@ int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const doub
 int sfmi_hpr_resample_f32(const void* X, int is_f64, const unsigned char* visible, const int* prefix, const long long* off,
                           const int* count, int B, long long N, int context_N, unsigned seed, int shape0, float noise, float* out,
                           void* stream);
+
+/* ---- Coarse-to-fine sparse iso-surface extraction (csrc/iso_sparse.hip): a mesh at Q points per axis without the Q^3
+ *      lattice.  The reference decodes and marches the dense lattice only: xgutils/geoutil.py:175-233 (array2mesh), shapeformer.py:382-391
+ *      (vis_ind's decode), vqdif.py:60-76 (decode_index); every entry below replaces a part of that route.
+ * CONTRACT
+ *   Lattice   Q = (Q0-1) 2^L + 1, Q0 >= 2, L >= 1, Q^3 < 2^31; axis = np.linspace(-1, 1, Q) as f32, the only coordinate table: every level
+ *             reads it at fine indices.  A level-l cell (i0,i1,i2) spans the fine indices [i s, (i+1) s], s = 2^(L-l).  The key of a point,
+ *             and of a cell through its low corner, is the shape-local fine index p = (i0 Q + i1) Q + i2 (x slowest: nputil.makeGrid 'ij').
+ *   Hierarchy S_0 = all (Q0-1)^3 cells.  For l = 0..L: the field is evaluated at the corners of S_l; M_l = the cells of S_l whose 8 corners
+ *             are not all on one side of iso (v > iso, as csrc/mcubes.hip).  For l < L: A_l = every level-l lattice cell within Chebyshev
+ *             distance margin (0 or 1) of a cell of M_l, clipped to the lattice (it may hold cells outside S_l); S_{l+1} = the 8 children of
+ *             every cell of A_l.  A point's value is a function of its key only; a point of S_{l+1} that was a corner of S_l keeps
+ *             its value, every other one is evaluated.
+ *   Mesh      marching cubes (mc_table.h) over M_L in the format and order of sfmi_mc_emit_f32: vertices by (shape, p of the edge's low
+ *             point, axis), triangles by (shape, p of the cell's low corner, table order), faces local per shape, and the same vertex
+ *             expressions t = fdiv(iso-f0, f1-f0), fma(fdiv(pos, Q-1), hi-lo, lo).  Hence the result equals the dense mesh restricted to
+ *             the cells of M_L bit for bit, and the whole dense mesh where M_L holds every cut cell.
+ *   Memory    two bit sets per batch (points, cells): Q^3 bits per shape plus one int32 per 32-bit word = 4 bits per fine point in all;
+ *             everything else is proportional to the active counts.  Integer atomicOr only: deterministic.
+ * A bit set is `bits` (B*W words, W = ceil(Q^3/32), shape b's words at b*W) and `rank` (B*W int32): the INCLUSIVE prefix sum of the words'
+ * popcounts over the whole batch, which the caller scans from the popc entry's output.  The slot of key p of shape b in the batch-wide
+ * ascending list is rank[b W + p/32] - popcount(bits[b W + p/32] >> (p%32)).  Offsets (coff, poff, voff) are (B+1) int32 [device].
+ * Every entry returns SFMI_EINVAL before any launch for a NULL pointer, Q^3 >= 2^31, margin outside {0,1} or Q0 / L that disagree with Q. */
+/* bytes of [point bits | point rank | cell bits | cell rank], a quarter each (0: invalid arguments) */
+size_t sfmi_iso_sparse_workspace_bytes(int B, int Q);
+/* level 0: clears both bitmaps, then sets every coarse point in pbits and every coarse cell in cbits */
+int sfmi_iso_seed_i32(int B, int Q0, int L, int Q, unsigned* pbits, unsigned* cbits, void* stream);
+/* cnt[i] = popcount(bits[i]) for the B*W words */
+int sfmi_iso_popc_i32(const unsigned* bits, int* cnt, int B, int Q0, int L, int Q, void* stream);
+/* keys (n) int32: the set's shape-local keys, ascending per shape, shape after shape; n = rank[B*W-1] */
+int sfmi_iso_compact_i32(const unsigned* bits, const int* rank, int B, int Q0, int L, int Q, int* keys, int n, void* stream);
+/* dst[j] = the slot in the set (bits, rank) of key j of an earlier ascending list (keys, off), or -1 where the set does not hold it: the
+ * values of the level before are carried into the new point set and only the new points are evaluated */
+int sfmi_iso_carry_i32(const int* keys, const int* off, int n, const unsigned* bits, const int* rank, int B, int Q0, int L, int Q, int* dst,
+                       void* stream);
+/* the two passes that finish a carry once the new set's size n_new is known: vals[dst[j]] = old[j] and known[dst[j]] = 1 where dst[j] >= 0
+ * (known (n_new) uint8, zeroed by the caller); then sel[k] = the k-th slot i with known[i] == 0, from uincl (n) = the inclusive prefix
+ * count of such slots and their number n_sel: the points the field is still asked for, in ascending order */
+int sfmi_iso_carry_apply_f32(const int* dst, const float* old, int n, float* vals, unsigned char* known, int n_new, void* stream);
+int sfmi_iso_select_i32(const unsigned char* known, const int* uincl, int n, int* sel, int n_sel, void* stream);
+/* flag[j] = the cube index (bit c = corner c above iso, 1..254) where cell j of S_level (keys `cells`, offsets coff) is cut, else 0;
+ * vals (nP): the field at the point set's slots */
+int sfmi_iso_classify_f32(const int* cells, const int* coff, int nC, int level, const unsigned* pbits, const int* prank, const float* vals,
+                          int nP, float iso, int B, int Q0, int L, int Q, unsigned char* flag, void* stream);
+/* level < L: clears both bitmaps, then sets S_{level+1} in cbits and its corner points in pbits */
+int sfmi_iso_refine_i32(const int* cells, const int* coff, const unsigned char* flag, int nC, int level, int margin, int B, int Q0, int L, int Q,
+                        unsigned* pbits, unsigned* cbits, void* stream);
+/* over S_L with its flags (the cube indices classify stored): ntri (nC) triangles per cell (0 where not cut); emask (nP) int32, cleared here: bit a set where the edge from
+ * that point along axis a is a cut edge of a cell of M_L */
+int sfmi_iso_mc_count_i32(const int* cells, const int* coff, const unsigned char* flag, int nC, const unsigned* pbits, const int* prank, int nP,
+                          int B, int Q0, int L, int Q, int* emask, int* ntri, void* stream);
+/* vincl (nP) / tincl (nC): inclusive prefix sums of popcount(emask) / ntri; voff (B+1): exclusive vertex offsets per shape.
+ * verts (V,3) f32 mapped onto the box [lo,hi] as array2mesh does, faces (T,3) int32 local per shape */
+int sfmi_iso_mc_emit_f32(const int* cells, const int* coff, const unsigned char* flag, int nC, const int* pkeys, const int* poff, int nP,
+                         const unsigned* pbits, const int* prank, const float* vals, float iso, const int* emask, const int* vincl,
+                         const int* tincl, const int* voff, int B, int Q0, int L, int Q, float lo0, float lo1, float lo2, float hi0, float hi1,
+                         float hi2, float* verts, int* faces, void* stream);
 
 #ifdef __cplusplus
 }

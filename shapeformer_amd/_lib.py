@@ -61,6 +61,7 @@ PROTOTYPES = {
     "sfmi_sigmoid_f32": (i32, [c_ptr, c_ptr, i64, c_ptr]),
     "sfmi_sdf_query_grid_slab_f32": (i32, [c_ptr, i32, i32, i32, c_ptr, c_ptr, c_ptr, i32, i32, i32, c_ptr]),
     "sfmi_sdf_query_grid_aff_f32": (i32, [c_ptr, i32, i32, i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i32, i32, i32, c_ptr]),
+    "sfmi_sdf_query_keys_f32": (i32, [c_ptr, i32, c_ptr, c_ptr, i64, c_ptr, c_ptr, c_ptr, i32, i32, i32, c_ptr]),
     # encoder (per-point path)
     "sfmi_enc_pack_floats": (sz, []),
     "sfmi_enc_pack_weights": (i32, [c_ptr] * 10),
@@ -169,6 +170,18 @@ PROTOTYPES = {
     "sfmi_hpr_workspace_bytes": (sz, [i32, i64]),
     "sfmi_hpr_visible": (i32, [c_ptr, i32, c_ptr, c_ptr, c_ptr, i32, i64, C.c_double] + [c_ptr] * 6),
     "sfmi_hpr_resample_f32": (i32, [c_ptr, i32] + [c_ptr] * 4 + [i32, i64, i32, C.c_uint, i32, f32, c_ptr, c_ptr]),
+    # coarse-to-fine sparse iso-surface extraction (csrc/iso_sparse.hip)
+    "sfmi_iso_sparse_workspace_bytes": (sz, [i32, i32]),
+    "sfmi_iso_seed_i32": (i32, [i32] * 4 + [c_ptr] * 3),
+    "sfmi_iso_popc_i32": (i32, [c_ptr, c_ptr] + [i32] * 4 + [c_ptr]),
+    "sfmi_iso_compact_i32": (i32, [c_ptr, c_ptr] + [i32] * 4 + [c_ptr, i32, c_ptr]),
+    "sfmi_iso_carry_i32": (i32, [c_ptr, c_ptr, i32, c_ptr, c_ptr] + [i32] * 4 + [c_ptr, c_ptr]),
+    "sfmi_iso_carry_apply_f32": (i32, [c_ptr, c_ptr, i32, c_ptr, c_ptr, i32, c_ptr]),
+    "sfmi_iso_select_i32": (i32, [c_ptr, c_ptr, i32, c_ptr, i32, c_ptr]),
+    "sfmi_iso_classify_f32": (i32, [c_ptr, c_ptr, i32, i32, c_ptr, c_ptr, c_ptr, i32, f32] + [i32] * 4 + [c_ptr, c_ptr]),
+    "sfmi_iso_refine_i32": (i32, [c_ptr] * 3 + [i32] * 7 + [c_ptr] * 3),
+    "sfmi_iso_mc_count_i32": (i32, [c_ptr] * 3 + [i32] + [c_ptr] * 2 + [i32] * 5 + [c_ptr] * 3),
+    "sfmi_iso_mc_emit_f32": (i32, [c_ptr] * 3 + [i32, c_ptr, c_ptr, i32] + [c_ptr] * 3 + [f32] + [c_ptr] * 4 + [i32] * 4 + [f32] * 6 + [c_ptr] * 3),
 }
 
 

@@ -156,8 +156,11 @@ class VisShapeFormer(VisCallback):
                  render_samples=64, end_tokens=None, mask_invalid=True, mask_invalid_completion=False,
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
                  thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
-                 eval_points=10 ** 5, **kw):
+                 eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, **kw):
         super().__init__(**kw)
+        # sparse_decode: visualize_batch meshes through VQDIF.decode_index_mesh (coarse-to-fine) at decode_res =
+        # (sparse_coarse-1) 2^L + 1 instead of decoding the dense decode_res^3 lattice; off: the dense route, unchanged
+        self.sparse_decode, self.sparse_coarse, self.sparse_margin = sparse_decode, sparse_coarse, sparse_margin
         # eval_metrics: visualize_batch also scores the completions on the device (metrics.evaluate: UHD / TMD against Xct, CD /
         # F-score at eval_tau against Xbd) from eval_points surface samples per completion mesh -> eval/<name>_metrics.json
         self.eval_metrics, self.eval_tau, self.eval_points = eval_metrics, eval_tau, eval_points
@@ -242,8 +245,12 @@ class VisShapeFormer(VisCallback):
         dense = np.full((len(sets), R ** 3), int(computed["empty_index"]), np.int32)
         for j, (_, t) in enumerate(sets):
             dense[j, t[:, 0]] = t[:, 1]                                      # batch_sparse2dense (common.py:171-189)
-        occ = vq.decode_index(torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev), grid_Q=Q, sigmoid=True)["logits"]
-        vd, fd, voff, toff = mcubes.marching_cubes_dev(occ.reshape(len(sets), Q, Q, Q), self.thresh)
+        if self.sparse_decode:
+            vd, fd, voff, toff = vq.decode_index_mesh(torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev), Q, coarse=self.sparse_coarse,
+                                                      margin=self.sparse_margin, thresh=self.thresh, sigmoid=True)
+        else:
+            occ = vq.decode_index(torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev), grid_Q=Q, sigmoid=True)["logits"]
+            vd, fd, voff, toff = mcubes.marching_cubes_dev(occ.reshape(len(sets), Q, Q, Q), self.thresh)
         if self.eval_metrics:
             out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir))
         v, f = vd.cpu().numpy().astype(np.float64), fd.cpu().numpy().astype(int)

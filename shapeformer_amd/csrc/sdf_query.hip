@@ -61,7 +61,10 @@ __device__ __forceinline__ SdfAxis sdf_axis(float x_api, int G) {
 // its per-(shape, channel) affine instead of being applied to the 64^3 x 32 grid in a pass of its own (67 MB of traffic per shape): the
 // trilinear weights of the 'border' gather sum to one, so  interp(x * scale + shift) = interp(x) * scale + shift  - 16 FMAs per lane on
 // the gathered features (fp32 rounding differs from the applied form by ~1e-7 of the feature).
-template <bool GRID_MODE, bool AFF = false>
+// KEYS (with GRID_MODE): the third input form - the N points are a ragged batch of lattice points named by their shape-local fine index
+// keys[j] = (ix*Q+iy)*Q+iz, ascending per shape, shape b owning koff[b] <= j < koff[b+1]; out (N).  A tile may straddle shapes, so the
+// shape is per lane; a point's coordinates and its own MFMA column are those of the lattice form, hence so is its result, bit for bit.
+template <bool GRID_MODE, bool AFF = false, bool KEYS = false>
 __global__ __launch_bounds__(512, 4) void sdf_query_kernel(
     const float* __restrict__ xyz,      // (B,N,3) in [-1,1]           (!GRID_MODE)
     const float* __restrict__ axis,     // (Q) f32 axis table          (GRID_MODE: pt = (ix*Q+iy)*Q+iz)
@@ -70,7 +73,8 @@ __global__ __launch_bounds__(512, 4) void sdf_query_kernel(
     const float* __restrict__ wpack,    // SDF_PACK_FLOATS
     float* __restrict__ out,            // (B,N)
     int B, long long N, int G, int Q, int apply_sigmoid,
-    const float* __restrict__ aff_scale = nullptr, const float* __restrict__ aff_shift = nullptr) {   // AFF: (B,32) each
+    const float* __restrict__ aff_scale = nullptr, const float* __restrict__ aff_shift = nullptr,     // AFF: (B,32) each
+    const int* __restrict__ keys = nullptr, const int* __restrict__ koff = nullptr) {                 // KEYS: (N), (B+1)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   {
     const f32x4* src = reinterpret_cast<const f32x4*>(wpack);
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(512, 4) void sdf_query_kernel(
   const int pl = lane & 31;
   // tile indices are 32-bit (the host entries bound B * ceil(N/32) < 2^31): no 64-bit division in the persistent loop
   const unsigned tiles_per_shape = (unsigned)((N + 31) >> 5);
-  const unsigned total_tiles = tiles_per_shape * (unsigned)B;
+  const unsigned total_tiles = KEYS ? tiles_per_shape : tiles_per_shape * (unsigned)B;
   const unsigned nwaves = gridDim.x * (blockDim.x >> 6);
   const unsigned wave_gid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
 
@@ -93,16 +97,19 @@ __global__ __launch_bounds__(512, 4) void sdf_query_kernel(
   const float wp1 = lds[SDF_OFF_FCP + 64 + lane];
 
   for (unsigned tile = wave_gid; tile < total_tiles; tile += nwaves) {
-    const int b = (int)(tile / tiles_per_shape);
+    int b = KEYS ? 0 : (int)(tile / tiles_per_shape);
     long long pt = (long long)(tile - (unsigned)b * tiles_per_shape) * 32 + pl;
     const bool valid = pt < N;
     if (!valid) pt = N - 1;
+    if (KEYS)
+      for (int i = 1; i < B; ++i) b += ((int)pt >= koff[i]);
 
     float px, py, pz;
     if (GRID_MODE) {
       // nputil.makeGrid 'ij' flatten: x slowest, z fastest (xgutils/nputil.py:618-654)
       // 32-bit index arithmetic (the host entry bounds Q^3 < 2^31): the 64-bit divisions cost the registers that used to spill
-      const unsigned p32 = (unsigned)pt, uq = (unsigned)Q;
+      const unsigned uq = (unsigned)Q;
+      const unsigned p32 = KEYS ? min((unsigned)keys[(int)pt], uq * uq * uq - 1u) : (unsigned)pt;   // a key outside the lattice reads no axis entry past the table
       const unsigned r = p32 / uq;
       const int iz = (int)(p32 - r * uq);
       const int ixx = (int)(r / uq);
@@ -118,12 +125,14 @@ __global__ __launch_bounds__(512, 4) void sdf_query_kernel(
     f32x16 c;
 #pragma unroll
     for (int t = 0; t < 16; ++t) c[t] = 0.0f;
-    const float* gb = grid + (long long)b * G * G * G * 32 + 4 * hi;
+    // KEYS: the shape is per lane; it enters the gather through the slowest grid index instead of a per-lane base pointer
+    const float* gb = grid + (KEYS ? 0ll : (long long)b * G * G * G * 32) + 4 * hi;
+    const int zb = KEYS ? b * G : 0;
 #pragma unroll
     for (int corner = 0; corner < 8; ++corner) {
       // ATen order: tnw,tne,tsw,tse,bnw,bne,bsw,bse  (t/b = z0/z1, n/s = y0/y1, w/e = x0/x1)
       const int dz = corner >> 2, dy = (corner >> 1) & 1, dx = corner & 1;
-      const int zi = dz ? az.i1 : az.i0, yi = dy ? ay.i1 : ay.i0, xi = dx ? ax.i1 : ax.i0;
+      const int zi = (dz ? az.i1 : az.i0) + zb, yi = dy ? ay.i1 : ay.i0, xi = dx ? ax.i1 : ax.i0;
       const float w = ((dx ? ax.w1 : ax.w0) * (dy ? ay.w1 : ay.w0)) * (dz ? az.w1 : az.w0);
       const f32x4* cp = reinterpret_cast<const f32x4*>(gb + (((long long)zi * G + yi) * G + xi) * 32);
 #pragma unroll
@@ -206,7 +215,10 @@ __global__ __launch_bounds__(512, 4) void sdf_query_kernel(
     r += __shfl_xor(r, 32, 64);
     r += lds[SDF_OFF_BOUT];
     if (apply_sigmoid) r = 1.0f / (1.0f + __expf(-r));
-    if (valid && hi == 0) out[(long long)b * N + pt] = r;
+    if (KEYS) {   // the point index is rebuilt from the (uniform) tile instead of living in registers across the layer chain
+      const long long j = (long long)tile * 32 + pl;
+      if (j < N && hi == 0) out[j] = r;
+    } else if (valid && hi == 0) out[(long long)b * N + pt] = r;
   }
 }
 
@@ -318,6 +330,20 @@ int sfmi_sdf_query_grid_aff_f32(const float* axis, int Q, int x0, int x1, const 
     hipLaunchKernelGGL((sdf_query_kernel<true, false>), dim3(sdf_grid_dim(tiles)), dim3(512),
                        SDF_PACK_FLOATS * sizeof(float), (hipStream_t)stream, nullptr, axis, axis + x0, grid_cl, wpack,
                        out, B, N, G, Q, apply_sigmoid, nullptr, nullptr);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+
+// keyed lattice points (the field of the coarse-to-fine iso-surface extraction; shapeformer.py:382-391 / vqdif.py:60-76 query the
+// whole lattice): keys (n_keys) int32 shape-local fine indices in [0, Q^3), ascending per shape, koff (B+1) device offsets with
+// koff[B] == n_keys; out[j] = the sfmi_sdf_query_grid_f32 value of shape b's lattice point keys[j], bit for bit.
+int sfmi_sdf_query_keys_f32(const float* axis, int Q, const int* keys, const int* koff, long long n_keys, const float* grid_cl, const float* wpack,
+                            float* out, int B, int G, int apply_sigmoid, void* stream) {
+  if (!axis || !koff || !grid_cl || !wpack || B <= 0 || Q <= 0 || Q > 1290 || G < 2 || n_keys < 0 || n_keys >= (1ll << 31)) return SFMI_EINVAL;   // Q^3 < 2^31
+  if (n_keys > 0 && (!keys || !out)) return SFMI_EINVAL;
+  if (n_keys == 0) return SFMI_OK;
+  hipLaunchKernelGGL((sdf_query_kernel<true, false, true>), dim3(sdf_grid_dim((n_keys + 31) >> 5)), dim3(512), SDF_PACK_FLOATS * sizeof(float),
+                     (hipStream_t)stream, nullptr, axis, axis, grid_cl, wpack, out, B, n_keys, G, Q, apply_sigmoid, nullptr, nullptr, keys, koff);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

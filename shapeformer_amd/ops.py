@@ -49,6 +49,20 @@ def sdf_query(xyz, grid_cl, wpack, sigmoid=False, out=None):
     return out
 
 
+def sdf_query_keys(axis, keys, koff, grid_cl, wpack, sigmoid=False):
+    """Keyed lattice points (csrc/sdf_query.hip KEYS): axis (Q) f32 table, keys (n) int32 shape-local fine indices (ix*Q+iy)*Q+iz ascending
+    per shape, koff (B+1) int32 device offsets -> (n) values, each equal to sdf_query_grid's value at (shape, key) bit for bit."""
+    _chk_cuda(axis, keys, koff, grid_cl, wpack)
+    axis, grid_cl = _c(axis, torch.float32), _c(grid_cl, torch.float32)
+    keys, koff = _c(keys, torch.int32), _c(koff, torch.int32)
+    B, G = grid_cl.shape[0], grid_cl.shape[1]
+    assert grid_cl.shape == (B, G, G, G, 32) and koff.shape == (B + 1,) and keys.dim() == 1
+    out = torch.empty(keys.numel(), device=axis.device, dtype=torch.float32)
+    L.check(L.lib().sfmi_sdf_query_keys_f32(L.ptr(axis), axis.numel(), L.ptr(keys), L.ptr(koff), keys.numel(), L.ptr(grid_cl), L.ptr(wpack),
+                                            L.ptr(out), B, G, int(sigmoid), L.stream_ptr()), "sfmi_sdf_query_keys_f32")
+    return out
+
+
 def sigmoid(x, out=None):
     """nputil.sigmoid of a device logits tensor (in-tree kernel: the SDF query's own epilogue expression)."""
     _chk_cuda(x)

@@ -575,6 +575,21 @@ class VQDIF:
             return dict(logits=ops.sdf_query_grid(axis, grid, self.sdf_w, sigmoid=sigmoid, x_range=x_range))
         return dict(logits=ops.sdf_query(Xtg.to(self.dev, torch.float32), grid, self.sdf_w, sigmoid=sigmoid))
 
+    def decode_index_mesh(self, code_ind, res, coarse=33, margin=1, thresh=0.5, sigmoid=True, bbox=((-1.0,) * 3, (1.0,) * 3), return_levels=False):
+        """The mesh of decode_index(grid_Q=res) + marching cubes without the res^3 lattice: the decoder is queried coarse to
+        fine, on a `coarse`^3 lattice first and then only around the cells the surface passes through; res = (coarse-1) 2^L + 1.
+        -> verts, faces, voff, toff as marching_cubes_dev [, levels] (iso_sparse.extract_sparse_dev).  The decoder grid is built once
+        in its applied-affine form, so the values are those of the lattice route without the in-kernel affine at every res."""
+        from . import iso_sparse, ops
+        nl = iso_sparse.lattice_levels(res, coarse)
+        if margin not in (0, 1):
+            raise L.SfmiError(f"decode_index_mesh: margin = {margin} must be 0 or 1")
+        grid = self.decoder_grid_cl(self.get_code_cl(code_ind), final_affine=True)
+        axis = torch.from_numpy(np.linspace(-1.0, 1.0, int(res)).astype(np.float32)).to(self.dev)
+        field = lambda keys, koff: ops.sdf_query_keys(axis, keys, koff, grid, self.sdf_w, sigmoid=sigmoid)
+        return iso_sparse.extract_sparse_dev(field, grid.shape[0], coarse, nl, thresh=thresh, margin=margin, bbox=bbox,
+                                             return_levels=return_levels, device=self.dev)
+
     def decode(self, grid_feat, Xtg):
         """vqdif.py:60-72 with a (B,d,R,R,R) feature grid."""
         from . import ops
