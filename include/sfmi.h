@@ -527,6 +527,69 @@ int sfmi_iso_mc_emit_f32(const int* cells, const int* coff, const unsigned char*
                          const int* tincl, const int* voff, int B, int Q0, int L, int Q, float lo0, float lo1, float lo2, float hi0, float hi1,
                          float hi2, float* verts, int* faces, void* stream);
 
+/* ---- Mesh decimation (csrc/simplify.hip): quadric vertex clustering to a face budget.  The reference decimates in the
+ *      call that meshes: xgutils/geoutil.py:175-233 (array2mesh(..., if_decimate=False, decimate_face=4096) -> igl.decimate(verts, faces,
+ *      decimate_face) when faces.shape[0] > decimate_face), called with if_decimate=True from xgutils/vis/npfvis.py:88-116.  What is kept is
+ *      that INTERFACE - a face budget, and a mesh at or below it returned unchanged - not igl.decimate's output: edge-collapse order is not
+ *      reproducible, vertex clustering (Lindstrom 2000, with Garland-Heckbert quadrics) is, and it is one pass over the mesh.
+ * CONTRACT
+ *   Input     a ragged batch of indexed meshes as sfmi_mc_emit_f32 / sfmi_iso_mc_emit_f32 leave them: verts (V,3) f32, faces (T,3) int32 with
+ *             indices local per shape, voff / toff (B+1) int32 [device] exclusive offsets (voff[B] == V, toff[B] == T); a box lo, hi
+ *             (3 doubles each, [host], lo < hi); a grid size G[b] in [1, 512] per shape.
+ *   Cell      of a vertex v, per axis in f32: t = fdiv(v - lo32, hi32 - lo32) (correctly rounded, as the vertex expression of the iso_sparse
+ *             section), c = clamp((int)floorf(t * (float)G), 0, G-1); key = (c0 G + c1) G + c2.  No fused multiply-add can form in it, so
+ *             numpy f32 gives the same bits.
+ *   Vertices  one output vertex per occupied cell, per shape in ascending key order.  Cells come from vertices: a vertex that no face uses
+ *             still occupies its cell.
+ *   Faces     an input face survives if and only if its three cells are pairwise distinct; survivors keep the input order, their indices are
+ *             the cells' slots, local per shape.  Two faces on the same three cells are BOTH kept (no duplicate removal, no manifold repair).
+ *   Position  in f64, relative to the cell centre ctr = lo + (c + 0.5) h, h = (hi - lo) / G.  Every corner (f, k) whose vertex lies in the
+ *             cell adds the plane of face f: n = (p1 - p0) x (p2 - p0) (not normalised: the weight is the squared area), d = -n.p0;
+ *             A += n n^T, b += d n (a face with two corners in the cell adds twice).  m = the mean of the cell's vertices.  tr = trace(A):
+ *             tr > 0: (A + reg tr I) x = -b + reg tr m (symmetric positive definite, condition <= 1 + 1/reg); else x = m.  x is clamped
+ *             componentwise to [-h/2, h/2] - a continuous clamp, not a fallback - and the vertex is f32(ctr + x).  reg > 0, default 1e-3.
+ *   Status    per shape: 0 ok; 1 no vertices; 2 a face index outside [0, V_b); 3 a non-finite vertex (the lowest code that applies).  A shape
+ *             with status != 0 yields no vertices and no faces.
+ *   Budget    a shape with T_b <= target is returned unchanged, bit for bit.  Otherwise, count(G) being the surviving faces at G:
+ *             count(512) <= target: G = 512; else lo = 1, hi = 512, while hi - lo > 1: mid = (lo + hi) / 2, count(mid) <= target ? lo = mid :
+ *             hi = mid; G = lo.  count is not monotone in G: the rule is this bisection, not "the largest G", and it leaves
+ *             count(G) <= target < count(G+1) whenever G < 512.  (shapeformer_amd/simplify.py: the shapes of a batch bisect together, one
+ *             counting pass and one read-back per step.)
+ *   Determinism  integer atomicOr / atomicAdd only, no floating-point atomics; each cell's records are summed in a fixed order by a fixed
+ *             tree: bit-identical from run to run, and a shape's output depends on that shape, its G, the box and reg only (a batch equals
+ *             per-shape calls bitwise).
+ * Bit sets: shape b owns ceil(G[b]^3 / 32) words of `bits` from woff[b] (woff (B+1) int32 [device]); `rank` is the INCLUSIVE prefix sum of the
+ * popc entry's output over all words, so the batch-wide slot of key p of shape b is rank[w] - popcount(bits[w] >> (p%32)), w = woff[b] + p/32,
+ * and coff[b] = rank[woff[b]-1] (0 for b = 0) is where the shape's cells start.  grid_host ([host], B ints) is what every entry validates;
+ * grid ([device]) is the same array for the kernels.  Every entry returns SFMI_EINVAL before any launch for a NULL pointer, a G outside
+ * [1, 512], a box without lo < hi or reg <= 0. */
+/* words of the batch's bit sets = woff[B]; -1 for B <= 0 or a G outside [1, 512] */
+long long sfmi_simplify_words(const int* grid_host, int B);
+/* clears bits and flags; vkey (V) = every vertex's cell key, its bit set; flags (B): bit 0 no vertices, bit 1 a bad face index, bit 2 a
+ * non-finite vertex */
+int sfmi_simplify_cells_f32(const float* verts, const int* faces, const int* voff, const int* toff, const int* grid_host, const int* grid,
+                            const int* woff, int B, int V, int T, const double* lo, const double* hi, int* vkey, unsigned* bits, int* flags,
+                            void* stream);
+/* cnt[i] = popcount(bits[i]), 0 for the words of a flagged shape; status (B) = the codes above */
+int sfmi_simplify_popc_i32(const unsigned* bits, const int* flags, const int* woff, const int* grid_host, int B, int* cnt, int* status,
+                           void* stream);
+/* vslot (V) = the batch-wide slot of every vertex's cell; INT_MAX for the vertices of a flagged shape */
+int sfmi_simplify_slots_i32(const int* vkey, const int* voff, const int* woff, const unsigned* bits, const int* rank, const int* flags,
+                            const int* grid_host, int B, int V, int* vslot, void* stream);
+/* the counting pass: surv (T) uint8 survive flags, count (B) survivors per shape (cleared here); cslot (3T) or NULL: the batch-wide slot of
+ * every corner record 3 f + k (INT_MAX in a flagged shape), the sort key of the solve.  Computes no quadrics. */
+int sfmi_simplify_faces_i32(const int* faces, const int* voff, const int* toff, const int* vslot, const int* flags, int B, int T,
+                            int* cslot, unsigned char* surv, int* count, void* stream);
+/* out (nC,3) f32, one wave64 per cell.  vorder (V) / corder (3T): the vertices / corner records STABLY sorted by vslot / cslot; vseg / cseg
+ * (nC+1): where each cell's run starts in them.  Lane l takes entries l, l+64, ... of a run; a fixed xor butterfly adds the lanes.  faces / corder may be NULL where every run of
+ * cseg is empty (a batch without faces). */
+int sfmi_simplify_solve_f32(const float* verts, const int* faces, const int* voff, const int* vkey, const int* grid_host, const int* grid,
+                            const int* vorder, const int* vseg, const int* corder, const int* cseg, int B, int nC, const double* lo,
+                            const double* hi, double reg, float* out, void* stream);
+/* out (nS,3) int32: the surviving faces in input order as slots local per shape; sincl (T): inclusive prefix sum of surv; coff (B+1) */
+int sfmi_simplify_emit_i32(const int* faces, const int* voff, const int* toff, const int* vslot, const unsigned char* surv, const int* sincl,
+                           const int* coff, int B, int T, int nS, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,14 @@ PROTOTYPES = {
     "sfmi_iso_refine_i32": (i32, [c_ptr] * 3 + [i32] * 7 + [c_ptr] * 3),
     "sfmi_iso_mc_count_i32": (i32, [c_ptr] * 3 + [i32] + [c_ptr] * 2 + [i32] * 5 + [c_ptr] * 3),
     "sfmi_iso_mc_emit_f32": (i32, [c_ptr] * 3 + [i32, c_ptr, c_ptr, i32] + [c_ptr] * 3 + [f32] + [c_ptr] * 4 + [i32] * 4 + [f32] * 6 + [c_ptr] * 3),
+    # mesh decimation: quadric vertex clustering (csrc/simplify.hip)
+    "sfmi_simplify_words": (i64, [c_ptr, i32]),
+    "sfmi_simplify_cells_f32": (i32, [c_ptr] * 7 + [i32] * 3 + [c_ptr] * 6),
+    "sfmi_simplify_popc_i32": (i32, [c_ptr] * 4 + [i32] + [c_ptr] * 3),
+    "sfmi_simplify_slots_i32": (i32, [c_ptr] * 7 + [i32] * 2 + [c_ptr] * 2),
+    "sfmi_simplify_faces_i32": (i32, [c_ptr] * 5 + [i32] * 2 + [c_ptr] * 4),
+    "sfmi_simplify_solve_f32": (i32, [c_ptr] * 10 + [i32] * 2 + [c_ptr] * 2 + [C.c_double] + [c_ptr] * 2),
+    "sfmi_simplify_emit_i32": (i32, [c_ptr] * 7 + [i32] * 3 + [c_ptr] * 2),
 }
 
 

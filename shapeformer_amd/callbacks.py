@@ -103,8 +103,11 @@ class VisSparseRecon3D(VisCallback):
     """vqdif.py:217-310: quantize -> sparse tokens -> dense -> decode on the `decoder_resolution`^3 lattice -> mesh."""
 
     def __init__(self, samples=32, Xct_as_Xbd=False, quant_grid_depth=4, decoder_resolution=128, vocab_size=4096,
-                 max_length=512, end_tokens=(4096, 4096), resolution=(512, 512), vis_Ytg=True, thresh=0.5, **kw):
+                 max_length=512, end_tokens=(4096, 4096), resolution=(512, 512), vis_Ytg=True, thresh=0.5, decimate_face=None, **kw):
         super().__init__(**kw)
+        # decimate_face: the mesh that is written and returned is decimated to that many faces on the device before the copy to the
+        # host (simplify.decimate_dev, DESIGN 5.10); eval_pc keeps sampling the undecimated mesh.  None: off, unchanged
+        self.decimate_face = decimate_face
         self.Xct_as_Xbd, self.quant_grid_depth, self.decoder_resolution = Xct_as_Xbd, quant_grid_depth, decoder_resolution
         self.vocab_size, self.max_length, self.end_tokens, self.thresh = vocab_size, max_length, tuple(end_tokens), thresh
 
@@ -138,10 +141,15 @@ class VisSparseRecon3D(VisCallback):
         self._occ_dev = None
         v, f, voff, toff = mcubes.marching_cubes_dev(occ[:1].reshape(1, Q, Q, Q), self.thresh)
         vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
+        full = (vert, face)                                                                # what eval_pc samples
+        if self.decimate_face is not None:
+            from .simplify import decimate_dev
+            v, f = decimate_dev(v, f, voff, toff, self.decimate_face)[:2]
+            vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
         path = meshio.write_mesh(data_dir, vert, face, input_name)                         # geoutil.write_mesh
         out = {"recon_mesh": {"vert": vert, "face": face}, "mesh_path": path}
-        if len(face):
-            eval_pc = meshio.sample_mesh(vert, face, 10 ** 5)
+        if len(full[1]):
+            eval_pc = meshio.sample_mesh(*full, 10 ** 5)
             os.makedirs(os.path.join(data_dir, "eval"), exist_ok=True)
             np.savez(os.path.join(data_dir, "eval", f"{input_name}.npz"), eval_pc=eval_pc)
             out["eval_pc"] = eval_pc
@@ -156,8 +164,12 @@ class VisShapeFormer(VisCallback):
                  render_samples=64, end_tokens=None, mask_invalid=True, mask_invalid_completion=False,
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
                  thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
-                 eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, **kw):
+                 eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, **kw):
         super().__init__(**kw)
+        # decimate_face: the meshes that are written to meshes/*.ply and returned are decimated to that many faces on the device before
+        # the copy to the host (simplify.decimate_dev), on the dense and the sparse_decode route alike; eval_pc, recon_<i>
+        # and eval_metrics keep sampling the undecimated meshes (the reference's vis_ind evaluates with if_decimate=False).  None: off
+        self.decimate_face = decimate_face
         # sparse_decode: visualize_batch meshes through VQDIF.decode_index_mesh (coarse-to-fine) at decode_res =
         # (sparse_coarse-1) 2^L + 1 instead of decoding the dense decode_res^3 lattice; off: the dense route, unchanged
         self.sparse_decode, self.sparse_coarse, self.sparse_margin = sparse_decode, sparse_coarse, sparse_margin
@@ -254,14 +266,21 @@ class VisShapeFormer(VisCallback):
         if self.eval_metrics:
             out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir))
         v, f = vd.cpu().numpy().astype(np.float64), fd.cpu().numpy().astype(int)
+        if self.decimate_face is not None:
+            from .simplify import decimate_dev
+            wd, gd, woff, goff = decimate_dev(vd, fd, voff, toff, self.decimate_face)[:4]
+            w, g = wd.cpu().numpy().astype(np.float64), gd.cpu().numpy().astype(int)
+        else:
+            w, g, woff, goff = v, f, voff, toff
         eval_pcs = []
         for j, (key, _) in enumerate(sets):
-            vert, face = v[voff[j]:voff[j + 1]], f[toff[j]:toff[j + 1]]
+            vert, face = v[voff[j]:voff[j + 1]], f[toff[j]:toff[j + 1]]      # the undecimated mesh: what is sampled for eval/
             if vert.shape[0] < 10:                                           # shapeformer.py:316-317
                 continue
             path = os.path.join(data_dir, "meshes", f"{input_name}_{key}_mesh.ply")
-            meshio.write_ply(path, vert, face)
-            out[key + "_mesh"] = {"vert": vert, "face": face, "path": path}
+            wv, wf = w[woff[j]:woff[j + 1]], g[goff[j]:goff[j + 1]]          # what is written and returned
+            meshio.write_ply(path, wv, wf)
+            out[key + "_mesh"] = {"vert": wv, "face": wf, "path": path}
             if key[0] == "s":
                 eval_pcs.append(meshio.sample_mesh(vert, face, 10 ** 5))
         if eval_pcs:

@@ -1,7 +1,8 @@
 """Iso-surface extraction on the GPU — host side of csrc/mcubes.hip.
 
-`array2mesh` mirrors xgutils/geoutil.py:175-233 for dim == 3 (no gaussian filter, no decimation, cart_coord=True):
-marching cubes at `thresh`, vertices mapped onto the bounding box of the query coordinates.  The reference calls
+`array2mesh` mirrors xgutils/geoutil.py:175-233 for dim == 3 (no gaussian filter, cart_coord=True): marching cubes at `thresh`,
+vertices mapped onto the bounding box of the query coordinates, then, with `if_decimate`, decimation to `decimate_face` faces on the
+device (simplify.decimate_dev: quadric vertex clustering - the reference's face budget, not igl.decimate's output).  The reference calls
 PyMCubes on the CPU after copying the 128^3 occupancy to the host; here the grid never leaves HBM and the result is an
 indexed mesh (shared vertices), in a deterministic order.  There is no CPU fallback.
 """
@@ -37,9 +38,11 @@ def marching_cubes_dev(occ: torch.Tensor, thresh: float = 0.5, bbox=((-1.0, -1.0
     return verts[:int(voff[-1])], faces[:int(toff[-1])], voff, toff
 
 
-def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), device="cuda:0"):
-    """geoutil.array2mesh(array, thresh, dim=3, coords=...) for ONE flattened or cubic grid -> (verts (V,3) float64,
-    faces (T,3) int) numpy, like the reference returns (`verts*(bbmax-bbmin)+bbmin`, faces.astype(int))."""
+def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), device="cuda:0", if_decimate=False,
+               decimate_face=4096):
+    """geoutil.array2mesh(array, thresh, dim=3, coords=..., if_decimate=..., decimate_face=...) for ONE flattened or cubic grid ->
+    (verts (V,3) float64, faces (T,3) int) numpy, like the reference returns (`verts*(bbmax-bbmin)+bbmin`, faces.astype(int)).
+    if_decimate: a mesh with more than `decimate_face` faces is decimated on the device, over the same box, before the copy."""
     a = torch.as_tensor(occupancy, dtype=torch.float32)
     if a.dim() != 3:
         Q = round(a.numel() ** (1.0 / 3))
@@ -48,5 +51,8 @@ def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.
     if coords is not None:
         c = np.asarray(coords).reshape(-1, 3)
         bbox = (c.min(0), c.max(0))                # nputil.arrayBBox
-    v, f, _, _ = marching_cubes_dev(a[None].to(device), thresh, bbox)
+    v, f, voff, toff = marching_cubes_dev(a[None].to(device), thresh, bbox)
+    if if_decimate:
+        from .simplify import decimate_dev
+        v, f = decimate_dev(v, f, voff, toff, decimate_face, bbox)[:2]
     return v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
