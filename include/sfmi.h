@@ -349,6 +349,22 @@ int sfmi_sdf_query_keys_f32(const float* axis, int Q, const int* keys, const int
                             const float* wpack, float* out, int B, int G, int apply_sigmoid, void* stream);
 /* nputil.sigmoid over stored logits (vqdif.py:262, shapeformer.py:388): y = 1 / (1 + exp(-x)), the fused epilogue's expression; may alias */
 int sfmi_sigmoid_f32(const float* x, float* y, long long n, void* stream);
+/* Value and gradient with respect to the query point (dec.py:62-100 differentiated, the refine / normal-estimation steps after
+ * geoutil.array2mesh).  Ragged batch: xyz (N,3) in the [-1,1] frame, poff (B+1) int32 [device] offsets, shape b owns poff[b] <= j < poff[b+1];
+ * grid_cl is the final (B,G,G,G,32) grid.  val (N) equals the value entry's logit bit for bit; grad (N,3) = d val / d xyz of the
+ * kernel's own expression: fc_p sees xyz/2 unclamped; the gather contributes (G-1)/(2*1.101) per axis times the derivative of the
+ * floor(ix) cell's trilinear patch, zero on an axis where the normalisation or the border clamp holds; relu'(x) = [x > 0].
+ * Optional epilogues (NULL = off): xyz_out (N,3) = x - s (val - level) g/|g|^2 with s = min(1, max_step |g| / |val - level|) (x where
+ * |g|^2 < 1e-24); normal_out (N,3) = -g/|g| (0 where |g|^2 < 1e-24).  *_cap: floats the output buffers hold.  wpack_grad: the image of the
+ * grad packer below (the value image, the fragment image of the transposed matrices, fc_p^T).  SFMI_EINVAL before any launch for a NULL
+ * required pointer, N <= 0 or >= 2^31, G < 2, a capacity below N / 3N; SFMI_ELDS when the device refuses the 125.3 KB of dynamic LDS. */
+size_t sfmi_sdf_pack_grad_floats(void);
+int sfmi_sdf_pack_weights_grad(const float* fc_p_w, const float* fc_p_b, const float* fc_c_w, const float* fc_c_b,
+                               const float* fc0_w, const float* fc0_b, const float* fc1_w, const float* fc1_b,
+                               const float* fc_out_w, const float* fc_out_b, float* out); /* [host] */
+int sfmi_sdf_query_grad_f32(const float* xyz, const int* poff, long long N, const float* grid_cl, const float* wpack_grad, float* val,
+                            long long val_cap, float* grad, long long grad_cap, float level, float max_step, float* xyz_out,
+                            long long xyz_out_cap, float* normal_out, long long normal_cap, int B, int G, void* stream);
 
 /* ---- Training step of the VQDIF autoencoder (csrc/train_vqdif.hip): vqdif.py:78-137 (forward, VQLoss,
  *      Adam), quantizer.py:68-89 (EMA codebook, straight-through), backward of enc.py:66-140, updown.py:79-132,

@@ -62,6 +62,9 @@ PROTOTYPES = {
     "sfmi_sdf_query_grid_slab_f32": (i32, [c_ptr, i32, i32, i32, c_ptr, c_ptr, c_ptr, i32, i32, i32, c_ptr]),
     "sfmi_sdf_query_grid_aff_f32": (i32, [c_ptr, i32, i32, i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i32, i32, i32, c_ptr]),
     "sfmi_sdf_query_keys_f32": (i32, [c_ptr, i32, c_ptr, c_ptr, i64, c_ptr, c_ptr, c_ptr, i32, i32, i32, c_ptr]),
+    "sfmi_sdf_pack_grad_floats": (sz, []),
+    "sfmi_sdf_pack_weights_grad": (i32, [c_ptr] * 11),
+    "sfmi_sdf_query_grad_f32": (i32, [c_ptr, c_ptr, i64, c_ptr, c_ptr, c_ptr, i64, c_ptr, i64, f32, f32, c_ptr, i64, c_ptr, i64, i32, i32, c_ptr]),
     # encoder (per-point path)
     "sfmi_enc_pack_floats": (sz, []),
     "sfmi_enc_pack_weights": (i32, [c_ptr] * 10),

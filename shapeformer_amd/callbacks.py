@@ -103,8 +103,14 @@ class VisSparseRecon3D(VisCallback):
     """vqdif.py:217-310: quantize -> sparse tokens -> dense -> decode on the `decoder_resolution`^3 lattice -> mesh."""
 
     def __init__(self, samples=32, Xct_as_Xbd=False, quant_grid_depth=4, decoder_resolution=128, vocab_size=4096,
-                 max_length=512, end_tokens=(4096, 4096), resolution=(512, 512), vis_Ytg=True, thresh=0.5, decimate_face=None, **kw):
+                 max_length=512, end_tokens=(4096, 4096), resolution=(512, 512), vis_Ytg=True, thresh=0.5, decimate_face=None,
+                 refine_steps=0, vertex_normals=False, **kw):
         super().__init__(**kw)
+        # refine_steps: that many Newton steps of the mesh vertices onto the decoder's iso-surface (VQDIF.refine_mesh_dev, DESIGN 5.11),
+        # each at most half a lattice cell; vertex_normals: the PLY carries the field's unit normals at its vertices.  The order is
+        # extract -> refine -> decimate -> normals at the final vertices; eval_pc samples the refined, undecimated mesh.  0 / False: off,
+        # unchanged (compute_batch then stores no `dense` code grid either)
+        self.refine_steps, self.vertex_normals = int(refine_steps), bool(vertex_normals)
         # decimate_face: the mesh that is written and returned is decimated to that many faces on the device before the copy to the
         # host (simplify.decimate_dev, DESIGN 5.10); eval_pc keeps sampling the undecimated mesh.  None: off, unchanged
         self.decimate_face = decimate_face
@@ -127,8 +133,10 @@ class VisSparseRecon3D(VisCallback):
             t = filter_end_tokens(th[b, :lh[b]], self.end_tokens)
             rows.append(np.concatenate([np.full((len(t), 1), b, np.int64), t], 1))
         self._occ_dev = ops.sigmoid(logits)[..., 0]                          # stays in HBM for the mesh extraction
-        return _np({"logits": logits, "quant_ind": raw.long(), "sparse": np.concatenate(rows, 0),
-                    "grid_mask": mask.bool(), "batch": batch})
+        out = {"logits": logits, "quant_ind": raw.long(), "sparse": np.concatenate(rows, 0), "grid_mask": mask.bool(), "batch": batch}
+        if self.refine_steps or self.vertex_normals:
+            out["dense"] = dense          # the code grid the decoder field is rebuilt from in visualize_batch
+        return _np(out)
 
     def visualize_batch(self, computed, input_name="", data_dir=None):
         from . import mcubes
@@ -140,14 +148,27 @@ class VisSparseRecon3D(VisCallback):
             occ = ops.sigmoid(torch.as_tensor(computed["logits"]).to(dev))[..., 0]       # nputil.sigmoid(logits)
         self._occ_dev = None
         v, f, voff, toff = mcubes.marching_cubes_dev(occ[:1].reshape(1, Q, Q, Q), self.thresh)
+        field = self.refine_steps or self.vertex_normals
+        if field:
+            vq = getattr(self.pl_module, "core", self.pl_module)
+            if "dense" not in computed:
+                raise KeyError("computed['dense'] is missing: this item was computed without refine_steps / vertex_normals; compute it again")
+            grid = vq.decoder_grid_cl(vq.get_code_cl(torch.as_tensor(computed["dense"])[:1].to(vq.dev)))
+            if self.refine_steps and len(v):
+                v = vq.refine_mesh_dev(grid, v, voff, thresh=self.thresh, steps=self.refine_steps, max_step=1.0 / (Q - 1))
         vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
         full = (vert, face)                                                                # what eval_pc samples
         if self.decimate_face is not None:
             from .simplify import decimate_dev
-            v, f = decimate_dev(v, f, voff, toff, self.decimate_face)[:2]
+            v, f, voff = decimate_dev(v, f, voff, toff, self.decimate_face)[:3]
             vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
-        path = meshio.write_mesh(data_dir, vert, face, input_name)                         # geoutil.write_mesh
+        normal = None
+        if self.vertex_normals and len(vert) >= 10:                                        # (write_mesh replaces smaller results by a dummy)
+            normal = vq.vertex_normals_dev(grid, v, voff).cpu().numpy().astype(np.float64)
+        path = meshio.write_mesh(data_dir, vert, face, input_name, normal=normal)          # geoutil.write_mesh
         out = {"recon_mesh": {"vert": vert, "face": face}, "mesh_path": path}
+        if normal is not None:
+            out["recon_mesh"]["normal"] = normal
         if len(full[1]):
             eval_pc = meshio.sample_mesh(*full, 10 ** 5)
             os.makedirs(os.path.join(data_dir, "eval"), exist_ok=True)
@@ -164,8 +185,12 @@ class VisShapeFormer(VisCallback):
                  render_samples=64, end_tokens=None, mask_invalid=True, mask_invalid_completion=False,
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
                  thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
-                 eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, **kw):
+                 eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, refine_steps=0,
+                 vertex_normals=False, **kw):
         super().__init__(**kw)
+        # refine_steps / vertex_normals: as VisSparseRecon3D's, on the dense and the sparse_decode route alike: extract -> refine ->
+        # decimate -> normals at the final vertices; eval_pc, recon_<i> and eval_metrics sample the refined, undecimated meshes
+        self.refine_steps, self.vertex_normals = int(refine_steps), bool(vertex_normals)
         # decimate_face: the meshes that are written to meshes/*.ply and returned are decimated to that many faces on the device before
         # the copy to the host (simplify.decimate_dev), on the dense and the sparse_decode route alike; eval_pc, recon_<i>
         # and eval_metrics keep sampling the undecimated meshes (the reference's vis_ind evaluates with if_decimate=False).  None: off
@@ -257,12 +282,20 @@ class VisShapeFormer(VisCallback):
         dense = np.full((len(sets), R ** 3), int(computed["empty_index"]), np.int32)
         for j, (_, t) in enumerate(sets):
             dense[j, t[:, 0]] = t[:, 1]                                      # batch_sparse2dense (common.py:171-189)
+        codes = torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev)
+        field = self.refine_steps or self.vertex_normals
         if self.sparse_decode:
-            vd, fd, voff, toff = vq.decode_index_mesh(torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev), Q, coarse=self.sparse_coarse,
-                                                      margin=self.sparse_margin, thresh=self.thresh, sigmoid=True)
+            vd, fd, voff, toff = vq.decode_index_mesh(codes, Q, coarse=self.sparse_coarse, margin=self.sparse_margin, thresh=self.thresh,
+                                                      sigmoid=True, refine_steps=self.refine_steps)
+            if self.vertex_normals:
+                grid = vq.decoder_grid_cl(vq.get_code_cl(codes))                    # the final grid decode_index_mesh refined on
         else:
-            occ = vq.decode_index(torch.from_numpy(dense.reshape(-1, R, R, R)).to(vq.dev), grid_Q=Q, sigmoid=True)["logits"]
+            occ = vq.decode_index(codes, grid_Q=Q, sigmoid=True)["logits"]
             vd, fd, voff, toff = mcubes.marching_cubes_dev(occ.reshape(len(sets), Q, Q, Q), self.thresh)
+            if field:
+                grid = vq.decoder_grid_cl(vq.get_code_cl(codes))                    # final (applied-affine) form, whatever form the lattice query took
+                if self.refine_steps and len(vd):
+                    vd = vq.refine_mesh_dev(grid, vd, voff, thresh=self.thresh, steps=self.refine_steps, max_step=1.0 / (Q - 1))
         if self.eval_metrics:
             out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir))
         v, f = vd.cpu().numpy().astype(np.float64), fd.cpu().numpy().astype(int)
@@ -271,7 +304,10 @@ class VisShapeFormer(VisCallback):
             wd, gd, woff, goff = decimate_dev(vd, fd, voff, toff, self.decimate_face)[:4]
             w, g = wd.cpu().numpy().astype(np.float64), gd.cpu().numpy().astype(int)
         else:
-            w, g, woff, goff = v, f, voff, toff
+            wd, w, g, woff, goff = vd, v, f, voff, toff
+        wn = None
+        if self.vertex_normals and len(wd):
+            wn = vq.vertex_normals_dev(grid, wd, woff).cpu().numpy().astype(np.float64)      # at the vertices that are written
         eval_pcs = []
         for j, (key, _) in enumerate(sets):
             vert, face = v[voff[j]:voff[j + 1]], f[toff[j]:toff[j + 1]]      # the undecimated mesh: what is sampled for eval/
@@ -279,8 +315,10 @@ class VisShapeFormer(VisCallback):
                 continue
             path = os.path.join(data_dir, "meshes", f"{input_name}_{key}_mesh.ply")
             wv, wf = w[woff[j]:woff[j + 1]], g[goff[j]:goff[j + 1]]          # what is written and returned
-            meshio.write_ply(path, wv, wf)
+            meshio.write_ply(path, wv, wf, normal=None if wn is None else wn[woff[j]:woff[j + 1]])
             out[key + "_mesh"] = {"vert": wv, "face": wf, "path": path}
+            if wn is not None:
+                out[key + "_mesh"]["normal"] = wn[woff[j]:woff[j + 1]]
             if key[0] == "s":
                 eval_pcs.append(meshio.sample_mesh(vert, face, 10 ** 5))
         if eval_pcs:

@@ -91,3 +91,63 @@ def sdf_query_grid(axis, grid_cl, wpack, sigmoid=False, out=None, x_range=None, 
     L.check(L.lib().sfmi_sdf_query_grid_aff_f32(L.ptr(axis), Q, x0, x1, L.ptr(grid_cl), L.ptr(sc), L.ptr(sh), L.ptr(wpack), L.ptr(out), B, G,
                                                 int(sigmoid), L.stream_ptr()), "sfmi_sdf_query_grid_aff_f32")
     return out
+
+
+# ---------------------------------------------------------------- SDF value + gradient (csrc/sdf_query.hip sdf_grad_kernel)
+def sdf_pack_weights_grad(sd, prefix="decoder.") -> np.ndarray:
+    """The gradient kernel's weight image: the sdf_pack_weights image, the fragment image of the transposed matrices, fc_p^T."""
+    g = lambda k: np.ascontiguousarray(np.asarray(sd[prefix + k], dtype=np.float32))
+    cat = lambda fmt: np.ascontiguousarray(np.stack([g(fmt.format(i)) for i in range(5)]))
+    out = np.empty(L.lib().sfmi_sdf_pack_grad_floats(), np.float32)
+    arrs = [g("fc_p.weight"), g("fc_p.bias"), cat("fc_c.{}.weight"), cat("fc_c.{}.bias"),
+            cat("blocks.{}.fc_0.weight"), cat("blocks.{}.fc_0.bias"), cat("blocks.{}.fc_1.weight"),
+            cat("blocks.{}.fc_1.bias"), g("fc_out.weight"), g("fc_out.bias"), out]
+    L.check(L.lib().sfmi_sdf_pack_weights_grad(*[a.ctypes.data for a in arrs]), "sfmi_sdf_pack_weights_grad")
+    return out
+
+
+def _sdf_grad_launch(xyz, grid_cl, wpack_grad, off, level=0.0, max_step=0.0, step=False, normals=False):
+    """One launch of the gradient kernel.  xyz (B,N,3) with off None (equal offsets are built), or (N,3) with off (B+1) int32 device
+    offsets (ragged).  -> val, grad, xyz_out or None, normal or None, shaped like the input."""
+    _chk_cuda(xyz, grid_cl, wpack_grad, off)
+    xyz, grid_cl = _c(xyz, torch.float32), _c(grid_cl, torch.float32)
+    B, G = grid_cl.shape[0], grid_cl.shape[1]
+    assert grid_cl.shape == (B, G, G, G, 32) and wpack_grad.numel() == L.lib().sfmi_sdf_pack_grad_floats()
+    if off is None:
+        assert xyz.dim() == 3 and xyz.shape[0] == B and xyz.shape[2] == 3, tuple(xyz.shape)
+        off = torch.arange(B + 1, device=xyz.device, dtype=torch.int32) * xyz.shape[1]
+        vshape = (B, xyz.shape[1], 1)
+    else:
+        off = _c(off, torch.int32)
+        assert xyz.dim() == 2 and xyz.shape[1] == 3 and off.shape == (B + 1,), (tuple(xyz.shape), tuple(off.shape))
+        vshape = (xyz.shape[0],)
+    n = xyz.numel() // 3
+    val = torch.empty(vshape, device=xyz.device, dtype=torch.float32)
+    grad = torch.empty_like(xyz)
+    xo = torch.empty_like(xyz) if step else None
+    no = torch.empty_like(xyz) if normals else None
+    if n == 0:
+        return val, grad, xo, no
+    L.check(L.lib().sfmi_sdf_query_grad_f32(L.ptr(xyz), L.ptr(off), n, L.ptr(grid_cl), L.ptr(wpack_grad), L.ptr(val), val.numel(), L.ptr(grad),
+                                            grad.numel(), float(level), float(max_step), L.ptr(xo), 0 if xo is None else xo.numel(), L.ptr(no),
+                                            0 if no is None else no.numel(), B, G, L.stream_ptr()), "sfmi_sdf_query_grad_f32")
+    return val, grad, xo, no
+
+
+def sdf_query_grad(xyz, grid_cl, wpack_grad, off=None):
+    """Logit and d logit / d xyz (the [-1,1] frame) of the fused implicit decoder.  xyz (B,N,3) -> val (B,N,1), grad (B,N,3); or ragged:
+    xyz (N,3) with off (B+1) int32 device offsets -> val (N), grad (N,3).  val equals sdf_query's logit bit for bit."""
+    return _sdf_grad_launch(xyz, grid_cl, wpack_grad, off)[:2]
+
+
+def sdf_refine_step(xyz, grid_cl, wpack_grad, level, max_step, off=None):
+    """One Newton step towards the iso-surface logit == level, the move clamped to max_step in length (fused step epilogue):
+    x' = x - s (val - level) g / |g|^2, s = min(1, max_step |g| / |val - level|); x where |g|^2 < 1e-24.  -> x', val (at x)."""
+    val, _, xo, _ = _sdf_grad_launch(xyz, grid_cl, wpack_grad, off, level=level, max_step=max_step, step=True)
+    return xo, val
+
+
+def sdf_normals(xyz, grid_cl, wpack_grad, off=None):
+    """Unit normals -g/|g| of the decoder field at xyz (outward: occupancy rises inward), zero where |g|^2 < 1e-24 (fused normal
+    epilogue).  Shapes as sdf_query_grad."""
+    return _sdf_grad_launch(xyz, grid_cl, wpack_grad, off, normals=True)[3]

@@ -364,8 +364,9 @@ class LocalDecoder(_GridOps):
             self.up.append(_Conv(sd, f"upsampler.blocks.{3 * s + 1}.", dev, 3, 1, 1))
             self.up[-1].pack_subpixel(dev)
             self.up.append(_Conv(sd, f"upsampler.blocks.{3 * s + 2}.", dev, 3, 1, 1))
-        from .ops import sdf_pack_weights
+        from .ops import sdf_pack_weights, sdf_pack_weights_grad
         self.sdf_w = torch.from_numpy(sdf_pack_weights(sd, prefix="")).to(dev)
+        self.sdf_w_grad = torch.from_numpy(sdf_pack_weights_grad(sd, prefix="")).to(dev)      # value image + transposed image
 
     def _single_gcr(self, x, cv, name):
         sc, sh = self._gn(x, cv.gamma, cv.beta, name)
@@ -480,6 +481,7 @@ class VQDIF:
     unet_final = property(lambda self: self.decoder.unet_final)
     up = property(lambda self: self.decoder.up)
     sdf_w = property(lambda self: self.decoder.sdf_w)
+    sdf_w_grad = property(lambda self: self.decoder.sdf_w_grad)
 
     def state_dict_np(self):
         """The (numpy, reference-layout) state dict the packed device weights were built from (122 / 110 tensors)."""
@@ -575,7 +577,48 @@ class VQDIF:
             return dict(logits=ops.sdf_query_grid(axis, grid, self.sdf_w, sigmoid=sigmoid, x_range=x_range))
         return dict(logits=ops.sdf_query(Xtg.to(self.dev, torch.float32), grid, self.sdf_w, sigmoid=sigmoid))
 
-    def decode_index_mesh(self, code_ind, res, coarse=33, margin=1, thresh=0.5, sigmoid=True, bbox=((-1.0,) * 3, (1.0,) * 3), return_levels=False):
+    def decode_index_grad(self, code_ind, Xtg):
+        """decode_index at arbitrary points with the gradient of the logit with respect to Xtg (the [-1,1] frame; what torch.autograd
+        gives on the reference's decoder, dec.py:62-100) -> dict(logits (B,N,1), grad (B,N,3)).  DESIGN 5.11."""
+        from . import ops
+        grid = self.decoder_grid_cl(self.get_code_cl(code_ind))
+        val, grad = ops.sdf_query_grad(Xtg.to(self.dev, torch.float32), grid, self.sdf_w_grad)
+        return dict(logits=val, grad=grad)
+
+    def _voff_dev(self, voff, B, V):
+        h = np.asarray(voff.cpu() if isinstance(voff, torch.Tensor) else voff).astype(np.int64)
+        if h.shape != (B + 1,) or int(h[-1]) != V:
+            raise L.SfmiError(f"vertex offsets {h.tolist()}: expected {B + 1} offsets ending at the mesh's {V} vertices")
+        return torch.from_numpy(h.astype(np.int32)).to(self.dev)
+
+    def refine_mesh_dev(self, grid_cl, verts, voff, thresh=0.5, steps=2, max_step=None):
+        """Newton projection of mesh vertices onto the iso-surface of the decoder field (the refine step of ConvONet-style generators,
+        after marching cubes): `steps` launches of the gradient kernel's step epilogue, in logit space at level = log(thresh/(1-thresh)).
+        grid_cl: the final (B,G,G,G,32) decoder grid; verts (V,3) in the [-1,1] frame, ragged by voff (B+1) as marching_cubes_dev returns
+        them; max_step: the longest move of one step (the meshing routes pass half a lattice cell).  -> verts' (V,3); faces and
+        offsets are untouched by construction."""
+        from . import ops
+        if max_step is None:
+            raise ValueError("refine_mesh_dev: max_step is required (half a lattice cell of the mesh's resolution: 1 / (Q - 1))")
+        if not 0.0 < thresh < 1.0:
+            raise ValueError(f"refine_mesh_dev: thresh = {thresh} has no logit")
+        verts = verts.to(self.dev, torch.float32).contiguous()
+        off = self._voff_dev(voff, grid_cl.shape[0], verts.shape[0])
+        level = float(np.log(thresh / (1.0 - thresh)))
+        for _ in range(int(steps)):
+            if verts.shape[0] == 0:
+                break
+            verts = ops.sdf_refine_step(verts, grid_cl, self.sdf_w_grad, level, max_step, off=off)[0]
+        return verts
+
+    def vertex_normals_dev(self, grid_cl, verts, voff):
+        """Exact unit normals -grad f / |grad f| of the decoder field at mesh vertices (outward, as the face winding of mc_tables) -> (V,3)."""
+        from . import ops
+        verts = verts.to(self.dev, torch.float32).contiguous()
+        return ops.sdf_normals(verts, grid_cl, self.sdf_w_grad, off=self._voff_dev(voff, grid_cl.shape[0], verts.shape[0]))
+
+    def decode_index_mesh(self, code_ind, res, coarse=33, margin=1, thresh=0.5, sigmoid=True, bbox=((-1.0,) * 3, (1.0,) * 3), return_levels=False,
+                          refine_steps=0, normals=False):
         """The mesh of decode_index(grid_Q=res) + marching cubes without the res^3 lattice: the decoder is queried coarse to
         fine, on a `coarse`^3 lattice first and then only around the cells the surface passes through; res = (coarse-1) 2^L + 1.
         -> verts, faces, voff, toff as marching_cubes_dev [, levels] (iso_sparse.extract_sparse_dev).  The decoder grid is built once
@@ -587,8 +630,23 @@ class VQDIF:
         grid = self.decoder_grid_cl(self.get_code_cl(code_ind), final_affine=True)
         axis = torch.from_numpy(np.linspace(-1.0, 1.0, int(res)).astype(np.float32)).to(self.dev)
         field = lambda keys, koff: ops.sdf_query_keys(axis, keys, koff, grid, self.sdf_w, sigmoid=sigmoid)
-        return iso_sparse.extract_sparse_dev(field, grid.shape[0], coarse, nl, thresh=thresh, margin=margin, bbox=bbox,
-                                             return_levels=return_levels, device=self.dev)
+        out = iso_sparse.extract_sparse_dev(field, grid.shape[0], coarse, nl, thresh=thresh, margin=margin, bbox=bbox,
+                                            return_levels=return_levels, device=self.dev)
+        if not refine_steps and not normals:
+            return out
+        # refine_steps: Newton projection of the vertices onto the iso-surface, each step at most half a cell of the res^3 lattice;
+        # normals=True: the field's unit normals at the (refined) vertices, returned after the other outputs
+        if tuple(map(tuple, bbox)) != ((-1.0,) * 3, (1.0,) * 3):
+            raise L.SfmiError("decode_index_mesh: refine_steps / normals need the vertices in the decoder's own frame, bbox = (-1,1)^3")
+        if not sigmoid and refine_steps:
+            raise L.SfmiError("decode_index_mesh: refine_steps takes thresh as an occupancy (sigmoid=True)")
+        verts, voff = out[0], out[2]
+        if refine_steps:
+            verts = self.refine_mesh_dev(grid, verts, voff, thresh=thresh, steps=refine_steps, max_step=1.0 / (int(res) - 1))
+        out = (verts,) + tuple(out[1:])
+        if normals:
+            out = out + (self.vertex_normals_dev(grid, verts, voff),)
+        return out
 
     def decode(self, grid_feat, Xtg):
         """vqdif.py:60-72 with a (B,d,R,R,R) feature grid."""
