@@ -705,8 +705,8 @@ int sfmi_enc_pack_weights(const float* fc_pos_w /*64x3*/, const float* fc_pos_b 
 
 size_t sfmi_enc_workspace_bytes(int B, int T) {
   size_t bt = (size_t)B * T;
-  // cell + order + sorted cell (3 x 4) + start map + cursor map + 2 net buffers + 2 segmax buffers + csum + ccount + scan chunk sums
-  return bt * 12 + 2 * (size_t)B * ENC_G * ENC_G * ENC_G * 4 + 2 * bt * 128 + 2 * bt * 128 + bt * 256 + bt * 4 + 256 + (((size_t)B + 1) * 4 + 255) + 256 + (size_t)B * 64 * 4 + 65536 + 1024;
+  // cell + order + sorted cell (3 x 4, each rounded up to 16 bytes) + start map + cursor map + 2 net buffers + 2 segmax buffers + csum + ccount + scan chunk sums
+  return 3 * ((bt * 4 + 15) & ~(size_t)15) + 2 * (size_t)B * ENC_G * ENC_G * ENC_G * 4 + 2 * bt * 128 + 2 * bt * 128 + bt * 256 + bt * 4 + 256 + (((size_t)B + 1) * 4 + 255) + 256 + (size_t)B * 64 * 4 + 65536 + 1024;
 }
 
 static int enc_pipeline(const float* cloud, const float* wpack, float* grid_cl, unsigned char* mask, int* cell_out, void* workspace, int B, int T,
@@ -739,9 +739,12 @@ static int enc_pipeline(const float* cloud, const float* wpack, float* grid_cl, 
   hipStream_t st = (hipStream_t)stream_;
   const size_t bt = (size_t)B * T, nc = (size_t)B * ENC_G * ENC_G * ENC_G;
   char* w = (char*)workspace;
-  int* cell = (int*)w; w += bt * 4;
-  int* order = (int*)w; w += bt * 4;
-  int* scell = (int*)w; w += bt * 4;
+  // the three (B,T) int arrays take whole 16-byte steps: everything behind them is read as int4 / float4, and csum takes 64-bit
+  // atomics - with B * T odd they sat 4 bytes off an 8-byte boundary and the staged form's first atomic faulted (B = 3, T = 33)
+  const size_t bt4 = (bt * 4 + 15) & ~(size_t)15;
+  int* cell = (int*)w; w += bt4;
+  int* order = (int*)w; w += bt4;
+  int* scell = (int*)w; w += bt4;
   int* start = (int*)w; w += nc * 4;
   int* cursor = (int*)w; w += nc * 4;
   float* net[2]; net[0] = (float*)w; w += bt * 128; net[1] = (float*)w; w += bt * 128;
