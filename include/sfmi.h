@@ -197,13 +197,21 @@ int sfmi_decode_gemm_f32(const float* x, const float* Wp16, const float* c1, con
 int sfmi_decode_gemm_prof_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out,
                               int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt, int* pblk,
                               unsigned long long* prof, void* stream);
+/* the same as sfmi_decode_gemm_f32 for a decode chain that skips ended rows (no reference counterpart: the reference steps every row
+ * until all have ended): alen (optional, M device ints) is the chain's per-row attention length of sfmi_gpt_sample_live_f32; a workgroup
+ * whose row group (up to 6 row tiles, see above) holds no row with alen >= 0 does no work and leaves its outputs as they were.
+ * alen == NULL: identical to sfmi_decode_gemm_f32. */
+int sfmi_decode_gemm_live_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out,
+                              int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt,
+                              const int* alen, void* stream);
 /* embedding of the token at t = len[b]-1 into the fragment-packed residual buffer (input of the first decode step) */
 int sfmi_gpt_embed_packed_f32(const float* E0, const float* E1, const float* Ex, const float* pos_emb, const float* cond_pos_emb,
                               const int* seq, const int* len, const int* Lc, float* resid, int B, int D, int Lmax, int end0,
                               void* stream);
 /* CausalSelfAttention.forward for ONE new position per row against the KV cache (appends the new K,V row first).
  * shared_len (optional, device int): positions < shared_len[0] are read from ROW 0's cache by every row - the `sample_n` copies
- * of one condition (shapeformer.py:222-260) keep the condition's keys / values once */
+ * of one condition (shapeformer.py:222-260) keep the condition's keys / values once.
+ * A row whose len[b] is < 1 is skipped: y = 0 for it, its cache is neither read nor appended to (sfmi_gpt_sample_live_f32). */
 int sfmi_gpt_attn_decode_f32(const float* qkv_packed, const float* unused, float* Kc, float* Vc, const int* len, float* y_packed,
                              int S, int B, int D, int H, int Lmax, const int* shared_len, void* stream);
 /* the same behind the attention turnstile of the interleaved decode chains (no reference counterpart: the reference runs one
@@ -226,6 +234,19 @@ int sfmi_gpt_sample_f32(const float* part, int* seq, int* len, const int* Lc, fl
                         int row_offset, int rows_total,
                         int step_offset /* tokens generated before this run (non-empty z_indices, shapeformer.py:60-70): step j = len - Lc - step_offset */,
                         void* stream);
+/* the same, keeping the per-row ATTENTION LENGTH alen (B device ints, initialised to len by the caller; NULL: exactly
+ * sfmi_gpt_sample_f32): a launch that advances sets alen[b] = len[b], or -1 once row b has ENDED - skip_ended != 0, mask_invalid != 0,
+ * no hist, no force, and the token just completed (tuple_i == 1) has position end0 with the row's next step index >= 1.  Every later
+ * token of such a row is (end0, end1) with log-probability +0.0 whatever the logits are (sampling_masker leaves one finite entry), so
+ * a row with alen[b] < 0 gets exactly that without its logits being read, and its `resid` row is reset to zeros by the tuple_i == 1
+ * launch.  Pass alen as the `len` of sfmi_gpt_attn_decode_gated_f32 (a length < 0: y = 0, no cache read, no append) and to
+ * sfmi_decode_gemm_live_f32.  seq, len and logp are bit-identical to sfmi_gpt_sample_f32's. */
+int sfmi_gpt_sample_live_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
+                             float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D, int S,
+                             int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
+                             float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
+                             unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
+                             int* alen, int skip_ended, void* stream);
 /* ShapeRepresenter.sampling_masker alone (representers.py:120-155): logits (B,ldv) -> masked copy out (B,V); no draw, seq / len
  * are read only.  Row b holds len[b] complete tokens; for tuple_i == 1 the position just drawn sits at seq[b][len[b]][0]. */
 int sfmi_gpt_mask_logits_f32(const float* logits, const int* seq, const int* len, const int* Lc, float* out, int B, int V, int ldv,

@@ -170,6 +170,11 @@ struct DGemmArgs {
   float* slab; int* cnt;   // split-K scratch: ceil(M/16)*ceil(N/16)*S*320 floats, ceil(M/16)*ceil(N/16) ints (zeroed once)
   int* pblk; unsigned long long* prof;   // optional in-situ launch timing (prof_begin / prof_end_last)
   int prio;                              // s_setprio level of every wave of the launch (0 = hardware default; knob dgemm_prio)
+  // optional per-row attention length of the chain (SampleArgs::alen; < 0 = the row has ended): a workgroup whose row group holds no
+  // live row leaves after issuing its first operand batch - no MFMAs, no epilogue, no split-K ticket.  alen changes only in sampler
+  // launches of the same stream, so the S slices of a (tile, group) all take the same decision.  Outputs of such a group keep their
+  // previous (finite) contents; nobody reads them: the sampler does not read an ended row's logits.
+  const int* alen;
 };
 
 // Decode activations live in MFMA-fragment-packed layout: an (M x N) tensor is stored as
@@ -263,6 +268,14 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs a) {
     if (a.resid) pres = *reinterpret_cast<const f32x4*>(a.resid + off_ep);
   }
   const int steps = kw / 16;
+  // liveness of this group's rows, requested in the same round trip as the first operand batch (a dependent trip in front of the
+  // batch would cost every live group ~1.5 us per launch): lane l looks at rows l and 64 + l of the group
+  int live = 1;
+  if (a.alen) {
+    const int r0 = t0 * 16 + lane, r1 = r0 + 64;
+    live = lane < MT * 16 && r0 < a.M && a.alen[min(r0, a.M - 1)] >= 0;
+    if (MT > 4) live |= lane + 64 < MT * 16 && r1 < a.M && a.alen[min(r1, a.M - 1)] >= 0;
+  }
   // software pipeline over batches of UN k16-steps: the loads of batch b+1 are issued BEFORE the MFMAs of batch b
   // (two register sets, statically indexed), and every load of a batch is pinned ahead of the first MFMA that
   // follows (sched_barrier) - hipcc otherwise sinks loads next to their uses and the kernel turns latency-bound.
@@ -297,6 +310,7 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs a) {
       for (int j = 0; j < MT; ++j) xb[u][j] = xr[j][P::xidx((s0 + u) * 64) + lo];
     }
     __builtin_amdgcn_sched_barrier(0);
+    if (s0 == 0 && a.alen && __ballot(live) == 0ull) return;      // every wave of the workgroup sees the same rows: a uniform exit
 #pragma unroll
     for (int u = 0; u < UN; ++u) mfma_step(w[u], xb[u]);
   }
@@ -450,6 +464,13 @@ __device__ __forceinline__ void attn_decode_item(AttnLds<NWV>& s, const AttnArgs
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, HD = a.HD, D = a.D, Lmax = a.Lmax;
   const int t = __builtin_amdgcn_readfirstlane(a.len[b] - 1);  // position being processed
+  // a row that has ENDED comes with a length of -1 (the caller passes the per-row attention length, SampleArgs::alen): its tokens
+  // are forced from here on, so nothing of its cache is streamed and nothing is appended to it.  Uniform for the workgroup, and
+  // inside the item: the kernel's tail (finished-workgroup count, turnstile release, launch timing) runs as for any other item.
+  if (t < 0) {
+    if (tid < HD) a.y[pk_off(b, h * HD + tid, D)] = 0.f;
+    return;
+  }
   const int nq4 = HD / 4;
   float* Kb = a.Kc + ((long long)b * H + h) * Lmax * HD;
   float* Vb = a.Vc + ((long long)b * H + h) * Lmax * HD;
@@ -820,6 +841,12 @@ struct SampleArgs {
   int step_offset;              // tokens generated BEFORE this call (a non-empty z_indices, shapeformer.py:60-70): the step counter
                                 // of masker / history / log-prob / uniforms restarts at 0 at the first new token, as the reference's does
   float* mask_out;              // mask-only mode (sfmi_gpt_mask_logits_f32): masked logits -> mask_out[b*V + v], nothing else happens
+  // per-row attention length (sfmi_gpt_sample_live_f32), or null: alen[b] == len[b] while row b is live, -1 once it has ENDED - its
+  // last position is end0 and its next step index is >= 1, so with mask_invalid the only finite position logit is end0 and the
+  // value head is forced to end1: every later token is (end0, end1) with log-probability exactly 0, whatever the model computes.
+  // The decode attention is handed alen in place of len and streams nothing for an ended row; this kernel writes the forced token
+  // without reading the logits.  skip_ended == 0: alen only follows len.
+  int* alen; int skip_ended;
 };
 
 #define SMP_MAXC 512
@@ -844,6 +871,21 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   int* cidx = big ? reinterpret_cast<int*>(dyn_lds + SMP_BIG) : cidx_s;
   float* cexp = big ? dyn_lds + 2 * SMP_BIG : cexp_s;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (a.alen && a.skip_ended && a.alen[b] < 0) {
+    // ended row (uniform per workgroup): the forced token and its log-probability of +0.0f; no logits are read, nothing is sorted
+    const int L = a.len[b], j = L - a.Lc[b] - a.step_offset;
+    if (tid == 0) {
+      a.seq[((long long)b * a.Lmax + L) * 2 + a.tuple_i] = a.tuple_i ? a.end1 : a.end0;
+      if (a.logp && j < a.max_steps) a.logp[((long long)b * a.max_steps + j) * 2 + a.tuple_i] = 0.0f;
+      if (a.advance) a.len[b] = L + 1;
+    }
+    // the row's residual is no longer refreshed by the embedding tail below, and the block GEMMs keep adding to it: reset it once
+    // per step so that it stays finite however long the other rows run
+    if (a.resid && a.tuple_i == 1)
+      for (int qd = tid; qd < a.D / 4; qd += 256)
+        *reinterpret_cast<f32x4*>(a.resid + pk_off(b, 4 * qd, a.D)) = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
   // Everything the row needs from HBM is requested in ONE round trip: the logits (registers), the row's state words, and the
   // POSITION column of its token row (LDS, when it fits: Lmax <= SMP_NPOS) - the masks' binary searches over the condition and the
   // last / current positions are then LDS reads instead of chains of 8-10 dependent global loads (~1 us each: the sampler sits on
@@ -1072,7 +1114,11 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   if (tid == 0) {
     a.seq[((long long)b * a.Lmax + L) * 2 + a.tuple_i] = choice;
     if (a.logp && j < a.max_steps) a.logp[((long long)b * a.max_steps + j) * 2 + a.tuple_i] = lg[choice] - lse;
-    if (a.advance) a.len[b] = L + 1;
+    if (a.advance) {
+      a.len[b] = L + 1;
+      // the token just completed has position end0 and the row's next step index j + 1 is >= 1: the row has ended (SampleArgs::alen)
+      if (a.alen) a.alen[b] = (a.skip_ended && a.tuple_i == 1 && cur_pos == a.end0 && j + 1 >= 1) ? -1 : L + 1;
+    }
   }
   // ---- fused tails --------------------------------------------------------------------------
   if (a.resid) {
@@ -1195,7 +1241,8 @@ __global__ void set_len_kernel(int* len, const int* src, int B, int delta) {
 template <class P>
 static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out, int M,
                               int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt, int* pblk,
-                              unsigned long long* prof, void* stream) {
+                              unsigned long long* prof, void* stream, const int* alen = nullptr) {
+  if (prof && alen) return SFMI_EINVAL;      // a timed launch counts every workgroup at its end: no early exits
   if (!x || !Wp16 || !out || M <= 0 || M > 192 || S <= 0 || K % S || (ln && !c1)) return SFMI_EINVAL;   // larger batches: several chains (gpt.py)
   if (out_packed && N % 16) return SFMI_EINVAL;
   if (!out_packed && (ldo < N || ldo % 4)) return SFMI_EINVAL;   // row-major rows are written as float4s up to round_up(N, 4)
@@ -1216,7 +1263,7 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
   if (MT > mt_cap) { groups = (tiles + mt_cap - 1) / mt_cap; MT = (tiles + groups - 1) / groups; }
   DGemmArgs a;
   a.x = x; a.Wp = Wp16; a.c1 = c1; a.c2 = c2; a.resid = resid; a.out = out; a.M = M; a.N = N; a.K = K; a.ldo = ldo; a.ln = ln; a.act = act;
-  a.out_packed = out_packed; a.slab = slab; a.cnt = cnt; a.pblk = pblk; a.prof = prof; a.prio = g_tune.dgemm_prio;
+  a.out_packed = out_packed; a.slab = slab; a.cnt = cnt; a.pblk = pblk; a.prof = prof; a.prio = g_tune.dgemm_prio; a.alen = alen;
   hipStream_t st = (hipStream_t)stream;
   if ((g_tune.dgemm_nt2 == 2 || (g_tune.dgemm_nt2 == 1 && tiles % 3 == 0)) && NWv == 8 && (kslice / 8 / 16) % 2 == 0 && tiles >= 3) {
     // two n-tiles per wave, row groups of <= 3 row tiles, batches of two k16-steps: 5 operand loads per 24 MFMAs (7 in the one-tile
@@ -1311,6 +1358,11 @@ int sfmi_decode_gemm_f32(const float* x, const float* Wp16, const float* c1, con
                          float* out, int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab,
                          int* cnt, void* stream) {
   return decode_gemm_launch<DgProduct>(x, Wp16, c1, c2, resid, out, M, N, K, ldo, ln, act, out_packed, S, slab, cnt, nullptr, nullptr, stream);
+}
+int sfmi_decode_gemm_live_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid,
+                              float* out, int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab,
+                              int* cnt, const int* alen, void* stream) {
+  return decode_gemm_launch<DgProduct>(x, Wp16, c1, c2, resid, out, M, N, K, ldo, ln, act, out_packed, S, slab, cnt, nullptr, nullptr, stream, alen);
 }
 
 // replaces get_embeddings (mingpt.py:256-286) + the AR_N extra index (representers.py:188-196,432-442)
@@ -1424,12 +1476,12 @@ int sfmi_gpt_attn_prefill_lse_sd_f32(const float* qkv, float* Kc, float* Vc, con
 // replaces sampling_masker + sample_logits for one tuple element (representers.py:120-155, common.py:260-299,
 // shapeformer.py:91-106); advance != 0 also appends the token (len += 1).  Optional fused tail (resid != NULL):
 // tuple 0: resid[b] += E0[pos'] ; tuple 1: resid[b] = embedding of the completed token (next step's input).
-int sfmi_gpt_sample_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
-                        float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
-                        int S, int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
-                        float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
-                        unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
-                        void* stream) {
+int sfmi_gpt_sample_live_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
+                             float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
+                             int S, int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
+                             float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
+                             unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
+                             int* alen, int skip_ended, void* stream) {
   if (!part || !seq || !len || !Lc || V > 4352 || temperature <= 0.f || rows_total < B + row_offset || step_offset < 0) return SFMI_EINVAL;
   if (resid && (!E0 || (tuple_i == 1 && (!E1 || !Ex || !pos_emb)) || D % 4)) return SFMI_EINVAL;
   SampleArgs a;
@@ -1439,10 +1491,23 @@ int sfmi_gpt_sample_f32(const float* part, int* seq, int* len, const int* Lc, fl
   a.mask_invalid = mask_invalid; a.mask_completion = mask_completion; a.max_steps = max_steps; a.advance = advance;
   a.top_p = top_p; a.temperature = temperature; a.seed = seed; a.seed_dev = seed_dev; a.row_offset = row_offset; a.rows_total = rows_total;
   a.mask_out = nullptr; a.step_offset = step_offset;
+  // ended rows are skipped only where their tokens are forced and nobody looks at their logits: mask_invalid on, no logits history,
+  // no teacher forcing
+  a.alen = alen; a.skip_ended = (alen && skip_ended && mask_invalid && !hist && !force) ? 1 : 0;
   const size_t dyn = (top_k <= 0 || top_k > SMP_MAXC) ? (size_t)SMP_BIG * 12 : 0;
   hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(256), dyn, (hipStream_t)stream, a);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
+}
+int sfmi_gpt_sample_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
+                        float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
+                        int S, int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
+                        float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
+                        unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
+                        void* stream) {
+  return sfmi_gpt_sample_live_f32(part, seq, len, Lc, logp, hist, force, resid, E0, E1, Ex, pos_emb, D, S, B, V, ldv, Lmax, tuple_i, end0,
+                                  end1, top_k, top_p, temperature, greedy_row0, mask_invalid, mask_completion, max_steps, seed, seed_dev,
+                                  advance, row_offset, rows_total, step_offset, nullptr, 0, stream);
 }
 
 // replaces ShapeRepresenter.sampling_masker alone (representers.py:120-155): logits (B,ldv) -> masked copy out (B,V); the masking

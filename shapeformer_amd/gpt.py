@@ -210,6 +210,7 @@ class CondTupleGPT:
         st = dict(key=key,
                   seq=torch.zeros(B, self.Lmax + 1, 2, device=dev, dtype=torch.int32),
                   len=torch.zeros(B, device=dev, dtype=torch.int32), Lc=torch.zeros(B, device=dev, dtype=torch.int32),
+                  alen=torch.zeros(B, device=dev, dtype=torch.int32),    # per-row attention length: len while the row is live, -1 once it has ended (SKIP_ENDED)
                   resid=torch.zeros(Bp, D, device=dev), qkv=torch.zeros(Bp, 3 * D, device=dev), y=torch.zeros(Bp, D, device=dev),
                   h=torch.zeros(Bp, 4 * D, device=dev), logit=f(B, self.Vpad),
                   slab=f(L.lib().sfmi_decode_gemm_slab_floats(Bp, 4 * D, 4)), cnt=torch.zeros(Bp // 16 * (max(4 * D, self.Vpad) // 16 + 1), device=dev, dtype=torch.int32),
@@ -249,11 +250,17 @@ class CondTupleGPT:
         return out
 
     # ------------------------------------------------------------------ C-ABI wrappers
-    def _dgemm(self, x, wp, c1, c2, resid, out, M, N, K, ldo, ln, act, packed=1, S=1, st=None, prof=False):
+    def _dgemm(self, x, wp, c1, c2, resid, out, M, N, K, ldo, ln, act, packed=1, S=1, st=None, prof=False, alen=None):
+        """alen: the chain's per-row attention length (st["alen"]): row groups without a live row do no work (not with prof: a timed
+        launch counts every workgroup at its end)."""
         st = st or self._state
         while S > 1 and (K // S) % 128:
             S //= 2
         slab, cnt = (L.ptr(st["slab"]), L.ptr(st["cnt"])) if S > 1 else (None, None)
+        if alen is not None and not prof:
+            L.check(L.lib().sfmi_decode_gemm_live_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
+                                                      ln, act, packed, S, slab, cnt, L.ptr(alen), L.stream_ptr()), "sfmi_decode_gemm_live_f32")
+            return
         if prof:
             L.check(L.lib().sfmi_decode_gemm_prof_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
                                                       ln, act, packed, S, slab, cnt, L.ptr(st["pblk"]), L.ptr(st["prof"][4:]),
@@ -453,6 +460,13 @@ class CondTupleGPT:
     # L_c = 84), shared above (1.153 vs 1.116 at 300); 64 rows: shared wins from L_c = 84 on (2.037 vs 1.965; 2.569 vs 2.168 at 300).
     SHARED_PREFIX_MIN_ROW_TOKENS = 2800      # rows x condition length from which the shared form is taken
     SINGLE_CHAIN_ROWS = 96  # `sample` keeps a batch in ONE chain up to here and interleaves chains above (a lone chain cannot overlap anything)
+    # A row whose last position is the end token can only draw (end0, end1) from then on (mask_invalid: one finite logit per head,
+    # log-probability 0), yet it keeps stepping until ALL rows have ended (shapeformer.py:110-115).  True: such a row's KV cache is no
+    # longer streamed or appended to, its sampler writes the forced token without reading logits (st["alen"], csrc/gpt.hip SampleArgs::alen),
+    # and with SKIP_ENDED_GEMM a decode-GEMM row group without a live row does no work.  seq / len / logp are bit-identical either way.
+    # Armed only with mask_invalid, without logits history, teacher forcing or a timing ablation (those measure every row's stream).
+    SKIP_ENDED = True
+    SKIP_ENDED_GEMM = True
 
     def decode_step(self, st, B, sp):
         """Position t = len[b]-1 of every row through both stages; st["resid"] must hold its embedding on entry
@@ -467,34 +481,38 @@ class CondTupleGPT:
         pa, pg = "attn" in self._profile, "gemm" in self._profile      # in-situ launch timing (results untouched)
         # in-kernel split-K per GEMM (only the K = 4 n_embd product, and proj at <= 16 rows, use it)
         Sqkv, Sproj, Sfc1, Sfc2, Shead = 1, self.S_PROJ if B <= 16 else self.S_PROJ_M, 1, self.S_FC2, 1
+        armed = int(sp.get("skip_ended", 0))
+        # ended rows: the attention gets alen in its `len` slot (no new kernel argument), the GEMMs get it to drop all-ended row groups
+        alen_a = st["alen"] if armed else st["len"]
+        alen_g = st["alen"] if armed >= 2 else None
         for li, ly in enumerate(self.layers):
             stage_end = li + 1 == len(self.layers) or self.layers[li + 1].stage != ly.stage
             if "gemm" not in skip:
-                self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg)
+                self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg, alen=alen_g)
             if "attn" not in skip:
                 L.check(lib.sfmi_gpt_attn_decode_gated_f32(L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]),
-                                                           L.ptr(st["len"]), L.ptr(st["y"]), B, D, self.H, self.Lmax + 1,
+                                                           L.ptr(alen_a), L.ptr(st["y"]), B, D, self.H, self.Lmax + 1,
                                                            L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
                                                            L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
                                                            L.ptr(st["prof"]) if pa else None, L.stream_ptr()), "sfmi_gpt_attn_decode_gated_f32")
             if "gemm" not in skip:
-                self._dgemm(st["y"], ly.pproj, None, ly.bproj, r, r, B, D, D, D, 0, 0, S=Sproj, st=st, prof=pg)
-                self._dgemm(r, ly.pfc1, ly.c1fc1, ly.c2fc1, None, st["h"], B, 4 * D, D, 4 * D, 1, 1, S=Sfc1, st=st, prof=pg)
-                self._dgemm(st["h"], ly.pfc2, None, ly.bfc2, r, r, B, D, 4 * D, D, 0, 0, S=Sfc2, st=st, prof=pg)
+                self._dgemm(st["y"], ly.pproj, None, ly.bproj, r, r, B, D, D, D, 0, 0, S=Sproj, st=st, prof=pg, alen=alen_g)
+                self._dgemm(r, ly.pfc1, ly.c1fc1, ly.c2fc1, None, st["h"], B, 4 * D, D, 4 * D, 1, 1, S=Sfc1, st=st, prof=pg, alen=alen_g)
+                self._dgemm(st["h"], ly.pfc2, None, ly.bfc2, r, r, B, D, 4 * D, D, 0, 0, S=Sfc2, st=st, prof=pg, alen=alen_g)
             if stage_end:
                 s = ly.stage
                 hp, hc1, hc2 = self.head_f[s]
-                self._dgemm(r, hp, hc1, hc2, None, st["logit"], B, self.V, D, self.Vpad, 1, 0, packed=0, S=Shead, st=st)
+                self._dgemm(r, hp, hc1, hc2, None, st["logit"], B, self.V, D, self.Vpad, 1, 0, packed=0, S=Shead, st=st, alen=alen_g)
                 hist = sp["hist"][s] if sp.get("hist") is not None else None
-                L.check(lib.sfmi_gpt_sample_f32(L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
-                                                L.ptr(st["logp"]), L.ptr(hist), L.ptr(sp.get("force")),
-                                                L.ptr(r), L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), D,
-                                                1, B, self.V, self.Vpad, self.Lmax + 1,
-                                                s, self.end[0], self.end[1], sp["top_k"], sp["top_p"], sp["temperature"],
-                                                int(sp["best_in_first"]), int(sp["mask_invalid"]),
-                                                int(sp["mask_invalid_completion"]), sp["max_steps"], sp["seed"], L.ptr(st.get("seed")), int(s == 1),
-                                                sp.get("row_offset", 0), sp.get("rows_total", B), int(sp.get("step_offset", 0)),
-                                                L.stream_ptr()), "sfmi_gpt_sample_f32")
+                L.check(lib.sfmi_gpt_sample_live_f32(L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
+                                                     L.ptr(st["logp"]), L.ptr(hist), L.ptr(sp.get("force")),
+                                                     L.ptr(r), L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), D,
+                                                     1, B, self.V, self.Vpad, self.Lmax + 1,
+                                                     s, self.end[0], self.end[1], sp["top_k"], sp["top_p"], sp["temperature"],
+                                                     int(sp["best_in_first"]), int(sp["mask_invalid"]),
+                                                     int(sp["mask_invalid_completion"]), sp["max_steps"], sp["seed"], L.ptr(st.get("seed")), int(s == 1),
+                                                     sp.get("row_offset", 0), sp.get("rows_total", B), int(sp.get("step_offset", 0)),
+                                                     L.ptr(st["alen"]), int(bool(armed)), L.stream_ptr()), "sfmi_gpt_sample_live_f32")
 
     # ------------------------------------------------------------------ sample_indices
     def _prepare(self, c_tokens, Lc, max_steps, sp_kw, slot=0, row_offset=0, rows_total=None, return_logits=False,
@@ -524,6 +542,7 @@ class CondTupleGPT:
             st["seq"][torch.arange(B, device=self.dev)[:, None], pos] = torch.as_tensor(z_tokens).to(self.dev, torch.int32)
             st["len"].add_(Lz)
             shared_prefix = False
+        st["alen"].copy_(st["len"])
         st["logp"].zero_()
         st["seed"].copy_(torch.from_numpy(np.array([sp_kw["seed"]], np.uint32).view(np.int32)))
         hist = None
@@ -532,6 +551,10 @@ class CondTupleGPT:
         sp = dict(sp_kw, max_steps=int(max_steps), hist=hist, row_offset=int(row_offset),
                   rows_total=int(rows_total if rows_total is not None else B), chain=int(slot - 100 if slot >= 100 else 0),
                   shared_prefix=bool(shared_prefix), step_offset=Lz, gate_lanes=int(gate_lanes))
+        # ended rows are skipped (0 = no, 1 = attention + sampler, 2 = and the decode GEMMs' all-ended row groups) only where their tokens
+        # are forced and nobody looks at their logits; a launch-shape choice like the others: part of the graph-cache key through sp
+        sp["skip_ended"] = (2 if self.SKIP_ENDED_GEMM else 1) if (self.SKIP_ENDED and sp_kw["mask_invalid"] and not return_logits
+                                                                  and force_tokens is None and not self._ablate) else 0
         if force_tokens is not None:   # (B,max_steps,2) teacher forcing for stepwise parity tests
             ft = torch.zeros(B, max_steps, 2, dtype=torch.int32)
             ft[:, :force_tokens.shape[1]] = torch.as_tensor(force_tokens).to(torch.int32)
@@ -573,7 +596,7 @@ class CondTupleGPT:
             if cached is None or cached[0] != gkey or return_logits:
                 side = torch.cuda.Stream(device=self.dev)
                 side.wait_stream(torch.cuda.current_stream())
-                saved = {k: st[k].clone() for k in ("seq", "len", "logp", "resid")}
+                saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid")}
                 with torch.cuda.stream(side):
                     self.decode_step(st, B, sp)      # warm-up outside capture
                 torch.cuda.current_stream().wait_stream(side)
