@@ -204,6 +204,22 @@ int sfmi_decode_gemm_prof_f32(const float* x, const float* Wp16, const float* c1
 int sfmi_decode_gemm_live_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out,
                               int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt,
                               const int* alen, void* stream);
+/* Decode step of a PACKED chain (CondTupleGPT.COMPACT_LIVE): the live rows of the chain sit in slots 0 .. nlive-1 of the activation
+ * buffers, in ascending row order; what persists (seq, len, alen, Lc, logp, the KV caches) stays indexed by row.
+ * sfmi_gpt_compact_rows_f32, at the head of a step: builds the map from alen (slot_of[B]: the row's slot, -1 once it has ended;
+ * row_of[Bpad]: live rows first, then the ended ones, both ascending; slot_len[Bpad] = alen by slot, -1 without a live row; *nlive)
+ * and moves the step's embeddings from `stage` (B x D row-major: sfmi_gpt_embed_rows_f32 / the stage-1 tail of
+ * sfmi_gpt_sample_rows_f32) into the fragment-packed resid at the rows' slots; slots without a live row are zeroed.
+ * sfmi_decode_gemm_rows_f32: sfmi_decode_gemm_f32 for the row tiles that hold a live slot - a row group (see above) of MT tiles
+ * runs min(max(ceil(*nlive / 16) - first tile, 0), MT) of them (partial == 0: all MT unless that count is 0); the launch form is
+ * chosen from M alone, so every row it computes has sfmi_decode_gemm_f32's bits; the other tiles' outputs keep their contents. */
+int sfmi_gpt_compact_rows_f32(const int* alen, int* slot_of, int* row_of, int* nlive, int* slot_len, const float* stage, float* resid,
+                              int B, int Bpad, int D, void* stream);
+int sfmi_decode_gemm_rows_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out,
+                              int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt,
+                              const int* nlive, int partial, void* stream);
+int sfmi_gpt_embed_rows_f32(const float* E0, const float* E1, const float* Ex, const float* pos_emb, const float* cond_pos_emb,
+                            const int* seq, const int* len, const int* Lc, float* stage, int B, int D, int Lmax, int end0, void* stream);
 /* embedding of the token at t = len[b]-1 into the fragment-packed residual buffer (input of the first decode step) */
 int sfmi_gpt_embed_packed_f32(const float* E0, const float* E1, const float* Ex, const float* pos_emb, const float* cond_pos_emb,
                               const int* seq, const int* len, const int* Lc, float* resid, int B, int D, int Lmax, int end0,
@@ -222,6 +238,11 @@ int sfmi_gpt_attn_decode_f32(const float* qkv_packed, const float* unused, float
 int sfmi_gpt_attn_decode_gated_f32(const float* qkv_packed, float* Kc, float* Vc, const int* len, float* y_packed, int B, int D, int H,
                                    int Lmax, const int* shared_len, int* sem, int* blk, int lanes, unsigned long long* prof,
                                    void* stream);
+/* the same for a packed chain: item (s, head) reads qkv and slot_len and writes y at SLOT s and walks the caches of row row_of[s];
+ * the shared prefix is read from cache row 0 */
+int sfmi_gpt_attn_decode_rows_f32(const float* qkv_packed, float* Kc, float* Vc, const int* slot_len, const int* row_of, float* y_packed,
+                                  int B, int D, int H, int Lmax, const int* shared_len, int* sem, int* blk, int lanes,
+                                  unsigned long long* prof, void* stream);
 /* one tuple element of one sampling step per row: sampling_masker (representers.py:120-155) + filter_sampling_logits /
  * sample_logits (models/common.py:260-299: temperature, top-k with ties, top-p) + inverse-CDF draw from counter-hash uniforms
  * indexed (step, tuple, row_offset + b) + best_in_first greedy row + log-prob + optional masked-logit history; writes the
@@ -247,6 +268,13 @@ int sfmi_gpt_sample_live_f32(const float* part, int* seq, int* len, const int* L
                              float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
                              unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
                              int* alen, int skip_ended, void* stream);
+/* the sampler of a packed chain (mask_invalid on, no history, no forcing): one workgroup per ROW; logits and (stage 0) the residual
+ * at slot_of[b], the stage-1 tail into stage[b]; a row with slot_of[b] < 0 takes the forced token.  Same seq / len / alen / logp. */
+int sfmi_gpt_sample_rows_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* resid, float* stage,
+                             const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D, int S, int B, int V, int ldv,
+                             int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p, float temperature, int greedy_row0,
+                             int mask_completion, int max_steps, unsigned seed, const unsigned* seed_dev, int advance, int row_offset,
+                             int rows_total, int step_offset, int* alen, const int* slot_of, void* stream);
 /* ShapeRepresenter.sampling_masker alone (representers.py:120-155): logits (B,ldv) -> masked copy out (B,V); no draw, seq / len
  * are read only.  Row b holds len[b] complete tokens; for tuple_i == 1 the position just drawn sits at seq[b][len[b]][0]. */
 int sfmi_gpt_mask_logits_f32(const float* logits, const int* seq, const int* len, const int* Lc, float* out, int B, int V, int ldv,

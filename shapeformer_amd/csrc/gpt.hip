@@ -16,6 +16,7 @@
 //             top-p cut, counter-hash uniforms (no host RNG, no per-step D2H of (B,4097) logits)
 #include "sfmi_common.h"
 #include <mutex>
+#include <type_traits>
 #include <string>
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -175,6 +176,13 @@ struct DGemmArgs {
   // launches of the same stream, so the S slices of a (tile, group) all take the same decision.  Outputs of such a group keep their
   // previous (finite) contents; nobody reads them: the sampler does not read an ended row's logits.
   const int* alen;
+  // optional live-row count of a chain whose live rows are PACKED into slots 0 .. nlive-1 (compact_rows_kernel): a row group runs only
+  // its row tiles that hold a live slot, mtl = clamp(ceil(nlive / 16) - t0, 0, MT): MFMAs, statistics, the LDS hand-off and the
+  // epilogue of the other tiles sit behind wave-uniform branches of the one kernel body (partial == 0: all MT tiles of a group with
+  // mtl > 0, the plain group exit).  A tile that is not run still costs its activation loads (unconditional, so the batch keeps its
+  // graded waits) and the epilogue operands prefetched for it.  The instance (MT, NW, UN, NT) and S are chosen from M alone, so a
+  // row's summation order never depends on nlive; a tile that is not run takes no split-K ticket and its outputs keep their contents.
+  const int* nlive; int partial;
 };
 
 // Decode activations live in MFMA-fragment-packed layout: an (M x N) tensor is stored as
@@ -276,13 +284,14 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs a) {
     live = lane < MT * 16 && r0 < a.M && a.alen[min(r0, a.M - 1)] >= 0;
     if (MT > 4) live |= lane + 64 < MT * 16 && r1 < a.M && a.alen[min(r1, a.M - 1)] >= 0;
   }
+  // the packed chain's live-row count: one scalar word, requested in that same round trip
+  const int nl = a.nlive ? *a.nlive : 0;
+  int mtl = MT;      // row tiles of this group that are run (wave-uniform; MT wherever the chain is not packed)
   // software pipeline over batches of UN k16-steps: the loads of batch b+1 are issued BEFORE the MFMAs of batch b
   // (two register sets, statically indexed), and every load of a batch is pinned ahead of the first MFMA that
   // follows (sched_barrier) - hipcc otherwise sinks loads next to their uses and the kernel turns latency-bound.
-  auto mfma_step = [&](const f32x4 (&wv)[NT], const f32x4 (&xs)[MT]) {
-#pragma unroll
-    for (int j = 0; j < MT; ++j) {
-      const f32x4 xv = xs[j];
+  auto mfma_tile = [&](const int j, const f32x4 (&wv)[NT], const f32x4 xv) {
+    {
       // LayerNorm statistics (a few VALU ops; computed unconditionally, only used when a.ln)
       if (!P::kNoStats && (!P::kStatsOnlyIfLn || a.ln)) {
         s1[j] += (xv[0] + xv[1]) + (xv[2] + xv[3]);
@@ -310,9 +319,26 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs a) {
       for (int j = 0; j < MT; ++j) xb[u][j] = xr[j][P::xidx((s0 + u) * 64) + lo];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (s0 == 0 && a.alen && __ballot(live) == 0ull) return;      // every wave of the workgroup sees the same rows: a uniform exit
+    if (s0 == 0) {
+      if (a.alen && __ballot(live) == 0ull) return;      // every wave of the workgroup sees the same rows: a uniform exit
+      if (a.nlive) {                                     // one word for the whole launch: uniform as well
+        mtl = min(max(((nl + 15) >> 4) - t0, 0), MT);
+        if (mtl == 0) return;
+        if (!a.partial) mtl = MT;
+      }
+    }
+    // Row tile by row tile, behind a wave-uniform branch that holds MFMAs and statistics only: a tile without a live slot costs its
+    // (unconditional) activation loads and nothing else.  Per tile the k16-steps stay in ascending order: the same sums.
+    // (Bodies templated on the live tile count, dispatched behind the first batch, were built first: the structurizer lays them out
+    //  one after the other, the first batch - which each of them reads - stays live across all of them, and <3,8,2,2> needed 150
+    //  registers; under a bound of 128 it spilled.)
 #pragma unroll
-    for (int u = 0; u < UN; ++u) mfma_step(w[u], xb[u]);
+    for (int j = 0; j < MT; ++j) {
+      if (j < mtl) {
+#pragma unroll
+        for (int u = 0; u < UN; ++u) mfma_tile(j, w[u], xb[u][j]);
+      }
+    }
   }
   if (P::kSkipEpilogue) {   // ablation policies only: main loop alone (one store per lane keeps the accumulators alive)
     f32x4 t = {0.f, 0.f, 0.f, 0.f};
@@ -323,6 +349,7 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs a) {
   }
 #pragma unroll
   for (int j = 0; j < MT; ++j) {
+    if (j >= mtl) break;
 #pragma unroll
     for (int nn = 0; nn < NT; ++nn) {
       const f32x4 t = acc[j][nn][0] + acc[j][nn][1];
@@ -337,8 +364,8 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs a) {
     }
   }
   __syncthreads();
-  // epilogue: wave w finishes the virtual tiles v = w, w+NW, ...
-  for (int v = wave; v < VT; v += NW) {
+  // epilogue: wave w finishes the virtual tiles v = w, w+NW, ... (row tile v / NT: the ones that were run are v < mtl * NT)
+  for (int v = wave; v < mtl * NT; v += NW) {
     const int j = v / NT, nt = nt0 + v % NT;
     if (nt >= ntiles) continue;          // masked second tile of an odd tile count (wave-uniform)
     f32x4 r = {0.f, 0.f, 0.f, 0.f};
@@ -434,6 +461,9 @@ struct AttnArgs {
   float* Kc; float* Vc;  // (B,H,Lmax,HD)
   const int* len; float* y /*fragment-packed (M x D)*/;
   const int* shared_len;
+  // packed chain (sfmi_gpt_attn_decode_rows_f32), or null: item b is SLOT b - qkv, y and len are indexed by slot, the caches belong to
+  // row row_of[b].  A slot without a live row comes with a length of -1 like an ended row.
+  const int* row_of;
   int B, H, D, Lmax, HD; float scale;
   int* sem;      // optional turnstile words {next ticket, finished launches, gate time-outs}: the LAST workgroup of a launch bumps sem[1]
   int* blk;      // this chain's finished-workgroup counter (re-armed by the last workgroup)
@@ -464,6 +494,7 @@ __device__ __forceinline__ void attn_decode_item(AttnLds<NWV>& s, const AttnArgs
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, HD = a.HD, D = a.D, Lmax = a.Lmax;
   const int t = __builtin_amdgcn_readfirstlane(a.len[b] - 1);  // position being processed
+  const int rb = a.row_of ? __builtin_amdgcn_readfirstlane(a.row_of[b]) : b;      // the row whose caches this item walks (same round trip as len)
   // a row that has ENDED comes with a length of -1 (the caller passes the per-row attention length, SampleArgs::alen): its tokens
   // are forced from here on, so nothing of its cache is streamed and nothing is appended to it.  Uniform for the workgroup, and
   // inside the item: the kernel's tail (finished-workgroup count, turnstile release, launch timing) runs as for any other item.
@@ -472,8 +503,8 @@ __device__ __forceinline__ void attn_decode_item(AttnLds<NWV>& s, const AttnArgs
     return;
   }
   const int nq4 = HD / 4;
-  float* Kb = a.Kc + ((long long)b * H + h) * Lmax * HD;
-  float* Vb = a.Vc + ((long long)b * H + h) * Lmax * HD;
+  float* Kb = a.Kc + ((long long)rb * H + h) * Lmax * HD;
+  float* Vb = a.Vc + ((long long)rb * H + h) * Lmax * HD;
   // shared prefix (sample_n copies of ONE condition, shapeformer.py:222-260): keys / values of positions < shared_len[0] were
   // written once, by row 0's prefill, and every row reads them from row 0's cache (one HBM read, L2 / Infinity-Cache hits
   // for the other rows); a row's own cache holds its tail only
@@ -847,6 +878,10 @@ struct SampleArgs {
   // The decode attention is handed alen in place of len and streams nothing for an ended row; this kernel writes the forced token
   // without reading the logits.  skip_ended == 0: alen only follows len.
   int* alen; int skip_ended;
+  // packed chain (sfmi_gpt_sample_rows_f32), or null: row b's logits and residual sit at slot slot_of[b] (< 0: the row has ended and
+  // holds no slot); the stage-1 tail writes the next step's embedding to stage (B x D, row-major), from where compact_rows_kernel
+  // moves it to the row's slot of the next step.  Everything that persists stays indexed by row.
+  const int* slot_of; float* stage;
 };
 
 #define SMP_MAXC 512
@@ -871,7 +906,9 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   int* cidx = big ? reinterpret_cast<int*>(dyn_lds + SMP_BIG) : cidx_s;
   float* cexp = big ? dyn_lds + 2 * SMP_BIG : cexp_s;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (a.alen && a.skip_ended && a.alen[b] < 0) {
+  // (the map was built from alen at the head of the step, and alen[b] changes only at the end of this row's own stage-1 workgroup)
+  const int lb = a.slot_of ? a.slot_of[b] : b;
+  if (a.slot_of ? lb < 0 : (a.alen && a.skip_ended && a.alen[b] < 0)) {
     // ended row (uniform per workgroup): the forced token and its log-probability of +0.0f; no logits are read, nothing is sorted
     const int L = a.len[b], j = L - a.Lc[b] - a.step_offset;
     if (tid == 0) {
@@ -880,8 +917,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       if (a.advance) a.len[b] = L + 1;
     }
     // the row's residual is no longer refreshed by the embedding tail below, and the block GEMMs keep adding to it: reset it once
-    // per step so that it stays finite however long the other rows run
-    if (a.resid && a.tuple_i == 1)
+    // per step so that it stays finite however long the other rows run (a packed chain: the row holds no slot)
+    if (!a.slot_of && a.resid && a.tuple_i == 1)
       for (int qd = tid; qd < a.D / 4; qd += 256)
         *reinterpret_cast<f32x4*>(a.resid + pk_off(b, 4 * qd, a.D)) = f32x4{0.f, 0.f, 0.f, 0.f};
     return;
@@ -896,7 +933,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
 #pragma unroll
   for (int r = 0; r < 17; ++r) {
     const int v = tid + 256 * r;
-    xr[r] = v < a.V ? a.part[(long long)b * a.ldv + v] : 0.f;
+    xr[r] = v < a.V ? a.part[(long long)lb * a.ldv + v] : 0.f;
   }
   if (staged)
     for (int i = tid; i < a.Lmax; i += 256) spos[i] = row[2 * i];
@@ -923,7 +960,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const int v = tid + 256 * r;
     if (v >= a.V) continue;
     float x = xr[r];
-    for (int s = 1; s < a.S; ++s) x += a.part[((long long)s * a.M + b) * a.ldv + v];
+    for (int s = 1; s < a.S; ++s) x += a.part[((long long)s * a.M + lb) * a.ldv + v];
     if (a.tuple_i == 1) {
       if (cur_pos == a.end0) x = (v == a.end1) ? 1.0f : -INFINITY;
     } else {
@@ -1126,7 +1163,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     if (a.tuple_i == 0) {
       const f32x4* e0 = reinterpret_cast<const f32x4*>(a.E0 + (long long)choice * a.D);
       for (int qd = tid; qd < nq; qd += 256) {
-        f32x4* rr = reinterpret_cast<f32x4*>(a.resid + pk_off(b, 4 * qd, a.D));
+        f32x4* rr = reinterpret_cast<f32x4*>(a.resid + pk_off(lb, 4 * qd, a.D));
         *rr = *rr + e0[qd];
       }
     } else {
@@ -1143,7 +1180,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       const f32x4* ex = reinterpret_cast<const f32x4*>(a.Ex + (long long)ext * a.D);
       const f32x4* pe = reinterpret_cast<const f32x4*>(a.pos_emb + (long long)(t - lc) * a.D);
       for (int qd = tid; qd < nq; qd += 256)
-        *reinterpret_cast<f32x4*>(a.resid + pk_off(b, 4 * qd, a.D)) = ((e0[qd] + e1[qd]) + ex[qd]) + pe[qd];
+        *reinterpret_cast<f32x4*>(a.stage ? a.stage + (long long)b * a.D + 4 * qd : a.resid + pk_off(b, 4 * qd, a.D)) = ((e0[qd] + e1[qd]) + ex[qd]) + pe[qd];
     }
   }
 }
@@ -1153,7 +1190,7 @@ __global__ __launch_bounds__(256) void embed_packed_kernel(const float* __restri
                                                            const float* __restrict__ Ex, const float* __restrict__ pos_emb,
                                                            const float* __restrict__ cond_pos_emb, const int* __restrict__ seq,
                                                            const int* __restrict__ len, const int* __restrict__ Lc,
-                                                           float* __restrict__ resid, int D, int Lmax, int end0) {
+                                                           float* __restrict__ resid, int D, int Lmax, int end0, int row_major) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int t = len[b] - 1, lc = Lc[b];
   const int* row = seq + (long long)b * Lmax * 2;
@@ -1171,7 +1208,40 @@ __global__ __launch_bounds__(256) void embed_packed_kernel(const float* __restri
   const f32x4* ex = reinterpret_cast<const f32x4*>(Ex + (long long)ext * D);
   const f32x4* pe = reinterpret_cast<const f32x4*>(t < lc ? cond_pos_emb + (long long)t * D : pos_emb + (long long)(t - lc) * D);
   for (int qd = tid; qd < D / 4; qd += 256)
-    *reinterpret_cast<f32x4*>(resid + pk_off(b, 4 * qd, D)) = ((e0[qd] + e1[qd]) + ex[qd]) + pe[qd];
+    *reinterpret_cast<f32x4*>(row_major ? resid + (long long)b * D + 4 * qd : resid + pk_off(b, 4 * qd, D)) = ((e0[qd] + e1[qd]) + ex[qd]) + pe[qd];
+}
+
+// Head of a packed chain's decode step: live rows (alen >= 0) take the slots 0 .. nlive-1 in ascending row order, ended rows the
+// slots behind them, ascending as well (a stable partition, so every slot below B holds exactly one row).  One workgroup per row
+// (B <= 256): it counts the live rows below its own from alen - stable in this launch: alen changes only in the stage-1 sampler -
+// writes its own map entries (no workgroup reads what another one writes) and moves its row's step embedding from the row-major
+// staging buffer into the fragment-packed residual at its slot; an ended row's slot is zeroed, so the rows that share a tile with
+// live ones stay finite.  slot_len is alen by slot: the decode attention's length word.
+__global__ __launch_bounds__(256) void compact_rows_kernel(const int* __restrict__ alen, int* __restrict__ slot_of, int* __restrict__ row_of,
+                                                           int* __restrict__ nlive, int* __restrict__ slot_len,
+                                                           const float* __restrict__ stage, float* __restrict__ resid, int B, int Bpad, int D) {
+  __shared__ int s_all[4], s_below[4], s_mine;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int al = tid < B ? alen[tid] : -1;
+  const unsigned long long m_all = __ballot(al >= 0), m_below = __ballot(al >= 0 && tid < b);
+  if (lane == 0) { s_all[wave] = __popcll(m_all); s_below[wave] = __popcll(m_below); }
+  if (tid == b) s_mine = al;
+  __syncthreads();
+  const int total = (s_all[0] + s_all[1]) + (s_all[2] + s_all[3]), below = (s_below[0] + s_below[1]) + (s_below[2] + s_below[3]);
+  const int mine = s_mine;
+  const int slot = mine >= 0 ? below : total + (b - below);
+  if (tid == 0) {
+    slot_of[b] = mine >= 0 ? slot : -1;
+    row_of[slot] = b;
+    slot_len[slot] = mine >= 0 ? mine : -1;
+    if (b == 0) *nlive = total;
+  }
+  if (b == 0 && B + tid < Bpad) { row_of[B + tid] = -1; slot_len[B + tid] = -1; }      // padding slots of the last tile hold no row
+  for (int qd = tid; qd < D / 4; qd += 256) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (mine >= 0) v = *reinterpret_cast<const f32x4*>(stage + (long long)b * D + 4 * qd);
+    *reinterpret_cast<f32x4*>(resid + pk_off(slot, 4 * qd, D)) = v;
+  }
 }
 
 // per-row cross entropy: loss[m] = logsumexp(logits[m,:V]) - logits[m, target[m]]   (F.cross_entropy, shapeformer.py:136)
@@ -1241,8 +1311,8 @@ __global__ void set_len_kernel(int* len, const int* src, int B, int delta) {
 template <class P>
 static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out, int M,
                               int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt, int* pblk,
-                              unsigned long long* prof, void* stream, const int* alen = nullptr) {
-  if (prof && alen) return SFMI_EINVAL;      // a timed launch counts every workgroup at its end: no early exits
+                              unsigned long long* prof, void* stream, const int* alen = nullptr, const int* nlive = nullptr, int partial = 0) {
+  if (prof && (alen || nlive)) return SFMI_EINVAL;      // a timed launch counts every workgroup at its end: no early exits
   if (!x || !Wp16 || !out || M <= 0 || M > 192 || S <= 0 || K % S || (ln && !c1)) return SFMI_EINVAL;   // larger batches: several chains (gpt.py)
   if (out_packed && N % 16) return SFMI_EINVAL;
   if (!out_packed && (ldo < N || ldo % 4)) return SFMI_EINVAL;   // row-major rows are written as float4s up to round_up(N, 4)
@@ -1264,6 +1334,7 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
   DGemmArgs a;
   a.x = x; a.Wp = Wp16; a.c1 = c1; a.c2 = c2; a.resid = resid; a.out = out; a.M = M; a.N = N; a.K = K; a.ldo = ldo; a.ln = ln; a.act = act;
   a.out_packed = out_packed; a.slab = slab; a.cnt = cnt; a.pblk = pblk; a.prof = prof; a.prio = g_tune.dgemm_prio; a.alen = alen;
+  a.nlive = nlive; a.partial = partial;
   hipStream_t st = (hipStream_t)stream;
   if ((g_tune.dgemm_nt2 == 2 || (g_tune.dgemm_nt2 == 1 && tiles % 3 == 0)) && NWv == 8 && (kslice / 8 / 16) % 2 == 0 && tiles >= 3) {
     // two n-tiles per wave, row groups of <= 3 row tiles, batches of two k16-steps: 5 operand loads per 24 MFMAs (7 in the one-tile
@@ -1364,6 +1435,14 @@ int sfmi_decode_gemm_live_f32(const float* x, const float* Wp16, const float* c1
                               int* cnt, const int* alen, void* stream) {
   return decode_gemm_launch<DgProduct>(x, Wp16, c1, c2, resid, out, M, N, K, ldo, ln, act, out_packed, S, slab, cnt, nullptr, nullptr, stream, alen);
 }
+// the GEMM of a chain whose live rows are packed into slots 0 .. *nlive - 1 (sfmi_gpt_compact_rows_f32): see DGemmArgs::nlive
+int sfmi_decode_gemm_rows_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid,
+                              float* out, int M, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab,
+                              int* cnt, const int* nlive, int partial, void* stream) {
+  if (!nlive) return SFMI_EINVAL;
+  return decode_gemm_launch<DgProduct>(x, Wp16, c1, c2, resid, out, M, N, K, ldo, ln, act, out_packed, S, slab, cnt, nullptr, nullptr, stream,
+                                       nullptr, nlive, partial ? 1 : 0);
+}
 
 // replaces get_embeddings (mingpt.py:256-286) + the AR_N extra index (representers.py:188-196,432-442)
 // (+ LayerNorm ln1 of the first block).  P == 0: one row per sequence at t = len[b]-1; P > 0: prefill rows (b,t<P).
@@ -1402,13 +1481,13 @@ int sfmi_gpt_rowprep_f32(const float* resid_in, const float* part, const float* 
 // replaces CausalSelfAttention.forward for ONE new position per row with a KV cache (mingpt.py:73-91).
 // sem (optional, 3 device ints zeroed by the caller while no launch is in flight) + blk (1 device int, zero; one per chain):
 // the launch passes the attention turnstile first (at most `lanes` gated launches stream at a time, FIFO).
-int sfmi_gpt_attn_decode_gated_f32(const float* qkv_part, float* Kc, float* Vc, const int* len, float* y, int B, int D, int H,
-                                   int Lmax, const int* shared_len, int* sem, int* blk, int lanes, unsigned long long* prof, void* stream) {
+static int attn_decode_launch(const float* qkv_part, float* Kc, float* Vc, const int* len, const int* row_of, float* y, int B, int D, int H,
+                              int Lmax, const int* shared_len, int* sem, int* blk, int lanes, unsigned long long* prof, void* stream) {
   if (!qkv_part || !Kc || !Vc || !len || !y || D % H || (D / H) > 64 || (D / H) % 4 || Lmax > 1024) return SFMI_EINVAL;
   if (sem && (!blk || lanes <= 0)) return SFMI_EINVAL;
   if (prof && !blk) return SFMI_EINVAL;
   AttnArgs a;
-  a.qkv = qkv_part; a.Kc = Kc; a.Vc = Vc; a.len = len; a.y = y; a.shared_len = shared_len;
+  a.qkv = qkv_part; a.Kc = Kc; a.Vc = Vc; a.len = len; a.y = y; a.shared_len = shared_len; a.row_of = row_of;
   a.B = B; a.H = H; a.D = D; a.Lmax = Lmax; a.HD = D / H; a.scale = 1.0f / sqrtf((float)a.HD);
   a.sem = sem; a.blk = blk; a.prof = prof;
   const int nitems = B * H;
@@ -1435,6 +1514,18 @@ int sfmi_gpt_attn_decode_gated_f32(const float* qkv_part, float* Kc, float* Vc, 
 #undef AT
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
+}
+int sfmi_gpt_attn_decode_gated_f32(const float* qkv_part, float* Kc, float* Vc, const int* len, float* y, int B, int D, int H,
+                                   int Lmax, const int* shared_len, int* sem, int* blk, int lanes, unsigned long long* prof, void* stream) {
+  return attn_decode_launch(qkv_part, Kc, Vc, len, nullptr, y, B, D, H, Lmax, shared_len, sem, blk, lanes, prof, stream);
+}
+// the same for a packed chain: item (s, head) reads qkv / slot_len and writes y at SLOT s, and walks the caches of row row_of[s]
+// (slot_len[s] < 0: no live row in the slot).  The shared prefix is read from cache row 0, whichever slot row 0 holds.
+int sfmi_gpt_attn_decode_rows_f32(const float* qkv_part, float* Kc, float* Vc, const int* slot_len, const int* row_of, float* y, int B,
+                                  int D, int H, int Lmax, const int* shared_len, int* sem, int* blk, int lanes, unsigned long long* prof,
+                                  void* stream) {
+  if (!row_of) return SFMI_EINVAL;
+  return attn_decode_launch(qkv_part, Kc, Vc, slot_len, row_of, y, B, D, H, Lmax, shared_len, sem, blk, lanes, prof, stream);
 }
 int sfmi_gpt_attn_decode_f32(const float* qkv_part, const float* bqkv, float* Kc, float* Vc, const int* len, float* y,
                              int S, int B, int D, int H, int Lmax, const int* shared_len, void* stream) {
@@ -1476,12 +1567,12 @@ int sfmi_gpt_attn_prefill_lse_sd_f32(const float* qkv, float* Kc, float* Vc, con
 // replaces sampling_masker + sample_logits for one tuple element (representers.py:120-155, common.py:260-299,
 // shapeformer.py:91-106); advance != 0 also appends the token (len += 1).  Optional fused tail (resid != NULL):
 // tuple 0: resid[b] += E0[pos'] ; tuple 1: resid[b] = embedding of the completed token (next step's input).
-int sfmi_gpt_sample_live_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
-                             float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
-                             int S, int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
-                             float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
-                             unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
-                             int* alen, int skip_ended, void* stream) {
+static int sample_launch(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
+                         float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
+                         int S, int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
+                         float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
+                         unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
+                         int* alen, int skip_ended, const int* slot_of, float* stage, void* stream) {
   if (!part || !seq || !len || !Lc || V > 4352 || temperature <= 0.f || rows_total < B + row_offset || step_offset < 0) return SFMI_EINVAL;
   if (resid && (!E0 || (tuple_i == 1 && (!E1 || !Ex || !pos_emb)) || D % 4)) return SFMI_EINVAL;
   SampleArgs a;
@@ -1494,10 +1585,34 @@ int sfmi_gpt_sample_live_f32(const float* part, int* seq, int* len, const int* L
   // ended rows are skipped only where their tokens are forced and nobody looks at their logits: mask_invalid on, no logits history,
   // no teacher forcing
   a.alen = alen; a.skip_ended = (alen && skip_ended && mask_invalid && !hist && !force) ? 1 : 0;
+  a.slot_of = slot_of; a.stage = stage;
+  if (slot_of && (!a.skip_ended || !resid || !stage)) return SFMI_EINVAL;      // rows are packed only where ended rows are skipped
   const size_t dyn = (top_k <= 0 || top_k > SMP_MAXC) ? (size_t)SMP_BIG * 12 : 0;
   hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(256), dyn, (hipStream_t)stream, a);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
+}
+int sfmi_gpt_sample_live_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
+                             float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
+                             int S, int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,
+                             float temperature, int greedy_row0, int mask_invalid, int mask_completion, int max_steps,
+                             unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
+                             int* alen, int skip_ended, void* stream) {
+  return sample_launch(part, seq, len, Lc, logp, hist, force, resid, E0, E1, Ex, pos_emb, D, S, B, V, ldv, Lmax, tuple_i, end0, end1, top_k,
+                       top_p, temperature, greedy_row0, mask_invalid, mask_completion, max_steps, seed, seed_dev, advance, row_offset,
+                       rows_total, step_offset, alen, skip_ended, nullptr, nullptr, stream);
+}
+// the sampler of a packed chain (SampleArgs::slot_of): one workgroup per ROW as before; logits (and, stage 0, the residual) at the row's
+// slot, the stage-1 tail into `stage`.  Uniforms, the greedy row, seq, len, alen and logp stay keyed by row.
+int sfmi_gpt_sample_rows_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* resid, float* stage,
+                             const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D, int S, int B, int V, int ldv,
+                             int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p, float temperature, int greedy_row0,
+                             int mask_completion, int max_steps, unsigned seed, const unsigned* seed_dev, int advance, int row_offset,
+                             int rows_total, int step_offset, int* alen, const int* slot_of, void* stream) {
+  if (!slot_of || !alen) return SFMI_EINVAL;
+  return sample_launch(part, seq, len, Lc, logp, nullptr, nullptr, resid, E0, E1, Ex, pos_emb, D, S, B, V, ldv, Lmax, tuple_i, end0, end1,
+                       top_k, top_p, temperature, greedy_row0, 1, mask_completion, max_steps, seed, seed_dev, advance, row_offset,
+                       rows_total, step_offset, alen, 1, slot_of, stage, stream);
 }
 int sfmi_gpt_sample_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
                         float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D,
@@ -1531,7 +1646,27 @@ int sfmi_gpt_embed_packed_f32(const float* E0, const float* E1, const float* Ex,
                               void* stream) {
   if (!E0 || !E1 || !Ex || !pos_emb || !cond_pos_emb || !seq || !len || !Lc || !resid || D % 16) return SFMI_EINVAL;
   hipLaunchKernelGGL(embed_packed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, E0, E1, Ex, pos_emb, cond_pos_emb, seq, len, Lc,
-                     resid, D, Lmax, end0);
+                     resid, D, Lmax, end0, 0);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+// the same embedding into the row-major staging buffer (B x D) of a packed chain (sfmi_gpt_compact_rows_f32 moves it to the slots)
+int sfmi_gpt_embed_rows_f32(const float* E0, const float* E1, const float* Ex, const float* pos_emb, const float* cond_pos_emb,
+                            const int* seq, const int* len, const int* Lc, float* stage, int B, int D, int Lmax, int end0, void* stream) {
+  if (!E0 || !E1 || !Ex || !pos_emb || !cond_pos_emb || !seq || !len || !Lc || !stage || D % 16) return SFMI_EINVAL;
+  hipLaunchKernelGGL(embed_packed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, E0, E1, Ex, pos_emb, cond_pos_emb, seq, len, Lc,
+                     stage, D, Lmax, end0, 1);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+// slot map of a packed chain + the step's embeddings into the residual at their slots (compact_rows_kernel).  slot_of (B), row_of and
+// slot_len (Bpad = sfmi_decode_gemm_padded_rows(B)), nlive (1); resid holds Bpad rows.
+int sfmi_gpt_compact_rows_f32(const int* alen, int* slot_of, int* row_of, int* nlive, int* slot_len, const float* stage, float* resid,
+                              int B, int Bpad, int D, void* stream) {
+  if (!alen || !slot_of || !row_of || !nlive || !slot_len || !stage || !resid || B <= 0 || B > 256 || Bpad < B || Bpad - B > 256 || D % 16)
+    return SFMI_EINVAL;
+  hipLaunchKernelGGL(compact_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, alen, slot_of, row_of, nlive, slot_len, stage, resid,
+                     B, Bpad, D);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

@@ -213,6 +213,10 @@ class CondTupleGPT:
                   alen=torch.zeros(B, device=dev, dtype=torch.int32),    # per-row attention length: len while the row is live, -1 once it has ended (SKIP_ENDED)
                   resid=torch.zeros(Bp, D, device=dev), qkv=torch.zeros(Bp, 3 * D, device=dev), y=torch.zeros(Bp, D, device=dev),
                   h=torch.zeros(Bp, 4 * D, device=dev), logit=f(B, self.Vpad),
+                  # packed chain (COMPACT_LIVE, csrc/gpt.hip compact_rows_kernel): the step's embeddings by row, the slot map, the live count
+                  emb=torch.zeros(B, D, device=dev), slot_of=torch.zeros(B, device=dev, dtype=torch.int32),
+                  row_of=torch.zeros(Bp, device=dev, dtype=torch.int32), slot_len=torch.zeros(Bp, device=dev, dtype=torch.int32),
+                  nlive=torch.zeros(1, device=dev, dtype=torch.int32),
                   slab=f(L.lib().sfmi_decode_gemm_slab_floats(Bp, 4 * D, 4)), cnt=torch.zeros(Bp // 16 * (max(4 * D, self.Vpad) // 16 + 1), device=dev, dtype=torch.int32),
                   Kc=f(len(self.layers), B, self.Lmax + 1, D), Vc=f(len(self.layers), B, self.Lmax + 1, D),
                   logp=torch.zeros(B, max_steps, 2, device=dev, dtype=torch.float32),
@@ -250,13 +254,18 @@ class CondTupleGPT:
         return out
 
     # ------------------------------------------------------------------ C-ABI wrappers
-    def _dgemm(self, x, wp, c1, c2, resid, out, M, N, K, ldo, ln, act, packed=1, S=1, st=None, prof=False, alen=None):
+    def _dgemm(self, x, wp, c1, c2, resid, out, M, N, K, ldo, ln, act, packed=1, S=1, st=None, prof=False, alen=None, nlive=None, partial=1):
         """alen: the chain's per-row attention length (st["alen"]): row groups without a live row do no work (not with prof: a timed
-        launch counts every workgroup at its end)."""
+        launch counts every workgroup at its end).  nlive: the live-row count of a packed chain (st["nlive"]): only the row tiles that
+        hold a live slot are run (partial=0: whole row groups, as with alen)."""
         st = st or self._state
         while S > 1 and (K // S) % 128:
             S //= 2
         slab, cnt = (L.ptr(st["slab"]), L.ptr(st["cnt"])) if S > 1 else (None, None)
+        if nlive is not None and not prof:
+            L.check(L.lib().sfmi_decode_gemm_rows_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
+                                                      ln, act, packed, S, slab, cnt, L.ptr(nlive), int(partial), L.stream_ptr()), "sfmi_decode_gemm_rows_f32")
+            return
         if alen is not None and not prof:
             L.check(L.lib().sfmi_decode_gemm_live_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
                                                       ln, act, packed, S, slab, cnt, L.ptr(alen), L.stream_ptr()), "sfmi_decode_gemm_live_f32")
@@ -467,6 +476,13 @@ class CondTupleGPT:
     # Armed only with mask_invalid, without logits history, teacher forcing or a timing ablation (those measure every row's stream).
     SKIP_ENDED = True
     SKIP_ENDED_GEMM = True
+    # Ended rows are spread evenly over the 16-row tiles, so the group exit above acts only late in a run.  COMPACT_LIVE (with both
+    # knobs above, and armed where they are): at the head of every step the chain's live rows are packed into slots 0 .. nlive-1 of the
+    # activation buffers (resid, qkv, y, h, logit), in ascending row order, and the decode GEMMs run only the row tiles that hold a
+    # live slot (COMPACT_LIVE_TILES False: whole row groups).  seq, len, alen, Lc, logp and the KV caches stay indexed by row; the
+    # launch forms are chosen from the chain's rows as before, so every row's arithmetic - and seq / len / logp - is bit-identical.
+    COMPACT_LIVE = True
+    COMPACT_LIVE_TILES = True
 
     def decode_step(self, st, B, sp):
         """Position t = len[b]-1 of every row through both stages; st["resid"] must hold its embedding on entry
@@ -485,25 +501,49 @@ class CondTupleGPT:
         # ended rows: the attention gets alen in its `len` slot (no new kernel argument), the GEMMs get it to drop all-ended row groups
         alen_a = st["alen"] if armed else st["len"]
         alen_g = st["alen"] if armed >= 2 else None
+        compact = int(sp.get("compact_live", 0))      # 0 = rows in place, 1 = packed + GEMM group exit, 2 = packed + live row tiles only
+        gk = dict(alen=alen_g)
+        if compact:
+            gk = dict(nlive=st["nlive"], partial=int(compact >= 2))
+            L.check(lib.sfmi_gpt_compact_rows_f32(L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.ptr(st["row_of"]), L.ptr(st["nlive"]),
+                                                  L.ptr(st["slot_len"]), L.ptr(st["emb"]), L.ptr(r), B, r.shape[0], D, L.stream_ptr()),
+                    "sfmi_gpt_compact_rows_f32")
         for li, ly in enumerate(self.layers):
             stage_end = li + 1 == len(self.layers) or self.layers[li + 1].stage != ly.stage
             if "gemm" not in skip:
-                self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg, alen=alen_g)
-            if "attn" not in skip:
+                self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg, **gk)
+            if "attn" not in skip and compact:
+                L.check(lib.sfmi_gpt_attn_decode_rows_f32(L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]),
+                                                          L.ptr(st["slot_len"]), L.ptr(st["row_of"]), L.ptr(st["y"]), B, D, self.H, self.Lmax + 1,
+                                                          L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
+                                                          L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
+                                                          L.ptr(st["prof"]) if pa else None, L.stream_ptr()), "sfmi_gpt_attn_decode_rows_f32")
+            elif "attn" not in skip:
                 L.check(lib.sfmi_gpt_attn_decode_gated_f32(L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]),
                                                            L.ptr(alen_a), L.ptr(st["y"]), B, D, self.H, self.Lmax + 1,
                                                            L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
                                                            L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
                                                            L.ptr(st["prof"]) if pa else None, L.stream_ptr()), "sfmi_gpt_attn_decode_gated_f32")
             if "gemm" not in skip:
-                self._dgemm(st["y"], ly.pproj, None, ly.bproj, r, r, B, D, D, D, 0, 0, S=Sproj, st=st, prof=pg, alen=alen_g)
-                self._dgemm(r, ly.pfc1, ly.c1fc1, ly.c2fc1, None, st["h"], B, 4 * D, D, 4 * D, 1, 1, S=Sfc1, st=st, prof=pg, alen=alen_g)
-                self._dgemm(st["h"], ly.pfc2, None, ly.bfc2, r, r, B, D, 4 * D, D, 0, 0, S=Sfc2, st=st, prof=pg, alen=alen_g)
+                self._dgemm(st["y"], ly.pproj, None, ly.bproj, r, r, B, D, D, D, 0, 0, S=Sproj, st=st, prof=pg, **gk)
+                self._dgemm(r, ly.pfc1, ly.c1fc1, ly.c2fc1, None, st["h"], B, 4 * D, D, 4 * D, 1, 1, S=Sfc1, st=st, prof=pg, **gk)
+                self._dgemm(st["h"], ly.pfc2, None, ly.bfc2, r, r, B, D, 4 * D, D, 0, 0, S=Sfc2, st=st, prof=pg, **gk)
             if stage_end:
                 s = ly.stage
                 hp, hc1, hc2 = self.head_f[s]
-                self._dgemm(r, hp, hc1, hc2, None, st["logit"], B, self.V, D, self.Vpad, 1, 0, packed=0, S=Shead, st=st, alen=alen_g)
+                self._dgemm(r, hp, hc1, hc2, None, st["logit"], B, self.V, D, self.Vpad, 1, 0, packed=0, S=Shead, st=st, **gk)
                 hist = sp["hist"][s] if sp.get("hist") is not None else None
+                if compact:
+                    L.check(lib.sfmi_gpt_sample_rows_f32(L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
+                                                         L.ptr(st["logp"]), L.ptr(r), L.ptr(st["emb"]),
+                                                         L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), D,
+                                                         1, B, self.V, self.Vpad, self.Lmax + 1,
+                                                         s, self.end[0], self.end[1], sp["top_k"], sp["top_p"], sp["temperature"],
+                                                         int(sp["best_in_first"]), int(sp["mask_invalid_completion"]), sp["max_steps"],
+                                                         sp["seed"], L.ptr(st.get("seed")), int(s == 1),
+                                                         sp.get("row_offset", 0), sp.get("rows_total", B), int(sp.get("step_offset", 0)),
+                                                         L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.stream_ptr()), "sfmi_gpt_sample_rows_f32")
+                    continue
                 L.check(lib.sfmi_gpt_sample_live_f32(L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
                                                      L.ptr(st["logp"]), L.ptr(hist), L.ptr(sp.get("force")),
                                                      L.ptr(r), L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), D,
@@ -543,6 +583,13 @@ class CondTupleGPT:
             st["len"].add_(Lz)
             shared_prefix = False
         st["alen"].copy_(st["len"])
+        # the identity map (a packed chain rebuilds it at the head of every step)
+        st["slot_of"].copy_(torch.arange(B, device=self.dev, dtype=torch.int32))
+        st["row_of"].fill_(-1)
+        st["row_of"][:B] = st["slot_of"]
+        st["slot_len"].fill_(-1)
+        st["slot_len"][:B] = st["len"]
+        st["nlive"].fill_(B)
         st["logp"].zero_()
         st["seed"].copy_(torch.from_numpy(np.array([sp_kw["seed"]], np.uint32).view(np.int32)))
         hist = None
@@ -555,6 +602,7 @@ class CondTupleGPT:
         # are forced and nobody looks at their logits; a launch-shape choice like the others: part of the graph-cache key through sp
         sp["skip_ended"] = (2 if self.SKIP_ENDED_GEMM else 1) if (self.SKIP_ENDED and sp_kw["mask_invalid"] and not return_logits
                                                                   and force_tokens is None and not self._ablate) else 0
+        sp["compact_live"] = (2 if self.COMPACT_LIVE_TILES else 1) if (self.COMPACT_LIVE and sp["skip_ended"] >= 2) else 0
         if force_tokens is not None:   # (B,max_steps,2) teacher forcing for stepwise parity tests
             ft = torch.zeros(B, max_steps, 2, dtype=torch.int32)
             ft[:, :force_tokens.shape[1]] = torch.as_tensor(force_tokens).to(torch.int32)
@@ -582,11 +630,18 @@ class CondTupleGPT:
             st["rowoff"] = torch.tensor([0] + list(np.cumsum(nrow)), dtype=torch.int32).to(self.dev)
             if P > 0 and st["M_packed"] > 0:
                 self.prefill(st, B, P)
-        # embedding of the last condition token (step-0 input) into the fragment-packed residual buffer
-        L.check(L.lib().sfmi_gpt_embed_packed_f32(L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb),
-                                                  L.ptr(self.cond_pos_emb), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
-                                                  L.ptr(st["resid"]), B, self.D, self.Lmax + 1, self.end[0], L.stream_ptr()),
-                "sfmi_gpt_embed_packed_f32")
+        # embedding of the last condition token (step-0 input) into the fragment-packed residual buffer (a packed chain: into the
+        # row-major staging buffer, from where the head of the step moves it to the rows' slots)
+        if sp["compact_live"]:
+            L.check(L.lib().sfmi_gpt_embed_rows_f32(L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb),
+                                                    L.ptr(self.cond_pos_emb), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
+                                                    L.ptr(st["emb"]), B, self.D, self.Lmax + 1, self.end[0], L.stream_ptr()),
+                    "sfmi_gpt_embed_rows_f32")
+        else:
+            L.check(L.lib().sfmi_gpt_embed_packed_f32(L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb),
+                                                      L.ptr(self.cond_pos_emb), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
+                                                      L.ptr(st["resid"]), B, self.D, self.Lmax + 1, self.end[0], L.stream_ptr()),
+                    "sfmi_gpt_embed_packed_f32")
         graph = None
         if use_graph and steps > 1:
             gkey = (B, tuple(sorted((k, v) for k, v in sp.items() if k not in ("hist", "force", "seed"))), return_logits,
@@ -596,7 +651,7 @@ class CondTupleGPT:
             if cached is None or cached[0] != gkey or return_logits:
                 side = torch.cuda.Stream(device=self.dev)
                 side.wait_stream(torch.cuda.current_stream())
-                saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid")}
+                saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid", "emb")}
                 with torch.cuda.stream(side):
                     self.decode_step(st, B, sp)      # warm-up outside capture
                 torch.cuda.current_stream().wait_stream(side)
