@@ -246,7 +246,13 @@ int sfmi_gpt_attn_decode_rows_f32(const float* qkv_packed, float* Kc, float* Vc,
 /* one tuple element of one sampling step per row: sampling_masker (representers.py:120-155) + filter_sampling_logits /
  * sample_logits (models/common.py:260-299: temperature, top-k with ties, top-p) + inverse-CDF draw from counter-hash uniforms
  * indexed (step, tuple, row_offset + b) + best_in_first greedy row + log-prob + optional masked-logit history; writes the
- * token into seq, and the next GEMM input (tok_embs add / next position's embedding) into `resid` */
+ * token into seq, and the next GEMM input (tok_embs add / next position's embedding) into `resid`.
+ * 0 < top_k <= 512 with more than 512 candidates (ties at the k-th value): the first 512 in rank order (value descending, index
+ * ascending) are kept.  logp / hist / force are touched only at steps 0 <= j < max_steps.
+ * Accepted (anything else: SFMI_EINVAL, nothing launched; the _live and _rows forms alike): part, seq, len, Lc non-NULL; B >= 1;
+ * 1 <= V <= 4352; ldv >= V; S >= 1; Lmax >= 1; tuple_i in {0, 1}; temperature > 0; row_offset >= 0; rows_total >= row_offset + B;
+ * step_offset >= 0; max_steps >= 1 when logp, hist or force is given; with resid: E0 (tuple_i == 1: E1, Ex and pos_emb too) non-NULL
+ * and D a positive multiple of 16 (the residual is fragment-packed); _rows: slot_of, alen, resid and stage non-NULL. */
 int sfmi_gpt_sample_f32(const float* part, int* seq, int* len, const int* Lc, float* logp, float* hist, const int* force,
                         float* resid, const float* E0, const float* E1, const float* Ex, const float* pos_emb, int D, int S,
                         int B, int V, int ldv, int Lmax, int tuple_i, int end0, int end1, int top_k, float top_p,

@@ -847,7 +847,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const float* __r
 // fused sampler: one workgroup per row
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned fkey_u(float f) {
-  unsigned u = __float_as_uint(f);
+  unsigned u = __float_as_uint(f + 0.0f);   // -0.0f + 0.0f = +0.0f: the keys order as the floats compare (common.py:263 keeps l >= kth)
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -913,7 +913,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const int L = a.len[b], j = L - a.Lc[b] - a.step_offset;
     if (tid == 0) {
       a.seq[((long long)b * a.Lmax + L) * 2 + a.tuple_i] = a.tuple_i ? a.end1 : a.end0;
-      if (a.logp && j < a.max_steps) a.logp[((long long)b * a.max_steps + j) * 2 + a.tuple_i] = 0.0f;
+      if (a.logp && j >= 0 && j < a.max_steps) a.logp[((long long)b * a.max_steps + j) * 2 + a.tuple_i] = 0.0f;
       if (a.advance) a.len[b] = L + 1;
     }
     // the row's residual is no longer refreshed by the embedding tail below, and the block GEMMs keep adding to it: reset it once
@@ -941,6 +941,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   __syncthreads();
   auto pos_at = [&](int i) { return staged ? spos[i] : row[2 * i]; };
   const int j = L - lc - a.step_offset;  // step index of this row (the reference's loop counter, shapeformer.py:71)
+  const bool j_in = j >= 0 && j < a.max_steps;   // the row owns a slot of logp / hist / force only at these steps
   const int last_pos = pos_at(L - 1);
   const int cur_pos = pos_at(L);  // valid for tuple 1 (pos just sampled)
   // this draw's uniform (counter hash of (step, tuple, global row)): formed here so that the seed's load is off the serial tail
@@ -969,7 +970,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     }
     lg[v] = x;
     if (a.mask_out) a.mask_out[(long long)b * a.V + v] = x;
-    if (a.hist) a.hist[((long long)b * a.max_steps + j) * a.V + v] = x;
+    if (a.hist && j_in) a.hist[((long long)b * a.max_steps + j) * a.V + v] = x;
     if (x > lmax) { lmax = x; amax = v; }
   }
   if (a.mask_out) return;   // mask-only mode (uniform per launch)
@@ -1040,6 +1041,40 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       }
     }
     __syncthreads();
+    if (!big && s_cnt > SMP_MAXC) {   // uniform per workgroup
+      // Ties at the k-th key overflow the 512-entry buffer, and which lanes lost the race above differs from launch to launch.  Keep
+      // the first 512 candidates in rank order (value descending, index ascending) instead: every candidate above the k-th key -
+      // fewer than k <= 512 of them - and then the ties in ascending index order, placed by a ballot prefix over 256 indices at a
+      // time (sampler section).
+      __syncthreads();                // every thread has read s_cnt
+      if (tid == 0) s_cnt = 0;
+      __syncthreads();
+      for (int v = tid; v < a.V; v += 256) {
+        const float x = lg[v] * invT;
+        if (x > -INFINITY && fkey_u(x) > kth) {
+          const int slot = atomicAdd(&s_cnt, 1);
+          cval[slot] = x; cidx[slot] = v;
+        }
+      }
+      __syncthreads();
+      int base = s_cnt;
+      for (int v0 = 0; v0 < a.V && base < SMP_MAXC; v0 += 256) {      // base is the same in every thread
+        const int v = v0 + tid;
+        const float x = v < a.V ? lg[v] * invT : 0.f;
+        const bool tie = v < a.V && x > -INFINITY && fkey_u(x) == kth;
+        const unsigned long long m = __ballot(tie);
+        if (lane == 0) redi[4 + wave] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += redi[4 + w];
+        const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
+        if (tie && slot < SMP_MAXC) { cval[slot] = x; cidx[slot] = v; }
+        base += (redi[4] + redi[5]) + (redi[6] + redi[7]);
+        __syncthreads();
+      }
+      if (tid == 0) s_cnt = SMP_MAXC;
+      __syncthreads();
+    }
     const int C = min(s_cnt, NSMAX);
     int NS = 2;
     while (NS < C) NS <<= 1;
@@ -1147,10 +1182,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __syncthreads();
     choice = s_choice;
   }
-  if (a.force && j < a.max_steps) choice = a.force[((long long)b * a.max_steps + j) * 2 + a.tuple_i];
+  if (a.force && j_in) choice = a.force[((long long)b * a.max_steps + j) * 2 + a.tuple_i];
   if (tid == 0) {
     a.seq[((long long)b * a.Lmax + L) * 2 + a.tuple_i] = choice;
-    if (a.logp && j < a.max_steps) a.logp[((long long)b * a.max_steps + j) * 2 + a.tuple_i] = lg[choice] - lse;
+    if (a.logp && j_in) a.logp[((long long)b * a.max_steps + j) * 2 + a.tuple_i] = lg[choice] - lse;
     if (a.advance) {
       a.len[b] = L + 1;
       // the token just completed has position end0 and the row's next step index j + 1 is >= 1: the row has ended (SampleArgs::alen)
@@ -1574,7 +1609,10 @@ static int sample_launch(const float* part, int* seq, int* len, const int* Lc, f
                          unsigned seed, const unsigned* seed_dev, int advance, int row_offset, int rows_total, int step_offset,
                          int* alen, int skip_ended, const int* slot_of, float* stage, void* stream) {
   if (!part || !seq || !len || !Lc || V > 4352 || temperature <= 0.f || rows_total < B + row_offset || step_offset < 0) return SFMI_EINVAL;
-  if (resid && (!E0 || (tuple_i == 1 && (!E1 || !Ex || !pos_emb)) || D % 4)) return SFMI_EINVAL;
+  if (B <= 0 || V <= 0 || ldv < V || S < 1 || Lmax <= 0 || (tuple_i != 0 && tuple_i != 1) || row_offset < 0) return SFMI_EINVAL;
+  if ((logp || hist || force) && max_steps <= 0) return SFMI_EINVAL;
+  // the residual is fragment-packed (pk_off: 16-column tiles); the staging buffer is written in float4s
+  if (resid && (!E0 || (tuple_i == 1 && (!E1 || !Ex || !pos_emb)) || D <= 0 || D % 16)) return SFMI_EINVAL;
   SampleArgs a;
   a.part = part; a.seq = seq; a.len = len; a.Lc = Lc; a.logp = logp; a.hist = hist; a.force = force; a.S = S; a.M = B; a.V = V;
   a.ldv = ldv; a.resid = resid; a.E0 = E0; a.E1 = E1; a.Ex = Ex; a.pos_emb = pos_emb; a.D = D;
