@@ -220,6 +220,23 @@ int sfmi_decode_gemm_rows_f32(const float* x, const float* Wp16, const float* c1
                               const int* nlive, int partial, void* stream);
 int sfmi_gpt_embed_rows_f32(const float* E0, const float* E1, const float* Ex, const float* pos_emb, const float* cond_pos_emb,
                             const int* seq, const int* len, const int* Lc, float* stage, int B, int D, int Lmax, int end0, void* stream);
+/* A packed chain's step at a ROW-TILE BUDGET (CondTupleGPT.TILE_BUDGET): the live count never grows, so a value the host read a few
+ * steps ago bounds every later step, and the host picks launches shaped for that many row tiles instead of the chain's rows.
+ * sfmi_decode_gemm_tiles_f32: sfmi_decode_gemm_rows_f32 of a chain of form_rows rows over the row tiles 0 .. tiles-1 of the same packed
+ * buffers, slab and ticket words.  form_rows alone decides what a row's bits depend on (the k-parts per workgroup, by the rule
+ * sfmi_decode_gemm_f32 applies to M = form_rows, and the legality of S); tiles decides the tiles per workgroup, the row groups, the
+ * loads in flight and the grid, so every row < *nlive has the bits of the launch at M = form_rows; rows >= 16 * tiles are not written;
+ * tiles = ceil(form_rows / 16) is that launch.  SFMI_EINVAL: nlive NULL, tiles < 1, 16 * tiles (or the row groups the form pads to)
+ * beyond sfmi_decode_gemm_padded_rows(form_rows), and everything sfmi_decode_gemm_f32 refuses; there is no timed (prof) form.
+ * sfmi_gpt_compact_rows_budget_f32: sfmi_gpt_compact_rows_f32 at the head of such a step; over (1 device int, zeroed by the caller) is
+ * set to 1 - by a plain store, never cleared - when more than 16 * budget rows are live: the step's launches then drop rows, and the
+ * caller must treat its results as invalid.  SFMI_EINVAL: over NULL, budget < 1, 16 * budget > Bpad.
+ * The decode attention of such a step is sfmi_gpt_attn_decode_rows_f32 with B = min(rows, 16 * tiles) slots. */
+int sfmi_decode_gemm_tiles_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out,
+                               int form_rows, int tiles, int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab,
+                               int* cnt, const int* nlive, int partial, void* stream);
+int sfmi_gpt_compact_rows_budget_f32(const int* alen, int* slot_of, int* row_of, int* nlive, int* slot_len, const float* stage,
+                                     float* resid, int B, int Bpad, int D, int budget, int* over, void* stream);
 /* embedding of the token at t = len[b]-1 into the fragment-packed residual buffer (input of the first decode step) */
 int sfmi_gpt_embed_packed_f32(const float* E0, const float* E1, const float* Ex, const float* pos_emb, const float* cond_pos_emb,
                               const int* seq, const int* len, const int* Lc, float* resid, int B, int D, int Lmax, int end0,

@@ -124,6 +124,8 @@ PROTOTYPES = {
     "sfmi_decode_gemm_live_f32": (i32, [c_ptr] * 6 + [i32] * 8 + [c_ptr, c_ptr, c_ptr, c_ptr]),
     "sfmi_decode_gemm_rows_f32": (i32, [c_ptr] * 6 + [i32] * 8 + [c_ptr, c_ptr, c_ptr, i32, c_ptr]),
     "sfmi_gpt_compact_rows_f32": (i32, [c_ptr] * 7 + [i32] * 3 + [c_ptr]),
+    "sfmi_decode_gemm_tiles_f32": (i32, [c_ptr] * 6 + [i32] * 9 + [c_ptr, c_ptr, c_ptr, i32, c_ptr]),
+    "sfmi_gpt_compact_rows_budget_f32": (i32, [c_ptr] * 7 + [i32] * 4 + [c_ptr, c_ptr]),
     "sfmi_gpt_embed_rows_f32": (i32, [c_ptr] * 9 + [i32] * 4 + [c_ptr]),
     "sfmi_gpt_attn_decode_rows_f32": (i32, [c_ptr] * 6 + [i32] * 4 + [c_ptr, c_ptr, c_ptr, i32, c_ptr, c_ptr]),
     "sfmi_gpt_sample_rows_f32": (i32, [c_ptr] * 11 + [i32] * 10 + [C.c_float, C.c_float] + [i32] * 3 + [C.c_uint, c_ptr, i32, i32, i32, i32, c_ptr, c_ptr,

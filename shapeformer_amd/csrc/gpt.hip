@@ -1251,10 +1251,12 @@ __global__ __launch_bounds__(256) void embed_packed_kernel(const float* __restri
 // (B <= 256): it counts the live rows below its own from alen - stable in this launch: alen changes only in the stage-1 sampler -
 // writes its own map entries (no workgroup reads what another one writes) and moves its row's step embedding from the row-major
 // staging buffer into the fragment-packed residual at its slot; an ended row's slot is zeroed, so the rows that share a tile with
-// live ones stay finite.  slot_len is alen by slot: the decode attention's length word.
+// live ones stay finite.  slot_len is alen by slot: the decode attention's length word.  over (optional): set to 1, never cleared,
+// when more than 16 * budget rows are live (the step's launches cover `budget` row tiles).
 __global__ __launch_bounds__(256) void compact_rows_kernel(const int* __restrict__ alen, int* __restrict__ slot_of, int* __restrict__ row_of,
                                                            int* __restrict__ nlive, int* __restrict__ slot_len,
-                                                           const float* __restrict__ stage, float* __restrict__ resid, int B, int Bpad, int D) {
+                                                           const float* __restrict__ stage, float* __restrict__ resid, int B, int Bpad, int D,
+                                                           int budget, int* __restrict__ over) {
   __shared__ int s_all[4], s_below[4], s_mine;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int al = tid < B ? alen[tid] : -1;
@@ -1269,7 +1271,11 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(const int* __restrict
     slot_of[b] = mine >= 0 ? slot : -1;
     row_of[slot] = b;
     slot_len[slot] = mine >= 0 ? mine : -1;
-    if (b == 0) *nlive = total;
+    if (b == 0) {
+      *nlive = total;
+      // a step launched for `budget` row tiles (sfmi_decode_gemm_tiles_f32) would drop the live slots beyond them: the guard word says so
+      if (over && total > 16 * budget) over[0] = 1;
+    }
   }
   if (b == 0 && B + tid < Bpad) { row_of[B + tid] = -1; slot_len[B + tid] = -1; }      // padding slots of the last tile hold no row
   for (int qd = tid; qd < D / 4; qd += 256) {
@@ -1340,13 +1346,17 @@ __global__ void set_len_kernel(int* len, const int* src, int B, int delta) {
   if (i < B) len[i] = src[i] + delta;
 }
 
+extern "C" int sfmi_decode_gemm_padded_rows(int M);
 // Host side of sfmi_decode_gemm_f32: picks the instantiation from the launch shape (and the explicit sfmi_tune_set knobs dgemm_nw /
 // dgemm_un / dgemm_nt2 - nothing is read from the environment).  Only instantiations the default rules can reach exist: UN (k16-steps
 // of loads in flight) is at most 8 / 4 / 2 / 2 / 2 / 1 for 1 .. 6 row tiles, which keeps every one of them free of scratch.
 template <class P>
 static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid, float* out, int M,
                               int N, int K, int ldo, int ln, int act, int out_packed, int S, float* slab, int* cnt, int* pblk,
-                              unsigned long long* prof, void* stream, const int* alen = nullptr, const int* nlive = nullptr, int partial = 0) {
+                              unsigned long long* prof, void* stream, const int* alen = nullptr, const int* nlive = nullptr, int partial = 0,
+                              int budget = 0) {
+  // budget > 0 (sfmi_decode_gemm_tiles_f32): M is the chain's row count and decides NW below - with S, all that a row's summation
+  // order depends on - while the launch covers the row tiles 0 .. budget-1 only: MT, the row groups, UN, NT and the grid come from it
   if (prof && (alen || nlive)) return SFMI_EINVAL;      // a timed launch counts every workgroup at its end: no early exits
   if (!x || !Wp16 || !out || M <= 0 || M > 192 || S <= 0 || K % S || (ln && !c1)) return SFMI_EINVAL;   // larger batches: several chains (gpt.py)
   if (out_packed && N % 16) return SFMI_EINVAL;
@@ -1355,19 +1365,23 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
   if (prof && !pblk) return SFMI_EINVAL;
   const int kslice = K / S;
   // up to 6 row tiles per workgroup; more rows = row groups (grid.z), each of MT tiles: the packed operands must hold groups * MT * 16 rows
-  const int tiles = (M + 15) / 16;
+  int tiles = (M + 15) / 16;
   int groups = (tiles + 5) / 6, MT = (tiles + groups - 1) / groups;
   int NWv = (kslice >= 2048 && MT <= 4) ? 16 : 8;
   const int knob_nw = g_tune.dgemm_nw;     // 0 = the rule above; 4 / 8 / 16 k-parts per workgroup where the shape allows it
   if ((knob_nw == 4 || knob_nw == 8 || knob_nw == 16) && kslice % (16 * knob_nw) == 0 && MT <= (knob_nw == 8 ? 6 : 4)) NWv = knob_nw;
   if (kslice % (16 * NWv)) NWv = kslice % 64 == 0 ? 4 : 1;   // narrow models (K-slice not a multiple of 128): fewer k-parts
   if (kslice % (16 * NWv)) return SFMI_EINVAL;
+  if (budget > 0) {      // NW is pinned from here on; the tiles per workgroup and the row groups are the budget's (regrouped under mt_cap below)
+    tiles = budget;
+    groups = (tiles + 5) / 6; MT = (tiles + groups - 1) / groups;
+  }
   // the narrow forms have instances for fewer row tiles (NW = 4: 4, NW = 1: 1): more, smaller row groups instead.  The rows stay within
   // sfmi_decode_gemm_padded_rows (the two-n-tile form's groups of 3 already pad at least as far: tests/test_decode_ref_cpu.py)
-  const int mt_cap = NWv == 1 ? 1 : NWv == 4 ? 4 : 6;
+  const int mt_cap = NWv == 1 ? 1 : (NWv == 4 || NWv == 16) ? 4 : 6;      // (NW = 16 is chosen only at MT <= 4; a budget can regroup a pinned one)
   if (MT > mt_cap) { groups = (tiles + mt_cap - 1) / mt_cap; MT = (tiles + groups - 1) / groups; }
   DGemmArgs a;
-  a.x = x; a.Wp = Wp16; a.c1 = c1; a.c2 = c2; a.resid = resid; a.out = out; a.M = M; a.N = N; a.K = K; a.ldo = ldo; a.ln = ln; a.act = act;
+  a.x = x; a.Wp = Wp16; a.c1 = c1; a.c2 = c2; a.resid = resid; a.out = out; a.M = budget > 0 ? min(M, 16 * budget) : M; a.N = N; a.K = K; a.ldo = ldo; a.ln = ln; a.act = act;
   a.out_packed = out_packed; a.slab = slab; a.cnt = cnt; a.pblk = pblk; a.prof = prof; a.prio = g_tune.dgemm_prio; a.alen = alen;
   a.nlive = nlive; a.partial = partial;
   hipStream_t st = (hipStream_t)stream;
@@ -1377,6 +1391,7 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
     // Default (knob 1) when the row tiles divide into groups of exactly 3 (48 / 96 / 144 / 192 rows: no padded tile): GEMM phase of
     // 4 x 96 rows 3.06 -> 2.72 ms per step, loop 7.83 -> 7.53; with a padded tile (80 rows = 2 x 3 tiles for 5) it loses 1 %.
     const int g2 = (tiles + 2) / 3, MT2 = (tiles + g2 - 1) / g2;
+    if (budget > 0 && g2 * MT2 * 16 > sfmi_decode_gemm_padded_rows(M)) return SFMI_EINVAL;
     dim3 grid2(((N + 15) / 16 + 1) / 2, S, g2);
 #define DG2(MT_) hipLaunchKernelGGL((dgemm_kernel<MT_, 8, 2, 2, P>), grid2, dim3(512), 0, st, a)
     if (MT2 == 2) DG2(2); else DG2(3);      // tiles >= 3: MT2 is 2 (4 tiles) or 3, never 1
@@ -1384,6 +1399,7 @@ static int decode_gemm_launch(const float* x, const float* Wp16, const float* c1
     SFMI_CHECK_LAUNCH();
     return SFMI_OK;
   }
+  if (budget > 0 && groups * MT * 16 > sfmi_decode_gemm_padded_rows(M)) return SFMI_EINVAL;
   dim3 grid((N + 15) / 16, S, groups);
   const int steps = kslice / NWv / 16;
   int un = MT == 1 ? 8 : (MT == 2 ? 4 : (MT <= 5 ? 2 : 1));   // UN weight + UN*MT activation float4 loads in flight per wave (5 row tiles: 128 VGPRs; 6: 138 with two)
@@ -1496,6 +1512,17 @@ int sfmi_gpt_embed_f32(const float* E0, const float* E1, const float* Ex, const 
   hipLaunchKernelGGL(rowprep_kernel, dim3(a.M), dim3(256), 0, (hipStream_t)stream, a);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
+}
+
+// sfmi_decode_gemm_rows_f32 for a packed chain of form_rows rows at a budget of `tiles` row tiles: the launch covers the row tiles
+// 0 .. tiles-1 of the same buffers, slab and ticket words.  form_rows pins NW (the rule of decode_gemm_launch at M = form_rows), so every
+// row it computes has the bits of the full launch; tiles = ceil(form_rows / 16) IS that launch.
+int sfmi_decode_gemm_tiles_f32(const float* x, const float* Wp16, const float* c1, const float* c2, const float* resid,
+                               float* out, int form_rows, int tiles, int N, int K, int ldo, int ln, int act, int out_packed, int S,
+                               float* slab, int* cnt, const int* nlive, int partial, void* stream) {
+  if (!nlive || form_rows <= 0 || form_rows > 192 || tiles < 1 || 16 * tiles > sfmi_decode_gemm_padded_rows(form_rows)) return SFMI_EINVAL;
+  return decode_gemm_launch<DgProduct>(x, Wp16, c1, c2, resid, out, form_rows, N, K, ldo, ln, act, out_packed, S, slab, cnt, nullptr, nullptr,
+                                       stream, nullptr, nlive, partial ? 1 : 0, tiles);
 }
 
 // replaces the residual adds + LayerNorm of Block.forward (mingpt.py:107-111): x = resid + sum_s part[s] + bias
@@ -1704,7 +1731,19 @@ int sfmi_gpt_compact_rows_f32(const int* alen, int* slot_of, int* row_of, int* n
   if (!alen || !slot_of || !row_of || !nlive || !slot_len || !stage || !resid || B <= 0 || B > 256 || Bpad < B || Bpad - B > 256 || D % 16)
     return SFMI_EINVAL;
   hipLaunchKernelGGL(compact_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, alen, slot_of, row_of, nlive, slot_len, stage, resid,
-                     B, Bpad, D);
+                     B, Bpad, D, 0, (int*)nullptr);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+// the same at the head of a step whose launches cover the row tiles 0 .. budget-1 only (sfmi_decode_gemm_tiles_f32): over[0] = 1 when
+// more than 16 * budget rows are live (the step then computes nothing for the slots beyond); over is never cleared here
+int sfmi_gpt_compact_rows_budget_f32(const int* alen, int* slot_of, int* row_of, int* nlive, int* slot_len, const float* stage, float* resid,
+                                     int B, int Bpad, int D, int budget, int* over, void* stream) {
+  if (!alen || !slot_of || !row_of || !nlive || !slot_len || !stage || !resid || B <= 0 || B > 256 || Bpad < B || Bpad - B > 256 || D % 16)
+    return SFMI_EINVAL;
+  if (!over || budget < 1 || 16 * budget > Bpad) return SFMI_EINVAL;
+  hipLaunchKernelGGL(compact_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, alen, slot_of, row_of, nlive, slot_len, stage, resid,
+                     B, Bpad, D, budget, over);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

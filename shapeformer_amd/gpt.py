@@ -40,6 +40,65 @@ class _Layer:
     pass
 
 
+def tile_budget_policy(full, nlive_of_block, block, lag=2):
+    """Row-tile budget of a packed chain's block `block` of decode steps (CondTupleGPT.TILE_BUDGET).  full: the chain's row tiles;
+    nlive_of_block[i]: the chain's live count as copied to the host after block i's last step (entries from `block - lag + 1` on are
+    not looked at: the host has not waited for them).  Blocks 0 .. lag-1 get the full budget - nothing has been observed for them;
+    block j >= lag gets clamp(ceil(nlive_of_block[j - lag] / 16), 1, full): the live count never grows, so that covers every step of
+    the block.  There is no empty step: the smallest budget is one tile."""
+    if block < lag:
+        return int(full)
+    return int(min(int(full), max(1, (int(nlive_of_block[block - lag]) + 15) // 16)))
+
+
+class _BudgetFeedback:
+    """Host side of TILE_BUDGET for one run of the decode loop over the chains `ctxs` on `streams`: `graphs(done)` gives the step
+    graph of every chain for step `done` (a chain without budget graphs: its one graph, or None), `stepped(done)` is called after the
+    step's replays.  Steps go in blocks of TILE_BUDGET_EVERY; after a block's last replay every chain's stream copies {nlive, over} into
+    a pinned ring slot and records an event; before block j is enqueued the host waits for the events of block j - 2 - at least one
+    whole block is still queued then - and takes the budgets from that copy.  The budgets per block go to ctx["budget_log"]."""
+    RING = 4
+
+    def __init__(self, gpt, ctxs, streams):
+        self.ctxs, self.streams, self.every = ctxs, streams, max(1, int(gpt.TILE_BUDGET_EVERY))
+        self.armed = [c.get("graphs") is not None for c in ctxs]
+        self.cur = [c["graph"] for c in ctxs]
+        self.seen = [[] for _ in ctxs]      # live count per finished block, as read by the host
+        if any(self.armed):
+            self.ring = [torch.zeros(self.RING, 2, dtype=torch.int32).pin_memory() if a else None for a in self.armed]
+            self.ev = [[torch.cuda.Event() for _ in range(self.RING)] if a else None for a in self.armed]
+        for c in ctxs:
+            c["budget_log"] = []
+        gpt.last_budget_log = [c["budget_log"] for c in ctxs]      # the last run's budgets per chain and block (tests, records)
+
+    def graphs(self, done):
+        if done % self.every == 0:
+            j = done // self.every
+            for i, c in enumerate(self.ctxs):
+                if not self.armed[i]:
+                    continue
+                if j >= 2:
+                    self.ev[i][(j - 2) % self.RING].synchronize()
+                    nlive, over = self.ring[i][(j - 2) % self.RING].tolist()
+                    if over:
+                        raise L.SfmiError("a decode step ran at a row-tile budget below its live rows (TILE_BUDGET)")
+                    self.seen[i].append(nlive)
+                T = tile_budget_policy((c["B"] + 15) // 16, self.seen[i], j)
+                c["budget_log"].append(T)
+                self.cur[i] = c["graphs"][T]
+        return self.cur
+
+    def stepped(self, done):
+        if (done + 1) % self.every:
+            return
+        k = (done // self.every) % self.RING
+        for i, (c, s) in enumerate(zip(self.ctxs, self.streams)):
+            if self.armed[i]:
+                with torch.cuda.stream(s):
+                    self.ring[i][k].copy_(c["st"]["nlo"], non_blocking=True)
+                    self.ev[i][k].record(s)
+
+
 class CondTupleGPT:
     S_PROJ, S_FC2 = 1, 4   # in-kernel split-K of the N = n_embd GEMMs (64 n-tiles -> 256 workgroups)
     S_PROJ_M = 1           # proj above 16 rows: with four chains in flight 1 beats 2 beats 4 (4.13 / 4.17 / 4.18 ms per step); fc2: 4 beats 2 and 8
@@ -207,6 +266,7 @@ class CondTupleGPT:
         # decode activations are fragment-packed in 16-row tiles (csrc/gpt.hip pk_off); above 96 rows the decode GEMM works on
         # row groups of equal tile counts, so the buffers hold groups x tiles-per-group x 16 rows
         Bp = int(L.lib().sfmi_decode_gemm_padded_rows(B))
+        nlo = torch.zeros(2, device=dev, dtype=torch.int32)      # {nlive, over}: adjacent, so one small copy carries both to the host (TILE_BUDGET)
         st = dict(key=key,
                   seq=torch.zeros(B, self.Lmax + 1, 2, device=dev, dtype=torch.int32),
                   len=torch.zeros(B, device=dev, dtype=torch.int32), Lc=torch.zeros(B, device=dev, dtype=torch.int32),
@@ -216,7 +276,7 @@ class CondTupleGPT:
                   # packed chain (COMPACT_LIVE, csrc/gpt.hip compact_rows_kernel): the step's embeddings by row, the slot map, the live count
                   emb=torch.zeros(B, D, device=dev), slot_of=torch.zeros(B, device=dev, dtype=torch.int32),
                   row_of=torch.zeros(Bp, device=dev, dtype=torch.int32), slot_len=torch.zeros(Bp, device=dev, dtype=torch.int32),
-                  nlive=torch.zeros(1, device=dev, dtype=torch.int32),
+                  nlo=nlo, nlive=nlo[:1], over=nlo[1:],     # over: set by a budget step's compaction when more rows are live than its launches cover
                   slab=f(L.lib().sfmi_decode_gemm_slab_floats(Bp, 4 * D, 4)), cnt=torch.zeros(Bp // 16 * (max(4 * D, self.Vpad) // 16 + 1), device=dev, dtype=torch.int32),
                   Kc=f(len(self.layers), B, self.Lmax + 1, D), Vc=f(len(self.layers), B, self.Lmax + 1, D),
                   logp=torch.zeros(B, max_steps, 2, device=dev, dtype=torch.float32),
@@ -254,14 +314,19 @@ class CondTupleGPT:
         return out
 
     # ------------------------------------------------------------------ C-ABI wrappers
-    def _dgemm(self, x, wp, c1, c2, resid, out, M, N, K, ldo, ln, act, packed=1, S=1, st=None, prof=False, alen=None, nlive=None, partial=1):
+    def _dgemm(self, x, wp, c1, c2, resid, out, M, N, K, ldo, ln, act, packed=1, S=1, st=None, prof=False, alen=None, nlive=None, partial=1, tiles=0):
         """alen: the chain's per-row attention length (st["alen"]): row groups without a live row do no work (not with prof: a timed
         launch counts every workgroup at its end).  nlive: the live-row count of a packed chain (st["nlive"]): only the row tiles that
-        hold a live slot are run (partial=0: whole row groups, as with alen)."""
+        hold a live slot are run (partial=0: whole row groups, as with alen).  tiles > 0 (with nlive): the launch is shaped for the
+        row tiles 0 .. tiles-1 of the M-row chain (TILE_BUDGET); M still decides everything a row's bits depend on."""
         st = st or self._state
         while S > 1 and (K // S) % 128:
             S //= 2
         slab, cnt = (L.ptr(st["slab"]), L.ptr(st["cnt"])) if S > 1 else (None, None)
+        if nlive is not None and not prof and tiles:
+            L.check(L.lib().sfmi_decode_gemm_tiles_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, int(tiles), N, K, ldo,
+                                                       ln, act, packed, S, slab, cnt, L.ptr(nlive), int(partial), L.stream_ptr()), "sfmi_decode_gemm_tiles_f32")
+            return
         if nlive is not None and not prof:
             L.check(L.lib().sfmi_decode_gemm_rows_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
                                                       ln, act, packed, S, slab, cnt, L.ptr(nlive), int(partial), L.stream_ptr()), "sfmi_decode_gemm_rows_f32")
@@ -483,10 +548,21 @@ class CondTupleGPT:
     # launch forms are chosen from the chain's rows as before, so every row's arithmetic - and seq / len / logp - is bit-identical.
     COMPACT_LIVE = True
     COMPACT_LIVE_TILES = True
+    # The live count of a packed chain never grows, so a value the host read a few steps ago bounds every later step.  TILE_BUDGET (armed
+    # where COMPACT_LIVE_TILES is): `_prepare` captures one step graph per row-tile budget T = 1 .. ceil(B / 16), whose GEMM and attention
+    # launches are shaped for T row tiles (sfmi_decode_gemm_tiles_f32: the k-parts per workgroup stay those of the chain's B rows, so
+    # every row keeps its bits), and the loop replays, per block of TILE_BUDGET_EVERY steps, the graph of T = ceil(nlive / 16) of the
+    # live count copied to the host two blocks earlier (`tile_budget_policy`; one block always stays queued, the device never waits
+    # for the host).  A budget step whose compaction finds more live rows than it covers sets st["over"]: SfmiError at the next read.
+    # TILE_BUDGET_FORMS: the budgets that keep a graph of their own (None: all); any other budget replays the next larger one's.
+    TILE_BUDGET = True
+    TILE_BUDGET_EVERY = 8
+    TILE_BUDGET_FORMS = None
 
-    def decode_step(self, st, B, sp):
+    def decode_step(self, st, B, sp, budget=0):
         """Position t = len[b]-1 of every row through both stages; st["resid"] must hold its embedding on entry
-        (written by the previous step's sampler tail, or by `_embed` before the first step)."""
+        (written by the previous step's sampler tail, or by `_embed` before the first step).  budget > 0 (a packed chain with
+        live row tiles only): the step's launches cover the row tiles 0 .. budget-1."""
         D = self.D
         lib = L.lib()
         r = st["resid"]
@@ -503,7 +579,16 @@ class CondTupleGPT:
         alen_g = st["alen"] if armed >= 2 else None
         compact = int(sp.get("compact_live", 0))      # 0 = rows in place, 1 = packed + GEMM group exit, 2 = packed + live row tiles only
         gk = dict(alen=alen_g)
-        if compact:
+        Ba = B                                        # slots the decode attention walks
+        if compact >= 2 and budget:
+            gk = dict(nlive=st["nlive"], partial=1, tiles=int(budget))
+            Ba = min(B, 16 * int(budget))
+            L.check(lib.sfmi_gpt_compact_rows_budget_f32(L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.ptr(st["row_of"]), L.ptr(st["nlive"]),
+                                                         L.ptr(st["slot_len"]), L.ptr(st["emb"]), L.ptr(r), B, r.shape[0], D, int(budget),
+                                                         L.ptr(st["over"]), L.stream_ptr()), "sfmi_gpt_compact_rows_budget_f32")
+        elif budget:
+            raise L.SfmiError("a row-tile budget needs a packed chain that runs live row tiles only")
+        elif compact:
             gk = dict(nlive=st["nlive"], partial=int(compact >= 2))
             L.check(lib.sfmi_gpt_compact_rows_f32(L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.ptr(st["row_of"]), L.ptr(st["nlive"]),
                                                   L.ptr(st["slot_len"]), L.ptr(st["emb"]), L.ptr(r), B, r.shape[0], D, L.stream_ptr()),
@@ -514,7 +599,7 @@ class CondTupleGPT:
                 self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg, **gk)
             if "attn" not in skip and compact:
                 L.check(lib.sfmi_gpt_attn_decode_rows_f32(L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]),
-                                                          L.ptr(st["slot_len"]), L.ptr(st["row_of"]), L.ptr(st["y"]), B, D, self.H, self.Lmax + 1,
+                                                          L.ptr(st["slot_len"]), L.ptr(st["row_of"]), L.ptr(st["y"]), Ba, D, self.H, self.Lmax + 1,
                                                           L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
                                                           L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
                                                           L.ptr(st["prof"]) if pa else None, L.stream_ptr()), "sfmi_gpt_attn_decode_rows_f32")
@@ -573,6 +658,9 @@ class CondTupleGPT:
             shared_prefix = B * Lc_max >= self.SHARED_PREFIX_MIN_ROW_TOKENS
         steps = min(max_steps, self.Lmax - Lc_max - Lz)   # never exceed block_size (stop, don't crop)
         st = self._alloc(B, max_steps, slot)
+        if self.TILE_BUDGET and int(st["over"].item()):      # the last run of this slot dropped live rows in a budget step
+            st["over"].zero_()
+            raise L.SfmiError("a decode step ran at a row-tile budget below its live rows (TILE_BUDGET): the last results of this chain are invalid")
         st["seq"].zero_()
         st["seq"][:, :c_tokens.shape[1]] = c_tokens.to(self.dev, torch.int32)
         st["Lc"].copy_(Lc.to(self.dev, torch.int32))
@@ -603,6 +691,8 @@ class CondTupleGPT:
         sp["skip_ended"] = (2 if self.SKIP_ENDED_GEMM else 1) if (self.SKIP_ENDED and sp_kw["mask_invalid"] and not return_logits
                                                                   and force_tokens is None and not self._ablate) else 0
         sp["compact_live"] = (2 if self.COMPACT_LIVE_TILES else 1) if (self.COMPACT_LIVE and sp["skip_ended"] >= 2) else 0
+        # step graphs per row-tile budget: only where live row tiles are run at all (the timed GEMM launch has no such form: it runs every row)
+        sp["tile_budget"] = int(bool(self.TILE_BUDGET and sp["compact_live"] == 2 and "gemm" not in self._profile))
         if force_tokens is not None:   # (B,max_steps,2) teacher forcing for stepwise parity tests
             ft = torch.zeros(B, max_steps, 2, dtype=torch.int32)
             ft[:, :force_tokens.shape[1]] = torch.as_tensor(force_tokens).to(torch.int32)
@@ -642,30 +732,42 @@ class CondTupleGPT:
                                                       L.ptr(self.cond_pos_emb), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
                                                       L.ptr(st["resid"]), B, self.D, self.Lmax + 1, self.end[0], L.stream_ptr()),
                     "sfmi_gpt_embed_packed_f32")
-        graph = None
+        graph, graphs = None, None
         if use_graph and steps > 1:
+            full = (B + 15) // 16
+            forms = tuple(sorted(set(self.TILE_BUDGET_FORMS))) if self.TILE_BUDGET_FORMS is not None else None
             gkey = (B, tuple(sorted((k, v) for k, v in sp.items() if k not in ("hist", "force", "seed"))), return_logits,
-                    self._ablate, self._profile, self.S_PROJ, self.S_PROJ_M, self.S_FC2,
+                    self._ablate, self._profile, self.S_PROJ, self.S_PROJ_M, self.S_FC2, forms,
                     int(L.lib().sfmi_tune_generation()))      # launch-shape knobs are baked into a captured graph: re-capture when one changed
             cached = self._graphs.get(slot)
             if cached is None or cached[0] != gkey or return_logits:
                 side = torch.cuda.Stream(device=self.dev)
-                side.wait_stream(torch.cuda.current_stream())
-                saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid", "emb")}
-                with torch.cuda.stream(side):
-                    self.decode_step(st, B, sp)      # warm-up outside capture
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                for k, v in saved.items():
-                    st[k].copy_(v)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self.decode_step(st, B, sp)
-                for k, v in saved.items():           # capture does not execute, but keep state pristine
-                    st[k].copy_(v)
-                self._graphs[slot] = (gkey, graph)
+                # (the guard word is saved with the rest: a small form warmed up on a full chain trips it)
+                saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid", "emb", "over")}
+
+                def capture(budget):
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        self.decode_step(st, B, sp, budget)      # warm-up outside capture
+                    torch.cuda.current_stream().wait_stream(side)
+                    torch.cuda.synchronize()
+                    for k, v in saved.items():
+                        st[k].copy_(v)
+                    g_ = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g_):
+                        self.decode_step(st, B, sp, budget)
+                    for k, v in saved.items():           # capture does not execute, but keep state pristine
+                        st[k].copy_(v)
+                    return g_
+                graph = capture(0)      # the full form first: it writes every row of the scratch buffers the smaller forms' warm-ups leave alone
+                by_budget = {full: graph}
+                if sp["tile_budget"]:
+                    for T in range(full - 1, 0, -1):      # a budget without a form of its own replays the next larger one's graph
+                        by_budget[T] = capture(T) if (forms is None or T in forms) else by_budget[T + 1]
+                self._graphs[slot] = (gkey, graph, by_budget)
             graph = self._graphs[slot][1]
-        return dict(st=st, sp=sp, B=B, steps=steps, graph=graph, hist=hist, Lc_host=Lc_host, Lz=Lz)
+            graphs = self._graphs[slot][2] if sp["tile_budget"] else None
+        return dict(st=st, sp=sp, B=B, steps=steps, graph=graph, graphs=graphs, budget_log=[], hist=hist, Lc_host=Lc_host, Lz=Lz)
 
     @staticmethod
     def _sp(top_k, top_p, temperature, best_in_first, mask_invalid, mask_invalid_completion, seed):
@@ -715,11 +817,13 @@ class CondTupleGPT:
             after_prefill()
         done = 0
         if g is not None:
+            fb = _BudgetFeedback(self, [ctx], [torch.cuda.current_stream()])
             while done < steps:
                 n = min(check_every, steps - done) if stop_early else steps - done
                 for _ in range(n):
-                    g.replay()
-                done += n
+                    fb.graphs(done)[0].replay()
+                    fb.stepped(done)
+                    done += 1
                 if stop_early and ended():
                     break
         else:
@@ -903,16 +1007,22 @@ class CondTupleGPT:
             for s in streams:
                 s.wait_stream(cur)
         done = 0
+        fb = _BudgetFeedback(self, ctxs, streams)
+        on_step = getattr(self, "_on_step", None)      # measurement hook (tools/ar_sweep.py bins): called after every step's enqueue
         while done < steps:
             n = min(check_every, steps - done) if stop_early else steps - done
             for _ in range(n):
-                for c, s in zip(ctxs, streams):
+                gs = fb.graphs(done)
+                for c, s, g_ in zip(ctxs, streams, gs):
                     with torch.cuda.stream(s):
-                        if c["graph"] is not None:
-                            c["graph"].replay()
+                        if g_ is not None:
+                            g_.replay()
                         else:
                             self.decode_step(c["st"], c["B"], c["sp"])
-            done += n
+                fb.stepped(done)
+                done += 1
+                if on_step is not None:
+                    on_step(done, streams)
             if stop_early:
                 for s in streams:
                     cur.wait_stream(s)

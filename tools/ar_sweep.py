@@ -13,7 +13,10 @@ decode GEMMs' all-ended row groups; default 2 = the product), `profile=attn,gemm
 the first n compute-unit mask bits = n / 8 CUs of every XCD; hipExtStreamCreateWithCUMask), `cusplit=<n>` (chains 0, 1 on the first n
 bits, chains 2, 3 on the other 256 - n: spatial partition of the two kernel families together with a per-chain ablate=),
 `cumode=block` (mask bits taken as contiguous blocks instead: bits [0, n) vs [n, 256)), `hwid=1` (print which XCC / SE / CU the masked
-streams' workgroups land on).  Lines starting with # are skipped.
+streams' workgroups land on), `budget=0|1` / `every=<n>` (gpt.TILE_BUDGET / TILE_BUDGET_EVERY: step graphs per row-tile budget),
+`forms=1,2,3` (gpt.TILE_BUDGET_FORMS: the budgets that keep a graph of their own), `bins=<n>` (per-step time of the loop in bins of n
+steps: events recorded on the chains' own streams, no host sync; printed with the budgets the chains took per block),
+Lines starting with # are skipped.
 Condition lengths are uniform in [100, 216] (mean 158 = the bench's synthetic clouds); positions ascending, end-token closed.
 """
 from __future__ import annotations
@@ -182,6 +185,10 @@ def main():
         gpt._profile = kv.pop("profile", "")
         skip = int(kv.pop("skip", "2"))      # ended rows: 0 = every row keeps streaming, 1 = attention + sampler skip them, 2 = and the GEMMs' all-ended row groups
         gpt.SKIP_ENDED, gpt.SKIP_ENDED_GEMM = skip > 0, skip > 1
+        gpt.TILE_BUDGET, gpt.TILE_BUDGET_EVERY = kv.pop("budget", "1") != "0", int(kv.pop("every", "8"))
+        forms_ = kv.pop("forms", None)
+        gpt.TILE_BUDGET_FORMS = None if forms_ is None else tuple(int(v) for v in forms_.split(",") if v)
+        bins = int(kv.pop("bins", "0"))
         if kv.pop("part", "0") != "0":
             raise ValueError("part=: the self-placing attention launch was removed from the library after round 6's measurements (profiles/r06_overlap.md; code from commit ac5c852 on)")
         bg = kv.pop("bgsdf", None)
@@ -249,6 +256,16 @@ def main():
                         bgst["stream"].wait_event(ev[0])
                         bgev.extend(bg_launch(nl))
                 kw = dict(max_steps=a.steps, stop_early=False, seed=rep, after_prefill=started)
+                marks = []      # (step, one event per chain stream), every `bins` steps: enqueued behind the step's replay, never waited for in the loop
+                gpt._on_step = None
+                if bins and rep:
+                    def on_step(done, streams, marks=marks):
+                        if done % bins == 0 or done == 1:
+                            evs = [torch.cuda.Event(enable_timing=True) for _ in streams]
+                            for e_, s_ in zip(evs, streams):
+                                e_.record(s_)
+                            marks.append((done, evs))
+                    gpt._on_step = on_step
                 if rep:
                     probe.start()
                     if gpt._profile:
@@ -263,6 +280,15 @@ def main():
                 done_bg = sum(1 for e in bgev if e.query())
                 torch.cuda.synchronize()
                 assert int(r["steps"]) == a.steps
+                gpt._on_step = None
+                if rep and len(marks) > 1:
+                    # a bin's time = the latest chain's end event minus the latest chain's start event, per step
+                    t_ = [[marks[0][1][i].elapsed_time(m[1][i]) for i in range(len(m[1]))] for m in marks]
+                    say(f"#   bins of {bins} steps, ms/step (latest chain): " + " ".join(
+                        f"{marks[k][0]}:{(max(t_[k]) - max(t_[k - 1])) / (marks[k][0] - marks[k - 1][0]):.3f}" for k in range(1, len(marks))))
+                    logs_ = getattr(gpt, "last_budget_log", None) or []
+                    for ci, lg in enumerate(logs_):
+                        say(f"#   chain {ci} budgets per block of {gpt.TILE_BUDGET_EVERY}: " + "".join(str(min(v, 9)) for v in lg))
                 if rep:
                     ms.append(ev[0].elapsed_time(ev[1]) / a.steps)
                     if bg:
