@@ -12,6 +12,7 @@ shapeformer.py:227).  No CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import numpy as np
 import torch
@@ -51,52 +52,56 @@ def tile_budget_policy(full, nlive_of_block, block, lag=2):
     return int(min(int(full), max(1, (int(nlive_of_block[block - lag]) + 15) // 16)))
 
 
-class _BudgetFeedback:
-    """Host side of TILE_BUDGET for one run of the decode loop over the chains `ctxs` on `streams`: `graphs(done)` gives the step
-    graph of every chain for step `done` (a chain without budget graphs: its one graph, or None), `stepped(done)` is called after the
-    step's replays.  Steps go in blocks of TILE_BUDGET_EVERY; after a block's last replay every chain's stream copies {nlive, over} into
-    a pinned ring slot and records an event; before block j is enqueued the host waits for the events of block j - 2 - at least one
-    whole block is still queued then - and takes the budgets from that copy.  The budgets per block go to ctx["budget_log"]."""
+def decode_level(mask_invalid, return_logits, force_tokens, ablate, profile, skip_ended=True, compact_live=True, tile_budget=True):
+    """How far a decode chain goes in skipping rows that have ended: 0 = every row runs; 1 = ended rows are skipped in place (by the
+    attention, the sampler and the decode GEMMs' all-ended row groups); 2 = the live rows are packed and only the row tiles that hold a
+    live slot run; 3 = level 2 with a step graph per row-tile budget.  The last three arguments are CondTupleGPT.SKIP_ENDED,
+    COMPACT_LIVE and TILE_BUDGET: each rung needs the one below.  Ended rows are skipped only where their tokens are forced and nobody
+    looks at their logits: with mask_invalid, without logits history, teacher forcing or a timing ablation (those measure every
+    row's stream).  The timed GEMM launch ("gemm" in profile) has no form shaped for a budget: it runs every row."""
+    if not (skip_ended and mask_invalid and not return_logits and force_tokens is None and not ablate):
+        return 0
+    if not compact_live:
+        return 1
+    return 3 if tile_budget and "gemm" not in profile else 2
+
+
+class _Chain:
+    """One decode chain of `CondTupleGPT._run_chains`: its context, its stream and the host side of TILE_BUDGET.  Steps go in blocks
+    of TILE_BUDGET_EVERY; after a block's last replay the chain's stream copies {nlive, over} into a pinned ring slot and records an
+    event (`report`); before block j is enqueued the host waits for the event of block j - 2 - at least one whole block is still
+    queued then - and takes the budget, and with it the step graph, from that copy (`choose`).  The budgets per block go to
+    ctx["budget_log"].  A chain without budget graphs keeps its one graph; one without a graph steps eagerly."""
     RING = 4
 
-    def __init__(self, gpt, ctxs, streams):
-        self.ctxs, self.streams, self.every = ctxs, streams, max(1, int(gpt.TILE_BUDGET_EVERY))
-        self.armed = [c.get("graphs") is not None for c in ctxs]
-        self.cur = [c["graph"] for c in ctxs]
-        self.seen = [[] for _ in ctxs]      # live count per finished block, as read by the host
-        if any(self.armed):
-            self.ring = [torch.zeros(self.RING, 2, dtype=torch.int32).pin_memory() if a else None for a in self.armed]
-            self.ev = [[torch.cuda.Event() for _ in range(self.RING)] if a else None for a in self.armed]
-        for c in ctxs:
-            c["budget_log"] = []
-        gpt.last_budget_log = [c["budget_log"] for c in ctxs]      # the last run's budgets per chain and block (tests, records)
+    def __init__(self, ctx, stream, own_stream):
+        self.ctx, self.stream, self.own_stream = ctx, stream, own_stream
+        self.graph, self.by_budget = ctx["graph"], ctx.get("graphs")
+        self.seen = []      # live count per finished block, as read by the host
+        if self.by_budget is not None:
+            self.ring = torch.zeros(self.RING, 2, dtype=torch.int32).pin_memory()
+            self.ev = [torch.cuda.Event() for _ in range(self.RING)]
+        ctx["budget_log"] = []
 
-    def graphs(self, done):
-        if done % self.every == 0:
-            j = done // self.every
-            for i, c in enumerate(self.ctxs):
-                if not self.armed[i]:
-                    continue
-                if j >= 2:
-                    self.ev[i][(j - 2) % self.RING].synchronize()
-                    nlive, over = self.ring[i][(j - 2) % self.RING].tolist()
-                    if over:
-                        raise L.SfmiError("a decode step ran at a row-tile budget below its live rows (TILE_BUDGET)")
-                    self.seen[i].append(nlive)
-                T = tile_budget_policy((c["B"] + 15) // 16, self.seen[i], j)
-                c["budget_log"].append(T)
-                self.cur[i] = c["graphs"][T]
-        return self.cur
+    def scope(self):
+        """The chain's stream as the current one; nothing at all for a chain that runs on the caller's stream."""
+        return torch.cuda.stream(self.stream) if self.own_stream else contextlib.nullcontext()
 
-    def stepped(self, done):
-        if (done + 1) % self.every:
-            return
-        k = (done // self.every) % self.RING
-        for i, (c, s) in enumerate(zip(self.ctxs, self.streams)):
-            if self.armed[i]:
-                with torch.cuda.stream(s):
-                    self.ring[i][k].copy_(c["st"]["nlo"], non_blocking=True)
-                    self.ev[i][k].record(s)
+    def choose(self, j):
+        if j >= 2:
+            self.ev[(j - 2) % self.RING].synchronize()
+            nlive, over = self.ring[(j - 2) % self.RING].tolist()
+            if over:
+                raise L.SfmiError("a decode step ran at a row-tile budget below its live rows (TILE_BUDGET)")
+            self.seen.append(nlive)
+        T = tile_budget_policy((self.ctx["B"] + 15) // 16, self.seen, j)
+        self.ctx["budget_log"].append(T)
+        self.graph = self.by_budget[T]
+
+    def report(self, j):
+        with self.scope():
+            self.ring[j % self.RING].copy_(self.ctx["st"]["nlo"], non_blocking=True)
+            self.ev[j % self.RING].record(self.stream)
 
 
 class CondTupleGPT:
@@ -323,25 +328,19 @@ class CondTupleGPT:
         while S > 1 and (K // S) % 128:
             S //= 2
         slab, cnt = (L.ptr(st["slab"]), L.ptr(st["cnt"])) if S > 1 else (None, None)
-        if nlive is not None and not prof and tiles:
-            L.check(L.lib().sfmi_decode_gemm_tiles_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, int(tiles), N, K, ldo,
-                                                       ln, act, packed, S, slab, cnt, L.ptr(nlive), int(partial), L.stream_ptr()), "sfmi_decode_gemm_tiles_f32")
-            return
-        if nlive is not None and not prof:
-            L.check(L.lib().sfmi_decode_gemm_rows_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
-                                                      ln, act, packed, S, slab, cnt, L.ptr(nlive), int(partial), L.stream_ptr()), "sfmi_decode_gemm_rows_f32")
-            return
-        if alen is not None and not prof:
-            L.check(L.lib().sfmi_decode_gemm_live_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
-                                                      ln, act, packed, S, slab, cnt, L.ptr(alen), L.stream_ptr()), "sfmi_decode_gemm_live_f32")
-            return
+        mats = (L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out))
+        shape = (N, K, ldo, ln, act, packed, S, slab, cnt)
         if prof:
-            L.check(L.lib().sfmi_decode_gemm_prof_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
-                                                      ln, act, packed, S, slab, cnt, L.ptr(st["pblk"]), L.ptr(st["prof"][4:]),
-                                                      L.stream_ptr()), "sfmi_decode_gemm_prof_f32")
-            return
-        L.check(L.lib().sfmi_decode_gemm_f32(L.ptr(x), L.ptr(wp), L.ptr(c1), L.ptr(c2), L.ptr(resid), L.ptr(out), M, N, K, ldo,
-                                             ln, act, packed, S, slab, cnt, L.stream_ptr()), "sfmi_decode_gemm_f32")
+            entry, args = "sfmi_decode_gemm_prof_f32", (*mats, M, *shape, L.ptr(st["pblk"]), L.ptr(st["prof"][4:]))
+        elif nlive is not None and tiles:
+            entry, args = "sfmi_decode_gemm_tiles_f32", (*mats, M, int(tiles), *shape, L.ptr(nlive), int(partial))
+        elif nlive is not None:
+            entry, args = "sfmi_decode_gemm_rows_f32", (*mats, M, *shape, L.ptr(nlive), int(partial))
+        elif alen is not None:
+            entry, args = "sfmi_decode_gemm_live_f32", (*mats, M, *shape, L.ptr(alen))
+        else:
+            entry, args = "sfmi_decode_gemm_f32", (*mats, M, *shape)
+        L.check(getattr(L.lib(), entry)(*args, L.stream_ptr()), entry)
 
     def _rowprep(self, resid_in, part, bias, S, M, resid_out, xn, ln, Eadd=None, P=0, st=None):
         L.check(L.lib().sfmi_gpt_rowprep_f32(L.ptr(resid_in), L.ptr(part), L.ptr(bias), L.ptr(Eadd),
@@ -359,6 +358,58 @@ class CondTupleGPT:
                                            L.ptr(resid), L.ptr(xn), L.ptr(ln[0]) if ln else None, L.ptr(ln[1]) if ln else None,
                                            B, P, self.D, self.Lmax + 1,
                                            self.end[0], L.ptr(st.get("rowoff")), int(st.get("M_packed") or 0), L.stream_ptr()), "sfmi_gpt_embed_f32")
+
+    def _embed_step0(self, st, B, level):
+        """Embedding of the last condition token (step-0 input) into the fragment-packed residual buffer; a packed chain: into the
+        row-major staging buffer, from where the head of the step moves it to the rows' slots."""
+        entry, out = ("sfmi_gpt_embed_rows_f32", st["emb"]) if level >= 2 else ("sfmi_gpt_embed_packed_f32", st["resid"])
+        L.check(getattr(L.lib(), entry)(L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), L.ptr(self.cond_pos_emb),
+                                        L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]), L.ptr(out), B, self.D, self.Lmax + 1,
+                                        self.end[0], L.stream_ptr()), entry)
+
+    def _compact(self, st, B, budget):
+        """Head of a packed chain's step: the live rows' embeddings go from the staging buffer to slots 0 .. nlive-1 of the residual, in
+        ascending row order.  At a budget the launch also sets st["over"] when more rows are live than the budget's tiles hold."""
+        r = st["resid"]
+        a = (L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.ptr(st["row_of"]), L.ptr(st["nlive"]), L.ptr(st["slot_len"]), L.ptr(st["emb"]),
+             L.ptr(r), B, r.shape[0], self.D)
+        if budget:
+            L.check(L.lib().sfmi_gpt_compact_rows_budget_f32(*a, int(budget), L.ptr(st["over"]), L.stream_ptr()), "sfmi_gpt_compact_rows_budget_f32")
+        else:
+            L.check(L.lib().sfmi_gpt_compact_rows_f32(*a, L.stream_ptr()), "sfmi_gpt_compact_rows_f32")
+
+    def _attn_decode(self, st, sp, li, B, level, budget):
+        """Decode attention of layer li.  A packed chain walks its slots (at a budget: those of the budget's row tiles); rows in place
+        get alen in the `len` slot from level 1 on (no new kernel argument): an ended row is not streamed or appended to."""
+        lanes, pa = int(sp.get("gate_lanes", 0)), "attn" in self._profile
+        kv = (L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]))
+        tail = (self.D, self.H, self.Lmax + 1, L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
+                L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
+                L.ptr(st["prof"]) if pa else None, L.stream_ptr())
+        if level >= 2:
+            slots = min(B, 16 * int(budget)) if budget else B
+            L.check(L.lib().sfmi_gpt_attn_decode_rows_f32(*kv, L.ptr(st["slot_len"]), L.ptr(st["row_of"]), L.ptr(st["y"]), slots, *tail),
+                    "sfmi_gpt_attn_decode_rows_f32")
+        else:
+            L.check(L.lib().sfmi_gpt_attn_decode_gated_f32(*kv, L.ptr(st["alen"] if level else st["len"]), L.ptr(st["y"]), B, *tail),
+                    "sfmi_gpt_attn_decode_gated_f32")
+
+    def _sample_stage(self, st, sp, B, s, level):
+        """Sampler of stage s and the next input's embedding (its tail).  A packed chain reads the logits by slot and leaves the
+        embedding in the staging buffer; from level 1 on an ended row gets the forced token without a look at its logits."""
+        r = st["resid"]
+        state = (L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]), L.ptr(st["logp"]))
+        model = (L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), self.D, 1, B, self.V, self.Vpad, self.Lmax + 1,
+                 s, self.end[0], self.end[1], sp["top_k"], sp["top_p"], sp["temperature"], int(sp["best_in_first"]))
+        draw = (int(sp["mask_invalid_completion"]), sp["max_steps"], sp["seed"], L.ptr(st.get("seed")), int(s == 1),
+                sp.get("row_offset", 0), sp.get("rows_total", B), int(sp.get("step_offset", 0)), L.ptr(st["alen"]))
+        if level >= 2:
+            L.check(L.lib().sfmi_gpt_sample_rows_f32(*state, L.ptr(r), L.ptr(st["emb"]), *model, *draw, L.ptr(st["slot_of"]), L.stream_ptr()),
+                    "sfmi_gpt_sample_rows_f32")
+        else:
+            hist = sp["hist"][s] if sp.get("hist") is not None else None
+            L.check(L.lib().sfmi_gpt_sample_live_f32(*state, L.ptr(hist), L.ptr(sp.get("force")), L.ptr(r), *model, int(sp["mask_invalid"]),
+                                                     *draw, int(level > 0), L.stream_ptr()), "sfmi_gpt_sample_live_f32")
 
     def _gemm(self, x, w, bias, resid, y, M, N, K, act=0, og=0, ogs=0):
         """y (M,N) = act(x (M,K) w (N,K)^T + bias) + resid: the plain GEMMs of the prefill / teacher-forced forward
@@ -446,26 +497,11 @@ class CondTupleGPT:
     def forward(self, idx, extra_idx=None, L_cond=1, target_idx=None):
         """CondTupleGPT.forward: idx (B,L,2), extra_idx (B,L,1) or None (-> AR_N rule), target_idx (B,L,2)
         -> [logits_pos (B,L,V), logits_val (B,L,V)] (float32, on device)."""
-        self._sync_params()
-        idx = torch.as_tensor(idx).to(self.dev, torch.int32)
-        B, Lq, _ = idx.shape
-        assert Lq <= self.Lmax, "Cannot forward, model block size is exhausted."   # mingpt.py:279
-        st = dict(self._alloc(B, 1))
-        st["seq"] = torch.zeros(B, self.Lmax + 1, 2, device=self.dev, dtype=torch.int32)
-        st["seq"][:, :Lq] = idx
+        st, B, Lq = self._forward_state(idx, extra_idx, L_cond)
         if target_idx is not None:       # stage-1 input adds tok_embs[0][target pos] = seq[t+1][0]
             tgt = torch.as_tensor(target_idx).to(self.dev, torch.int32)
-            assert bool((tgt[:, :-1, 0] == idx[:, 1:, 0]).all()), "target_idx must be idx shifted left (shapeformer.py:37-41)"
+            assert bool((tgt[:, :-1, 0] == st["seq"][:, 1:Lq, 0]).all()), "target_idx must be idx shifted left (shapeformer.py:37-41)"
             st["seq"][:, Lq, 0] = tgt[:, -1, 0]
-        st["Lc"] = torch.full((B,), int(L_cond), device=self.dev, dtype=torch.int32)
-        st["len"] = torch.full((B,), Lq, device=self.dev, dtype=torch.int32)
-        st["nval"] = torch.full((B,), Lq, device=self.dev, dtype=torch.int32)
-        st["extra"] = None
-        st["rowoff"], st["M_packed"] = None, 0      # teacher-forced rows are a full (B,L) rectangle
-        if extra_idx is not None:
-            ex = torch.zeros(B, self.Lmax + 1, device=self.dev, dtype=torch.int32)
-            ex[:, :Lq] = torch.as_tensor(extra_idx).to(self.dev, torch.int32)[..., 0]
-            st["extra"] = ex
         return self.prefill(st, B, Lq, want_logits=True)
 
     __call__ = forward
@@ -535,25 +571,24 @@ class CondTupleGPT:
     SHARED_PREFIX_MIN_ROW_TOKENS = 2800      # rows x condition length from which the shared form is taken
     SINGLE_CHAIN_ROWS = 96  # `sample` keeps a batch in ONE chain up to here and interleaves chains above (a lone chain cannot overlap anything)
     # A row whose last position is the end token can only draw (end0, end1) from then on (mask_invalid: one finite logit per head,
-    # log-probability 0), yet it keeps stepping until ALL rows have ended (shapeformer.py:110-115).  True: such a row's KV cache is no
-    # longer streamed or appended to, its sampler writes the forced token without reading logits (st["alen"], csrc/gpt.hip SampleArgs::alen),
-    # and with SKIP_ENDED_GEMM a decode-GEMM row group without a live row does no work.  seq / len / logp are bit-identical either way.
-    # Armed only with mask_invalid, without logits history, teacher forcing or a timing ablation (those measure every row's stream).
+    # log-probability 0), yet it keeps stepping until ALL rows have ended (shapeformer.py:110-115).  The three switches below are the
+    # rungs of one ladder (`decode_level`: where they are armed, and what each level runs); seq / len / logp are bit-identical at
+    # every level.  SKIP_ENDED (level 1): such a row's KV cache is no longer streamed or appended to, its sampler writes the forced
+    # token without reading logits (st["alen"], csrc/gpt.hip SampleArgs::alen), and a decode-GEMM row group without a live row does
+    # no work.
     SKIP_ENDED = True
-    SKIP_ENDED_GEMM = True
-    # Ended rows are spread evenly over the 16-row tiles, so the group exit above acts only late in a run.  COMPACT_LIVE (with both
-    # knobs above, and armed where they are): at the head of every step the chain's live rows are packed into slots 0 .. nlive-1 of the
-    # activation buffers (resid, qkv, y, h, logit), in ascending row order, and the decode GEMMs run only the row tiles that hold a
-    # live slot (COMPACT_LIVE_TILES False: whole row groups).  seq, len, alen, Lc, logp and the KV caches stay indexed by row; the
-    # launch forms are chosen from the chain's rows as before, so every row's arithmetic - and seq / len / logp - is bit-identical.
+    # Ended rows are spread evenly over the 16-row tiles, so the group exit above acts only late in a run.  COMPACT_LIVE (level 2): at
+    # the head of every step the chain's live rows are packed into slots 0 .. nlive-1 of the activation buffers (resid, qkv, y, h,
+    # logit), in ascending row order, and the decode GEMMs run only the row tiles that hold a live slot.  seq, len, alen, Lc, logp and
+    # the KV caches stay indexed by row; the launch forms are chosen from the chain's rows as before, so every row's arithmetic is
+    # bit-identical.
     COMPACT_LIVE = True
-    COMPACT_LIVE_TILES = True
-    # The live count of a packed chain never grows, so a value the host read a few steps ago bounds every later step.  TILE_BUDGET (armed
-    # where COMPACT_LIVE_TILES is): `_prepare` captures one step graph per row-tile budget T = 1 .. ceil(B / 16), whose GEMM and attention
-    # launches are shaped for T row tiles (sfmi_decode_gemm_tiles_f32: the k-parts per workgroup stay those of the chain's B rows, so
-    # every row keeps its bits), and the loop replays, per block of TILE_BUDGET_EVERY steps, the graph of T = ceil(nlive / 16) of the
-    # live count copied to the host two blocks earlier (`tile_budget_policy`; one block always stays queued, the device never waits
-    # for the host).  A budget step whose compaction finds more live rows than it covers sets st["over"]: SfmiError at the next read.
+    # The live count of a packed chain never grows, so a value the host read a few steps ago bounds every later step.  TILE_BUDGET
+    # (level 3): `_step_graphs` captures one step graph per row-tile budget T = 1 .. ceil(B / 16), whose GEMM and attention launches
+    # are shaped for T row tiles (sfmi_decode_gemm_tiles_f32: the k-parts per workgroup stay those of the chain's B rows, so every
+    # row keeps its bits), and the loop replays, per block of TILE_BUDGET_EVERY steps, the graph of T = ceil(nlive / 16) of the live
+    # count copied to the host two blocks earlier (`tile_budget_policy`, `_Chain`; one block always stays queued, the device never
+    # waits for the host).  A budget step whose compaction finds more live rows than it covers sets st["over"]: SfmiError at the next read.
     # TILE_BUDGET_FORMS: the budgets that keep a graph of their own (None: all); any other budget replays the next larger one's.
     TILE_BUDGET = True
     TILE_BUDGET_EVERY = 8
@@ -561,103 +596,39 @@ class CondTupleGPT:
 
     def decode_step(self, st, B, sp, budget=0):
         """Position t = len[b]-1 of every row through both stages; st["resid"] must hold its embedding on entry
-        (written by the previous step's sampler tail, or by `_embed` before the first step).  budget > 0 (a packed chain with
-        live row tiles only): the step's launches cover the row tiles 0 .. budget-1."""
-        D = self.D
-        lib = L.lib()
-        r = st["resid"]
+        (written by the previous step's sampler tail, or by `_embed_step0` before the first step).  sp["level"] (`decode_level`) picks
+        every launch's form; budget > 0 (level 2 and up): the step's launches cover the row tiles 0 .. budget-1."""
+        D, r, level = self.D, st["resid"], int(sp.get("level", 0))
         skip = self._ablate                               # timing-only ablation hook (see __init__): results are garbage
         if "@" in skip:      # per-chain form "gemm@0,attn@1,attn@2": chain index = micro-batch slot
             skip = ",".join(t.split("@")[0] for t in skip.split(",") if int(t.split("@")[1]) == sp.get("chain", 0))
-        lanes = int(sp.get("gate_lanes", 0))
-        pa, pg = "attn" in self._profile, "gemm" in self._profile      # in-situ launch timing (results untouched)
+        pg = "gemm" in self._profile                      # in-situ launch timing (results untouched)
         # in-kernel split-K per GEMM (only the K = 4 n_embd product, and proj at <= 16 rows, use it)
         Sqkv, Sproj, Sfc1, Sfc2, Shead = 1, self.S_PROJ if B <= 16 else self.S_PROJ_M, 1, self.S_FC2, 1
-        armed = int(sp.get("skip_ended", 0))
-        # ended rows: the attention gets alen in its `len` slot (no new kernel argument), the GEMMs get it to drop all-ended row groups
-        alen_a = st["alen"] if armed else st["len"]
-        alen_g = st["alen"] if armed >= 2 else None
-        compact = int(sp.get("compact_live", 0))      # 0 = rows in place, 1 = packed + GEMM group exit, 2 = packed + live row tiles only
-        gk = dict(alen=alen_g)
-        Ba = B                                        # slots the decode attention walks
-        if compact >= 2 and budget:
-            gk = dict(nlive=st["nlive"], partial=1, tiles=int(budget))
-            Ba = min(B, 16 * int(budget))
-            L.check(lib.sfmi_gpt_compact_rows_budget_f32(L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.ptr(st["row_of"]), L.ptr(st["nlive"]),
-                                                         L.ptr(st["slot_len"]), L.ptr(st["emb"]), L.ptr(r), B, r.shape[0], D, int(budget),
-                                                         L.ptr(st["over"]), L.stream_ptr()), "sfmi_gpt_compact_rows_budget_f32")
-        elif budget:
+        if budget and level < 2:
             raise L.SfmiError("a row-tile budget needs a packed chain that runs live row tiles only")
-        elif compact:
-            gk = dict(nlive=st["nlive"], partial=int(compact >= 2))
-            L.check(lib.sfmi_gpt_compact_rows_f32(L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.ptr(st["row_of"]), L.ptr(st["nlive"]),
-                                                  L.ptr(st["slot_len"]), L.ptr(st["emb"]), L.ptr(r), B, r.shape[0], D, L.stream_ptr()),
-                    "sfmi_gpt_compact_rows_f32")
+        # the rows the decode GEMMs run: a packed chain's live row tiles (those of the budget); in place, from level 1 on, the row groups with a live row
+        rows = dict(nlive=st["nlive"], partial=1, tiles=int(budget)) if level >= 2 else dict(alen=st["alen"] if level else None)
+        if level >= 2:
+            self._compact(st, B, budget)
         for li, ly in enumerate(self.layers):
-            stage_end = li + 1 == len(self.layers) or self.layers[li + 1].stage != ly.stage
             if "gemm" not in skip:
-                self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg, **gk)
-            if "attn" not in skip and compact:
-                L.check(lib.sfmi_gpt_attn_decode_rows_f32(L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]),
-                                                          L.ptr(st["slot_len"]), L.ptr(st["row_of"]), L.ptr(st["y"]), Ba, D, self.H, self.Lmax + 1,
-                                                          L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
-                                                          L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
-                                                          L.ptr(st["prof"]) if pa else None, L.stream_ptr()), "sfmi_gpt_attn_decode_rows_f32")
-            elif "attn" not in skip:
-                L.check(lib.sfmi_gpt_attn_decode_gated_f32(L.ptr(st["qkv"]), L.ptr(st["Kc"][li]), L.ptr(st["Vc"][li]),
-                                                           L.ptr(alen_a), L.ptr(st["y"]), B, D, self.H, self.Lmax + 1,
-                                                           L.ptr(st["shared"]) if sp.get("shared_prefix") else None,
-                                                           L.ptr(self._sem) if lanes else None, L.ptr(st["blk"]) if (lanes or pa) else None, lanes,
-                                                           L.ptr(st["prof"]) if pa else None, L.stream_ptr()), "sfmi_gpt_attn_decode_gated_f32")
+                self._dgemm(r, ly.pqkv, ly.c1qkv, ly.c2qkv, None, st["qkv"], B, 3 * D, D, 3 * D, 1, 0, S=Sqkv, st=st, prof=pg, **rows)
+            if "attn" not in skip:
+                self._attn_decode(st, sp, li, B, level, budget)
             if "gemm" not in skip:
-                self._dgemm(st["y"], ly.pproj, None, ly.bproj, r, r, B, D, D, D, 0, 0, S=Sproj, st=st, prof=pg, **gk)
-                self._dgemm(r, ly.pfc1, ly.c1fc1, ly.c2fc1, None, st["h"], B, 4 * D, D, 4 * D, 1, 1, S=Sfc1, st=st, prof=pg, **gk)
-                self._dgemm(st["h"], ly.pfc2, None, ly.bfc2, r, r, B, D, 4 * D, D, 0, 0, S=Sfc2, st=st, prof=pg, **gk)
-            if stage_end:
-                s = ly.stage
-                hp, hc1, hc2 = self.head_f[s]
-                self._dgemm(r, hp, hc1, hc2, None, st["logit"], B, self.V, D, self.Vpad, 1, 0, packed=0, S=Shead, st=st, **gk)
-                hist = sp["hist"][s] if sp.get("hist") is not None else None
-                if compact:
-                    L.check(lib.sfmi_gpt_sample_rows_f32(L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
-                                                         L.ptr(st["logp"]), L.ptr(r), L.ptr(st["emb"]),
-                                                         L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), D,
-                                                         1, B, self.V, self.Vpad, self.Lmax + 1,
-                                                         s, self.end[0], self.end[1], sp["top_k"], sp["top_p"], sp["temperature"],
-                                                         int(sp["best_in_first"]), int(sp["mask_invalid_completion"]), sp["max_steps"],
-                                                         sp["seed"], L.ptr(st.get("seed")), int(s == 1),
-                                                         sp.get("row_offset", 0), sp.get("rows_total", B), int(sp.get("step_offset", 0)),
-                                                         L.ptr(st["alen"]), L.ptr(st["slot_of"]), L.stream_ptr()), "sfmi_gpt_sample_rows_f32")
-                    continue
-                L.check(lib.sfmi_gpt_sample_live_f32(L.ptr(st["logit"]), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
-                                                     L.ptr(st["logp"]), L.ptr(hist), L.ptr(sp.get("force")),
-                                                     L.ptr(r), L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb), D,
-                                                     1, B, self.V, self.Vpad, self.Lmax + 1,
-                                                     s, self.end[0], self.end[1], sp["top_k"], sp["top_p"], sp["temperature"],
-                                                     int(sp["best_in_first"]), int(sp["mask_invalid"]),
-                                                     int(sp["mask_invalid_completion"]), sp["max_steps"], sp["seed"], L.ptr(st.get("seed")), int(s == 1),
-                                                     sp.get("row_offset", 0), sp.get("rows_total", B), int(sp.get("step_offset", 0)),
-                                                     L.ptr(st["alen"]), int(bool(armed)), L.stream_ptr()), "sfmi_gpt_sample_live_f32")
+                self._dgemm(st["y"], ly.pproj, None, ly.bproj, r, r, B, D, D, D, 0, 0, S=Sproj, st=st, prof=pg, **rows)
+                self._dgemm(r, ly.pfc1, ly.c1fc1, ly.c2fc1, None, st["h"], B, 4 * D, D, 4 * D, 1, 1, S=Sfc1, st=st, prof=pg, **rows)
+                self._dgemm(st["h"], ly.pfc2, None, ly.bfc2, r, r, B, D, 4 * D, D, 0, 0, S=Sfc2, st=st, prof=pg, **rows)
+            if li + 1 == len(self.layers) or self.layers[li + 1].stage != ly.stage:      # stage end: head and sampler
+                hp, hc1, hc2 = self.head_f[ly.stage]
+                self._dgemm(r, hp, hc1, hc2, None, st["logit"], B, self.V, D, self.Vpad, 1, 0, packed=0, S=Shead, st=st, **rows)
+                self._sample_stage(st, sp, B, ly.stage, level)
 
     # ------------------------------------------------------------------ sample_indices
-    def _prepare(self, c_tokens, Lc, max_steps, sp_kw, slot=0, row_offset=0, rows_total=None, return_logits=False,
-                 force_tokens=None, use_graph=True, shared_prefix=False, z_tokens=None, gate_lanes=0):
-        """State + prefill + step-0 embedding + (cached) hipGraph of one decode step for one (micro-)batch.
-        z_tokens (B,L_z,2): tokens already generated after the condition (shapeformer.py:60-70 copies cat(c, z) into `sampled`):
-        they are prefilled together with the condition and sampling continues after them; the step counter restarts at 0."""
-        B = c_tokens.shape[0]
-        Lz = 0 if z_tokens is None else int(z_tokens.shape[1])
-        if B > self.MAX_CHAIN_ROWS:
-            raise L.SfmiError(f"a decode chain holds up to {self.MAX_CHAIN_ROWS} rows (larger batches run as several chains: sample / sample_microbatched)")
-        self._sync_params()
-        if getattr(self, "_decode_stale", False):
-            self.refresh_decode_weights()
-        Lc_host = Lc.cpu().tolist()
-        Lc_max = max(Lc_host)
-        if shared_prefix == "auto":      # the caller vouches for identical condition rows; shared only where it pays
-            shared_prefix = B * Lc_max >= self.SHARED_PREFIX_MIN_ROW_TOKENS
-        steps = min(max_steps, self.Lmax - Lc_max - Lz)   # never exceed block_size (DESIGN.md: stop, don't crop)
-        st = self._alloc(B, max_steps, slot)
+    def _reset_state(self, st, c_tokens, Lc, z_tokens, seed):
+        """The chain's rows at step 0: conditions (and z tokens) in seq, lengths, the identity slot map, cleared results."""
+        B, Lz = c_tokens.shape[0], 0 if z_tokens is None else int(z_tokens.shape[1])
         if self.TILE_BUDGET and int(st["over"].item()):      # the last run of this slot dropped live rows in a budget step
             st["over"].zero_()
             raise L.SfmiError("a decode step ran at a row-tile budget below its live rows (TILE_BUDGET): the last results of this chain are invalid")
@@ -669,7 +640,6 @@ class CondTupleGPT:
             pos = st["Lc"].long()[:, None] + torch.arange(Lz, device=self.dev)[None, :]
             st["seq"][torch.arange(B, device=self.dev)[:, None], pos] = torch.as_tensor(z_tokens).to(self.dev, torch.int32)
             st["len"].add_(Lz)
-            shared_prefix = False
         st["alen"].copy_(st["len"])
         # the identity map (a packed chain rebuilds it at the head of every step)
         st["slot_of"].copy_(torch.arange(B, device=self.dev, dtype=torch.int32))
@@ -679,25 +649,12 @@ class CondTupleGPT:
         st["slot_len"][:B] = st["len"]
         st["nlive"].fill_(B)
         st["logp"].zero_()
-        st["seed"].copy_(torch.from_numpy(np.array([sp_kw["seed"]], np.uint32).view(np.int32)))
-        hist = None
-        if return_logits:
-            hist = [torch.full((B, max_steps, self.V), float("nan"), device=self.dev) for _ in range(2)]
-        sp = dict(sp_kw, max_steps=int(max_steps), hist=hist, row_offset=int(row_offset),
-                  rows_total=int(rows_total if rows_total is not None else B), chain=int(slot - 100 if slot >= 100 else 0),
-                  shared_prefix=bool(shared_prefix), step_offset=Lz, gate_lanes=int(gate_lanes))
-        # ended rows are skipped (0 = no, 1 = attention + sampler, 2 = and the decode GEMMs' all-ended row groups) only where their tokens
-        # are forced and nobody looks at their logits; a launch-shape choice like the others: part of the graph-cache key through sp
-        sp["skip_ended"] = (2 if self.SKIP_ENDED_GEMM else 1) if (self.SKIP_ENDED and sp_kw["mask_invalid"] and not return_logits
-                                                                  and force_tokens is None and not self._ablate) else 0
-        sp["compact_live"] = (2 if self.COMPACT_LIVE_TILES else 1) if (self.COMPACT_LIVE and sp["skip_ended"] >= 2) else 0
-        # step graphs per row-tile budget: only where live row tiles are run at all (the timed GEMM launch has no such form: it runs every row)
-        sp["tile_budget"] = int(bool(self.TILE_BUDGET and sp["compact_live"] == 2 and "gemm" not in self._profile))
-        if force_tokens is not None:   # (B,max_steps,2) teacher forcing for stepwise parity tests
-            ft = torch.zeros(B, max_steps, 2, dtype=torch.int32)
-            ft[:, :force_tokens.shape[1]] = torch.as_tensor(force_tokens).to(torch.int32)
-            sp["force"] = ft.to(self.dev)
-            use_graph = False
+        st["seed"].copy_(torch.from_numpy(np.array([seed], np.uint32).view(np.int32)))
+
+    def _prefill_chain(self, st, B, Lc_host, Lz, shared_prefix, level):
+        """Prefill of the rows' conditions (and z tokens) up to the last token, which is step 0's input: its embedding goes where the
+        first decode step of a chain at `level` looks for it."""
+        Lc_max = max(Lc_host)
         P = Lc_max + Lz - 1
         st["nval"], st["extra"] = None, None
         if Lz:
@@ -720,53 +677,79 @@ class CondTupleGPT:
             st["rowoff"] = torch.tensor([0] + list(np.cumsum(nrow)), dtype=torch.int32).to(self.dev)
             if P > 0 and st["M_packed"] > 0:
                 self.prefill(st, B, P)
-        # embedding of the last condition token (step-0 input) into the fragment-packed residual buffer (a packed chain: into the
-        # row-major staging buffer, from where the head of the step moves it to the rows' slots)
-        if sp["compact_live"]:
-            L.check(L.lib().sfmi_gpt_embed_rows_f32(L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb),
-                                                    L.ptr(self.cond_pos_emb), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
-                                                    L.ptr(st["emb"]), B, self.D, self.Lmax + 1, self.end[0], L.stream_ptr()),
-                    "sfmi_gpt_embed_rows_f32")
-        else:
-            L.check(L.lib().sfmi_gpt_embed_packed_f32(L.ptr(self.E[0]), L.ptr(self.E[1]), L.ptr(self.Ex), L.ptr(self.pos_emb),
-                                                      L.ptr(self.cond_pos_emb), L.ptr(st["seq"]), L.ptr(st["len"]), L.ptr(st["Lc"]),
-                                                      L.ptr(st["resid"]), B, self.D, self.Lmax + 1, self.end[0], L.stream_ptr()),
-                    "sfmi_gpt_embed_packed_f32")
-        graph, graphs = None, None
-        if use_graph and steps > 1:
-            full = (B + 15) // 16
-            forms = tuple(sorted(set(self.TILE_BUDGET_FORMS))) if self.TILE_BUDGET_FORMS is not None else None
-            gkey = (B, tuple(sorted((k, v) for k, v in sp.items() if k not in ("hist", "force", "seed"))), return_logits,
-                    self._ablate, self._profile, self.S_PROJ, self.S_PROJ_M, self.S_FC2, forms,
-                    int(L.lib().sfmi_tune_generation()))      # launch-shape knobs are baked into a captured graph: re-capture when one changed
-            cached = self._graphs.get(slot)
-            if cached is None or cached[0] != gkey or return_logits:
-                side = torch.cuda.Stream(device=self.dev)
-                # (the guard word is saved with the rest: a small form warmed up on a full chain trips it)
-                saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid", "emb", "over")}
+        self._embed_step0(st, B, level)
 
-                def capture(budget):
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self.decode_step(st, B, sp, budget)      # warm-up outside capture
-                    torch.cuda.current_stream().wait_stream(side)
-                    torch.cuda.synchronize()
-                    for k, v in saved.items():
-                        st[k].copy_(v)
-                    g_ = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g_):
-                        self.decode_step(st, B, sp, budget)
-                    for k, v in saved.items():           # capture does not execute, but keep state pristine
-                        st[k].copy_(v)
-                    return g_
-                graph = capture(0)      # the full form first: it writes every row of the scratch buffers the smaller forms' warm-ups leave alone
-                by_budget = {full: graph}
-                if sp["tile_budget"]:
-                    for T in range(full - 1, 0, -1):      # a budget without a form of its own replays the next larger one's graph
-                        by_budget[T] = capture(T) if (forms is None or T in forms) else by_budget[T + 1]
-                self._graphs[slot] = (gkey, graph, by_budget)
-            graph = self._graphs[slot][1]
-            graphs = self._graphs[slot][2] if sp["tile_budget"] else None
+    def _step_graphs(self, st, B, sp, slot, return_logits):
+        """The slot's (cached) hipGraphs of one decode step: (the full form, {budget: graph} at level 3 or None)."""
+        full = (B + 15) // 16
+        forms = tuple(sorted(set(self.TILE_BUDGET_FORMS))) if self.TILE_BUDGET_FORMS is not None else None
+        gkey = (B, tuple(sorted((k, v) for k, v in sp.items() if k not in ("hist", "force", "seed"))), return_logits,
+                self._ablate, self._profile, self.S_PROJ, self.S_PROJ_M, self.S_FC2, forms,
+                int(L.lib().sfmi_tune_generation()))      # launch-shape knobs are baked into a captured graph: re-capture when one changed
+        cached = self._graphs.get(slot)
+        if cached is None or cached[0] != gkey or return_logits:
+            side = torch.cuda.Stream(device=self.dev)
+            # (the guard word is saved with the rest: a small form warmed up on a full chain trips it)
+            saved = {k: st[k].clone() for k in ("seq", "len", "alen", "logp", "resid", "emb", "over")}
+
+            def capture(budget):
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    self.decode_step(st, B, sp, budget)      # warm-up outside capture
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                for k, v in saved.items():
+                    st[k].copy_(v)
+                g_ = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_):
+                    self.decode_step(st, B, sp, budget)
+                for k, v in saved.items():           # capture does not execute, but keep state pristine
+                    st[k].copy_(v)
+                return g_
+            by_budget = {full: capture(0)}      # the full form first: it writes every row of the scratch buffers the smaller forms' warm-ups leave alone
+            if sp["level"] >= 3:
+                for T in range(full - 1, 0, -1):      # a budget without a form of its own replays the next larger one's graph
+                    by_budget[T] = capture(T) if (forms is None or T in forms) else by_budget[T + 1]
+            self._graphs[slot] = (gkey, by_budget[full], by_budget)
+        _, graph, by_budget = self._graphs[slot]
+        return graph, by_budget if sp["level"] >= 3 else None
+
+    def _prepare(self, c_tokens, Lc, max_steps, sp_kw, slot=0, row_offset=0, rows_total=None, return_logits=False,
+                 force_tokens=None, use_graph=True, shared_prefix=False, z_tokens=None, gate_lanes=0):
+        """State + prefill + step-0 embedding + (cached) hipGraph of one decode step for one (micro-)batch.
+        z_tokens (B,L_z,2): tokens already generated after the condition (shapeformer.py:60-70 copies cat(c, z) into `sampled`):
+        they are prefilled together with the condition and sampling continues after them; the step counter restarts at 0."""
+        B = c_tokens.shape[0]
+        Lz = 0 if z_tokens is None else int(z_tokens.shape[1])
+        if B > self.MAX_CHAIN_ROWS:
+            raise L.SfmiError(f"a decode chain holds up to {self.MAX_CHAIN_ROWS} rows (larger batches run as several chains: sample / sample_microbatched)")
+        self._sync_params()
+        if getattr(self, "_decode_stale", False):
+            self.refresh_decode_weights()
+        Lc_host = Lc.cpu().tolist()
+        Lc_max = max(Lc_host)
+        if shared_prefix == "auto":      # the caller vouches for identical condition rows; shared only where it pays
+            shared_prefix = B * Lc_max >= self.SHARED_PREFIX_MIN_ROW_TOKENS
+        shared_prefix = bool(shared_prefix) and not Lz
+        steps = min(max_steps, self.Lmax - Lc_max - Lz)   # never exceed block_size (DESIGN.md: stop, don't crop)
+        st = self._alloc(B, max_steps, slot)
+        self._reset_state(st, c_tokens, Lc, z_tokens, sp_kw["seed"])
+        hist = None
+        if return_logits:
+            hist = [torch.full((B, max_steps, self.V), float("nan"), device=self.dev) for _ in range(2)]
+        # the level is a launch-shape choice like the others: part of the graph-cache key through sp
+        sp = dict(sp_kw, max_steps=int(max_steps), hist=hist, row_offset=int(row_offset),
+                  rows_total=int(rows_total if rows_total is not None else B), chain=int(slot - 100 if slot >= 100 else 0),
+                  shared_prefix=shared_prefix, step_offset=Lz, gate_lanes=int(gate_lanes),
+                  level=decode_level(sp_kw["mask_invalid"], return_logits, force_tokens, self._ablate, self._profile,
+                                     self.SKIP_ENDED, self.COMPACT_LIVE, self.TILE_BUDGET))
+        if force_tokens is not None:   # (B,max_steps,2) teacher forcing for stepwise parity tests
+            ft = torch.zeros(B, max_steps, 2, dtype=torch.int32)
+            ft[:, :force_tokens.shape[1]] = torch.as_tensor(force_tokens).to(torch.int32)
+            sp["force"] = ft.to(self.dev)
+            use_graph = False
+        self._prefill_chain(st, B, Lc_host, Lz, shared_prefix, sp["level"])
+        graph, graphs = self._step_graphs(st, B, sp, slot, return_logits) if use_graph and steps > 1 else (None, None)
         return dict(st=st, sp=sp, B=B, steps=steps, graph=graph, graphs=graphs, budget_log=[], hist=hist, Lc_host=Lc_host, Lz=Lz)
 
     @staticmethod
@@ -792,51 +775,69 @@ class CondTupleGPT:
         Returns dict(samples (B,L_z+steps,2) int64, log_prob (B,steps,2), steps, [logits_history]).
         Mirrors ShapeFormer.sample_indices (shapeformer.py:54-123); torch.multinomial is replaced by an
         inverse-CDF draw on counter-hash uniforms (oracle/gpt_oracle.py:uniforms)."""
+        o = dict(sp_kw=self._sp(top_k, top_p, temperature, best_in_first, mask_invalid, mask_invalid_completion, seed),
+                 max_steps=max_steps, stop_early=stop_early, check_every=check_every, after_prefill=after_prefill,
+                 return_logits=return_logits, force_tokens=force_tokens, shared_prefix=shared_prefix, z_tokens=z_tokens,
+                 use_graph=use_graph, row0=int(row_offset), rows_total=rows_total, ended_reduce=ended_reduce)
         if c_tokens.shape[0] > self.SINGLE_CHAIN_ROWS:
             # more rows than one chain should hold: the same rows as interleaved chains (identical tokens - uniforms and the
             # greedy row are indexed by global row), results gathered as for one chain
             n_micro = min(4, -(-c_tokens.shape[0] // 80))      # up to 4 chains; a chain holds up to MAX_CHAIN_ROWS (192) rows, so one round
                                                                # takes 768 rows (measured best: 4 x 96); beyond that: successive rounds
-            r = self.sample_microbatched(c_tokens, Lc, n_micro=n_micro, max_steps=max_steps, top_k=top_k, top_p=top_p, temperature=temperature,
-                                         best_in_first=best_in_first, mask_invalid=mask_invalid, mask_invalid_completion=mask_invalid_completion,
-                                         seed=seed, stop_early=stop_early, check_every=check_every, after_prefill=after_prefill,
-                                         return_logits=return_logits, force_tokens=force_tokens, shared_prefix=shared_prefix,
-                                         z_tokens=z_tokens, use_graph=use_graph, _row0=int(row_offset), _rows_total=rows_total,
-                                         ended_reduce=ended_reduce)
+            r = self._sample_chains(c_tokens, Lc, n_micro, o)
             if not to_host:
                 return r
             Lz = 0 if z_tokens is None else int(z_tokens.shape[1])
             return self._host_result(r["state"], Lc.cpu().tolist(), Lz, r.get("logits_history"))
-        sp_kw = self._sp(top_k, top_p, temperature, best_in_first, mask_invalid, mask_invalid_completion, seed)
-        ctx = self._prepare(c_tokens, Lc, max_steps, sp_kw, return_logits=return_logits, force_tokens=force_tokens,
-                            use_graph=use_graph, shared_prefix=shared_prefix, z_tokens=z_tokens, row_offset=int(row_offset),
+        ctx = self._prepare(c_tokens, Lc, max_steps, o["sp_kw"], return_logits=return_logits, force_tokens=force_tokens,
+                            use_graph=use_graph, shared_prefix=shared_prefix, z_tokens=z_tokens, row_offset=o["row0"],
                             rows_total=rows_total)
-        ended = (lambda: self._all_ended(st, B)) if ended_reduce is None else (lambda: bool(ended_reduce(self._all_ended(st, B))))
-        st, sp, B, steps, g, hist, Lc_host = (ctx[k] for k in ("st", "sp", "B", "steps", "graph", "hist", "Lc_host"))
         if after_prefill is not None:
             after_prefill()
-        done = 0
-        if g is not None:
-            fb = _BudgetFeedback(self, [ctx], [torch.cuda.current_stream()])
-            while done < steps:
-                n = min(check_every, steps - done) if stop_early else steps - done
-                for _ in range(n):
-                    fb.graphs(done)[0].replay()
-                    fb.stepped(done)
-                    done += 1
-                if stop_early and ended():
-                    break
-        else:
-            while done < steps:
-                self.decode_step(st, B, sp)
-                done += 1
-                # the same check points as the graph loop and sample_microbatched: every check_every steps AND after the last step (a
-                # caller's ended_reduce is a collective: every process must reach it the same number of times whatever loop it runs)
-                if stop_early and (done % check_every == 0 or done == steps) and ended():
-                    break
+        done = self._run_chains([ctx], [torch.cuda.current_stream()], stop_early, check_every, ended_reduce)
         if not to_host:   # device-resident result for the completion pipeline (no D2H of tokens)
-            return dict(state=st, steps=done)
-        return self._host_result(st, Lc_host, ctx["Lz"], hist)
+            return dict(state=ctx["st"], steps=done)
+        return self._host_result(ctx["st"], ctx["Lc_host"], ctx["Lz"], ctx["hist"])
+
+    def _run_chains(self, ctxs, streams, stop_early, check_every, ended_reduce):
+        """THE decode loop: the prepared chains `ctxs` step side by side, chain i on streams[i] (its step graph of the block's budget,
+        or `decode_step` where it has none), until every row has ended or the shortest chain's steps are through.  Returns the steps
+        done.  The early stop is checked every `check_every` steps AND after the last step, whatever the chains replay: a caller's
+        ended_reduce is a collective, every process must reach it the same number of times.  A chain on the caller's stream is
+        enqueued there as it is: no stream switch, no wait."""
+        cur = torch.cuda.current_stream()
+        chains = [_Chain(c, s, s != cur) for c, s in zip(ctxs, streams)]
+        budgeted = [ch for ch in chains if ch.by_budget is not None]
+        self.last_budget_log = [c["budget_log"] for c in ctxs]      # the last run's budgets per chain and block (tests, records)
+        every = max(1, int(self.TILE_BUDGET_EVERY))
+        on_step = getattr(self, "_on_step", None)      # measurement hook (tools/ar_sweep.py bins): called after every step's enqueue
+        steps, done = min(c["steps"] for c in ctxs), 0
+        while done < steps:
+            n = min(check_every, steps - done) if stop_early else steps - done
+            for _ in range(n):
+                if done % every == 0:
+                    for ch in budgeted:
+                        ch.choose(done // every)
+                for ch in chains:
+                    with ch.scope():
+                        if ch.graph is not None:
+                            ch.graph.replay()
+                        else:
+                            self.decode_step(ch.ctx["st"], ch.ctx["B"], ch.ctx["sp"])
+                if (done + 1) % every == 0:
+                    for ch in budgeted:
+                        ch.report(done // every)
+                done += 1
+                if on_step is not None:
+                    on_step(done, streams)
+            if stop_early:
+                for ch in chains:
+                    if ch.own_stream:
+                        cur.wait_stream(ch.stream)
+                e_ = all(self._all_ended(c["st"], c["B"]) for c in ctxs)
+                if (e_ if ended_reduce is None else bool(ended_reduce(e_))):
+                    break
+        return done
 
     def _host_result(self, st, Lc_host, Lz, hist):
         """Device state -> the host-side result dict of `sample` (tokens after each row's condition, the z prefix included)."""
@@ -926,55 +927,69 @@ class CondTupleGPT:
         indexed by GLOBAL row), but the rows are split into `n_micro` independent micro-batches whose decode steps are
         separate hipGraphs replayed on separate HIP streams: one micro-batch's HBM-bound attention overlaps the other's
         MFMA-bound GEMMs (each chain is serial, the hardware interleaves the two)."""
+        o = dict(sp_kw=self._sp(top_k, top_p, temperature, best_in_first, mask_invalid, mask_invalid_completion, seed),
+                 max_steps=max_steps, stop_early=stop_early, check_every=check_every, after_prefill=after_prefill,
+                 return_logits=return_logits, force_tokens=force_tokens, shared_prefix=shared_prefix, z_tokens=z_tokens,
+                 use_graph=use_graph, row0=_row0, rows_total=_rows_total, ended_reduce=ended_reduce)
+        return self._sample_chains(c_tokens, Lc, n_micro, o)
+
+    def _sample_rounds(self, c_tokens, Lc, n_micro, o):
+        """More rows than n_micro chains hold: successive rounds of the same shape (rows keep their global index).  `o`: the
+        call's options; a round changes its rows, step count and early stop, and only the first calls after_prefill.  The rounds
+        take no part in a caller's ended_reduce."""
         B = c_tokens.shape[0]
-        rows_total = B if _rows_total is None else _rows_total
-        cap = n_micro * self.MAX_CHAIN_ROWS
-        if B > cap:      # more rows than n_micro chains hold: successive rounds of the same shape (rows keep their global index)
-            nr = -(-B // cap)
-            rb = [round(i * B / nr) for i in range(nr + 1)]
-            sl = lambda t, lo, hi: None if t is None else torch.as_tensor(t)[lo:hi]
-            def round_(lo, hi, steps, early):
-                return self.sample_microbatched(c_tokens[lo:hi], Lc[lo:hi], n_micro=n_micro, max_steps=steps, top_k=top_k, top_p=top_p,
-                                                temperature=temperature, best_in_first=best_in_first, mask_invalid=mask_invalid,
-                                                mask_invalid_completion=mask_invalid_completion, seed=seed, stop_early=early,
-                                                check_every=check_every, after_prefill=after_prefill if lo == 0 else None,
-                                                return_logits=return_logits, force_tokens=sl(force_tokens, lo, hi), shared_prefix=shared_prefix,
-                                                z_tokens=sl(z_tokens, lo, hi), use_graph=use_graph, _row0=_row0 + lo, _rows_total=rows_total)
-            spans = list(zip(rb[:-1], rb[1:]))
-            parts = [round_(lo, hi, max_steps, stop_early) for lo, hi in spans]
-            # the rounds stop early independently; a single run (shapeformer.py:110-115) keeps stepping every row until ALL rows have
-            # ended.  A row whose last POSITION is the end token can only draw end-token pairs from then on (the position masks leave
-            # nothing else, log-probability 0): a round that stopped sooner and holds only such rows is padded with exactly those
-            # tokens.  A row that "ended" by drawing the end VALUE at a real position is not forced to end tokens (and nothing is with
-            # mask_invalid off): such a round is re-run for the longest round's step count without the early stop - rows keep their
-            # global index and uniforms, so this is what the single run draws for them.
-            nmax = max(p["steps"] for p in parts)
-            for i, (lo, hi) in enumerate(spans):
-                p_ = parts[i]
-                short = nmax - p_["steps"]
-                if short <= 0:
-                    continue
-                stp = p_["state"]
-                last = stp["seq"][torch.arange(stp["len"].shape[0], device=self.dev), (stp["len"].long() - 1).clamp(min=0), 0]
-                full = stp["len"] >= self.Lmax           # the block is full: nothing more is drawn for this row in a single run either
-                if mask_invalid and bool(((last == self.end[0]) | full).all()):
-                    room = (self.Lmax - stp["len"]).clamp(min=0, max=short).long()
-                    pos = stp["len"].long()[:, None] + torch.arange(short, device=self.dev)[None, :]
-                    ok = torch.arange(short, device=self.dev)[None, :] < room[:, None]
-                    rows = torch.arange(stp["len"].shape[0], device=self.dev)[:, None].expand_as(pos)
-                    stp["seq"][rows[ok], pos[ok]] = torch.tensor(self.end, device=self.dev, dtype=torch.int32)
-                    stp["len"] = stp["len"] + room.to(torch.int32)
-                    if return_logits:      # the padded steps drew from a one-candidate distribution; their logits rows stay zero
-                        p_["logits_history"] = [torch.cat([h, h.new_zeros(h.shape[0], short, h.shape[2])], 1) for h in p_["logits_history"]]
-                else:
-                    parts[i] = round_(lo, hi, nmax, False)
-            res = dict(state={k: torch.cat([p["state"][k] for p in parts], 0) for k in parts[0]["state"]}, steps=nmax)
-            if return_logits:
-                res["logits_history"] = [torch.cat([p["logits_history"][i] for p in parts], 0) for i in range(2)]
-            return res
+        nr = -(-B // (n_micro * self.MAX_CHAIN_ROWS))
+        rb = [round(i * B / nr) for i in range(nr + 1)]
+        sl = lambda t, lo, hi: None if t is None else torch.as_tensor(t)[lo:hi]
+        def round_(lo, hi, steps, early):
+            return self._sample_chains(c_tokens[lo:hi], Lc[lo:hi], n_micro,
+                                       dict(o, max_steps=steps, stop_early=early, after_prefill=o["after_prefill"] if lo == 0 else None,
+                                            force_tokens=sl(o["force_tokens"], lo, hi), z_tokens=sl(o["z_tokens"], lo, hi),
+                                            row0=o["row0"] + lo, ended_reduce=None))
+        mask_invalid, return_logits = o["sp_kw"]["mask_invalid"], o["return_logits"]
+        spans = list(zip(rb[:-1], rb[1:]))
+        parts = [round_(lo, hi, o["max_steps"], o["stop_early"]) for lo, hi in spans]
+        # the rounds stop early independently; a single run (shapeformer.py:110-115) keeps stepping every row until ALL rows have
+        # ended.  A row whose last POSITION is the end token can only draw end-token pairs from then on (the position masks leave
+        # nothing else, log-probability 0): a round that stopped sooner and holds only such rows is padded with exactly those
+        # tokens.  A row that "ended" by drawing the end VALUE at a real position is not forced to end tokens (and nothing is with
+        # mask_invalid off): such a round is re-run for the longest round's step count without the early stop - rows keep their
+        # global index and uniforms, so this is what the single run draws for them.
+        nmax = max(p["steps"] for p in parts)
+        for i, (lo, hi) in enumerate(spans):
+            p_ = parts[i]
+            short = nmax - p_["steps"]
+            if short <= 0:
+                continue
+            stp = p_["state"]
+            last = stp["seq"][torch.arange(stp["len"].shape[0], device=self.dev), (stp["len"].long() - 1).clamp(min=0), 0]
+            full = stp["len"] >= self.Lmax           # the block is full: nothing more is drawn for this row in a single run either
+            if mask_invalid and bool(((last == self.end[0]) | full).all()):
+                room = (self.Lmax - stp["len"]).clamp(min=0, max=short).long()
+                pos = stp["len"].long()[:, None] + torch.arange(short, device=self.dev)[None, :]
+                ok = torch.arange(short, device=self.dev)[None, :] < room[:, None]
+                rows = torch.arange(stp["len"].shape[0], device=self.dev)[:, None].expand_as(pos)
+                stp["seq"][rows[ok], pos[ok]] = torch.tensor(self.end, device=self.dev, dtype=torch.int32)
+                stp["len"] = stp["len"] + room.to(torch.int32)
+                if return_logits:      # the padded steps drew from a one-candidate distribution; their logits rows stay zero
+                    p_["logits_history"] = [torch.cat([h, h.new_zeros(h.shape[0], short, h.shape[2])], 1) for h in p_["logits_history"]]
+            else:
+                parts[i] = round_(lo, hi, nmax, False)
+        res = dict(state={k: torch.cat([p["state"][k] for p in parts], 0) for k in parts[0]["state"]}, steps=nmax)
+        if return_logits:
+            res["logits_history"] = [torch.cat([p["logits_history"][i] for p in parts], 0) for i in range(2)]
+        return res
+
+    def _sample_chains(self, c_tokens, Lc, n_micro, o):
+        """`sample_microbatched` on the call's options `o`: the rows as n_micro interleaved chains, each prepared on its own stream."""
+        B = c_tokens.shape[0]
+        if o["rows_total"] is None:
+            o = dict(o, rows_total=B)
+        if B > n_micro * self.MAX_CHAIN_ROWS:
+            return self._sample_rounds(c_tokens, Lc, n_micro, o)
+        sl = lambda t, lo, hi: None if t is None else torch.as_tensor(t)[lo:hi]
         bounds = [round(i * B / n_micro) for i in range(n_micro + 1)]
         groups = [(bounds[i], bounds[i + 1]) for i in range(n_micro) if bounds[i + 1] > bounds[i]]
-        sp_kw = self._sp(top_k, top_p, temperature, best_in_first, mask_invalid, mask_invalid_completion, seed)
         streams = self._chain_streams(len(groups))
         cur = torch.cuda.current_stream()
         # attention turnstile (ATTN_LANES): only when every chain owns a hardware queue - a gate kernel spinning at the head of a
@@ -987,11 +1002,10 @@ class CondTupleGPT:
         for i, (lo, hi) in enumerate(groups):
             streams[i].wait_stream(cur)
             with torch.cuda.stream(streams[i] if self.PREFILL_ON_CHAIN_STREAMS else cur):
-                ctxs.append(self._prepare(c_tokens[lo:hi], Lc[lo:hi], max_steps, sp_kw, slot=100 + i, row_offset=_row0 + lo, rows_total=rows_total,
-                                          return_logits=return_logits, gate_lanes=lanes, use_graph=use_graph, shared_prefix=shared_prefix,
-                                          force_tokens=None if force_tokens is None else torch.as_tensor(force_tokens)[lo:hi],
-                                          z_tokens=None if z_tokens is None else torch.as_tensor(z_tokens)[lo:hi]))
-        steps = min(c["steps"] for c in ctxs)
+                ctxs.append(self._prepare(c_tokens[lo:hi], Lc[lo:hi], o["max_steps"], o["sp_kw"], slot=100 + i, row_offset=o["row0"] + lo,
+                                          rows_total=o["rows_total"], return_logits=o["return_logits"], gate_lanes=lanes, use_graph=o["use_graph"],
+                                          shared_prefix=o["shared_prefix"], force_tokens=sl(o["force_tokens"], lo, hi),
+                                          z_tokens=sl(o["z_tokens"], lo, hi)))
         if lanes:                      # re-arm the turnstile while nothing of the decode loop is in flight
             for s in streams:
                 cur.wait_stream(s)
@@ -1000,40 +1014,18 @@ class CondTupleGPT:
                 c["st"]["blk"].zero_()
             for s in streams:
                 s.wait_stream(cur)
-        if after_prefill is not None:
+        if o["after_prefill"] is not None:
             for s in streams:
                 cur.wait_stream(s)
-            after_prefill()
+            o["after_prefill"]()
             for s in streams:
                 s.wait_stream(cur)
-        done = 0
-        fb = _BudgetFeedback(self, ctxs, streams)
-        on_step = getattr(self, "_on_step", None)      # measurement hook (tools/ar_sweep.py bins): called after every step's enqueue
-        while done < steps:
-            n = min(check_every, steps - done) if stop_early else steps - done
-            for _ in range(n):
-                gs = fb.graphs(done)
-                for c, s, g_ in zip(ctxs, streams, gs):
-                    with torch.cuda.stream(s):
-                        if g_ is not None:
-                            g_.replay()
-                        else:
-                            self.decode_step(c["st"], c["B"], c["sp"])
-                fb.stepped(done)
-                done += 1
-                if on_step is not None:
-                    on_step(done, streams)
-            if stop_early:
-                for s in streams:
-                    cur.wait_stream(s)
-                e_ = all(self._all_ended(c["st"], c["B"]) for c in ctxs)
-                if (e_ if ended_reduce is None else bool(ended_reduce(e_))):
-                    break
+        done = self._run_chains(ctxs, streams, o["stop_early"], o["check_every"], o["ended_reduce"])
         for s in streams:
             cur.wait_stream(s)
         merged = {k: torch.cat([c["st"][k] for c in ctxs], 0) for k in ("seq", "len", "Lc", "logp")}
         res = dict(state=merged, steps=done)
-        if return_logits:     # masked-logit history of every row, (B, max_steps, V) x 2 (parity tests of the chain interleave)
+        if o["return_logits"]:     # masked-logit history of every row, (B, max_steps, V) x 2 (parity tests of the chain interleave)
             res["logits_history"] = [torch.cat([c["hist"][i] for c in ctxs], 0) for i in range(2)]
         return res
 

@@ -1,6 +1,6 @@
 """CondTupleGPT.TILE_BUDGET without a GPU: the policy that turns lagging live counts into row-tile budgets
-(shapeformer_amd.gpt.tile_budget_policy), and the precondition it rests on - a chain's live count never grows - asserted on the CPU
-oracle's tokens for every case tests/test_tile_budget_gpu.py runs."""
+(shapeformer_amd.gpt.tile_budget_policy), the precondition it rests on - a chain's live count never grows - asserted on the CPU
+oracle's tokens for every case tests/test_tile_budget_gpu.py runs, and the ladder that arms it (shapeformer_amd.gpt.decode_level)."""
 import os
 import sys
 
@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import skip_ended_ref as R                       # noqa: E402
 import test_compact_live_gpu as C                # noqa: E402  (the cases and their cached oracle tokens; nothing there touches a GPU on import)
-from shapeformer_amd.gpt import tile_budget_policy      # noqa: E402
+from shapeformer_amd.gpt import decode_level, tile_budget_policy      # noqa: E402
 
 LOOP_CASES = ("scatter96", "one_live96", "fill16", "spill17", "all_end32", "chains2x96")
 
@@ -81,3 +81,32 @@ def test_reference_live_count_never_grows(case):
         assert (np.diff(live_at_head) <= 0).all(), case
         fe = R.first_end_step(tok[sl])
         assert np.array_equal(live_at_head, [int((fe >= j).sum()) for j in range(R.STEPS)])
+
+
+# decode_level, written out.  One string per (SKIP_ENDED, COMPACT_LIVE, TILE_BUDGET) and _profile; its 16 digits are the levels of the
+# calls numbered 8 * mask_invalid + 4 * return_logits + 2 * (force_tokens given) + (an ablation set): only call 8 - masked, nobody looks
+# at logits, nothing forced, nothing ablated - ever leaves level 0.  Packing needs the skip, budgets need the packing, and the timed GEMM
+# launch ("gemm" in _profile) keeps budgets off.
+PROFILES = ("", "attn", "attn,gemm")
+LEVELS = {
+    (False, False, False): ("0000000000000000", "0000000000000000", "0000000000000000"),
+    (False, False, True): ("0000000000000000", "0000000000000000", "0000000000000000"),
+    (False, True, False): ("0000000000000000", "0000000000000000", "0000000000000000"),
+    (False, True, True): ("0000000000000000", "0000000000000000", "0000000000000000"),
+    (True, False, False): ("0000000010000000", "0000000010000000", "0000000010000000"),
+    (True, False, True): ("0000000010000000", "0000000010000000", "0000000010000000"),
+    (True, True, False): ("0000000020000000", "0000000020000000", "0000000020000000"),
+    (True, True, True): ("0000000030000000", "0000000030000000", "0000000020000000"),
+}
+
+
+def test_decode_level_table():
+    assert len(LEVELS) == 8
+    for switches, rows in LEVELS.items():
+        for profile, row in zip(PROFILES, rows):
+            for call in range(16):
+                mask, logits, forced, ablated = (bool(call >> s & 1) for s in (3, 2, 1, 0))
+                force = np.zeros((1, 1, 2), np.int64) if forced else None
+                for ablate in (("gemm", "attn", "attn@1", "gemm@0,attn@1") if ablated else ("",)):      # any ablation, whole or per chain
+                    got = decode_level(mask, logits, force, ablate, profile, *switches)
+                    assert got == int(row[call]), (switches, profile, call, ablate, got)

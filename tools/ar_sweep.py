@@ -8,8 +8,8 @@ with HIP events, optionally with one kernel family disabled (timing-only ablatio
 A configuration line is `name key=value ...`; keys: the sfmi_tune_set knobs (attn_blocks, attn_unroll, attn_waves,
 attn_lds_pad, ...), `ablate=gemm|attn`, `rows=`, `chains=`, `lanes=` (gpt.ATTN_LANES: attention turnstile, at most that many
 chains stream their KV cache at a time), `prefetch=` (gpt.PREFETCH_BLOCKS: Infinity-Cache weight prefetch branch of a single chain),
-`skip=0|1|2` (gpt.SKIP_ENDED / SKIP_ENDED_GEMM: rows that have ended are not skipped / skipped by attention and sampler / also by the
-decode GEMMs' all-ended row groups; default 2 = the product), `profile=attn,gemm` (in-situ launch timing: prints launches and mean us per family), `cus=<n>` (every chain on a stream restricted to
+`skip=0|1` (gpt.SKIP_ENDED: rows that have ended keep running / are skipped, as far as gpt.COMPACT_LIVE and `budget=` take it -
+gpt.decode_level; default 1 = the product), `profile=attn,gemm` (in-situ launch timing: prints launches and mean us per family), `cus=<n>` (every chain on a stream restricted to
 the first n compute-unit mask bits = n / 8 CUs of every XCD; hipExtStreamCreateWithCUMask), `cusplit=<n>` (chains 0, 1 on the first n
 bits, chains 2, 3 on the other 256 - n: spatial partition of the two kernel families together with a per-chain ablate=),
 `cumode=block` (mask bits taken as contiguous blocks instead: bits [0, n) vs [n, 256)), `hwid=1` (print which XCC / SE / CU the masked
@@ -183,8 +183,7 @@ def main():
         gpt.ATTN_LANES = int(kv.pop("lanes", "0"))
         gpt.S_PROJ_M, gpt.S_FC2 = int(kv.pop("sproj", "1")), int(kv.pop("sfc2", "4"))      # in-kernel split-K of proj / fc2 (part of the graph key)
         gpt._profile = kv.pop("profile", "")
-        skip = int(kv.pop("skip", "2"))      # ended rows: 0 = every row keeps streaming, 1 = attention + sampler skip them, 2 = and the GEMMs' all-ended row groups
-        gpt.SKIP_ENDED, gpt.SKIP_ENDED_GEMM = skip > 0, skip > 1
+        gpt.SKIP_ENDED = kv.pop("skip", "1") != "0"      # ended rows: 0 = every row keeps running (gpt.decode_level 0)
         gpt.TILE_BUDGET, gpt.TILE_BUDGET_EVERY = kv.pop("budget", "1") != "0", int(kv.pop("every", "8"))
         forms_ = kv.pop("forms", None)
         gpt.TILE_BUDGET_FORMS = None if forms_ is None else tuple(int(v) for v in forms_.split(",") if v)
