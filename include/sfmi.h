@@ -678,6 +678,65 @@ int sfmi_simplify_solve_f32(const float* verts, const int* faces, const int* vof
 int sfmi_simplify_emit_i32(const int* faces, const int* voff, const int* toff, const int* vslot, const unsigned char* surv, const int* sincl,
                            const int* coff, int B, int T, int nS, int* out, void* stream);
 
+/* ---- Mesh connected components (csrc/components.hip): labels, per-component statistics and compaction, so that the
+ *      floaters a wrong token leaves next to a completion can be counted and dropped where the mesh is.  The reference has a stub for the
+ *      step: xgutils/geoutil.py:151-163 (filterMesh, a vertex-mask filter with "# TODO filterF").
+ * CONTRACT
+ *   Input     a ragged batch of indexed meshes as in the decimation section: verts (V,3) f32, faces (T,3) int32 with indices local per
+ *             shape, voff / toff (B+1) int32 [device] exclusive offsets (voff[B] == V, toff[B] == T).
+ *   Connected two vertices of a shape are connected if one face names both; components are the classes of the transitive closure over the
+ *             vertices that some face names.  A degenerate face (a, a, b) still connects a and b.  Faces never connect across shapes.
+ *   Labels    a vertex that no face names belongs to no component: label -1.  The components of a shape are numbered 0 .. C_b-1 in
+ *             ascending order of their smallest vertex index, so the labels are a function of the mesh alone.  A face carries the label
+ *             of its first index.  Batch-wide, component c of shape b has id coff[b] + c (coff (B+1): exclusive counts per shape).
+ *   Stats     per component, in id order: n_vert, n_face int32; area = sum |(b-a) x (c-a)| / 2 and volume = sum a . (b x c) / 6 (signed)
+ *             in f64 from the f32 vertices, without fused multiply-adds (numpy f64 gives the same terms).
+ *   Order of the sums  the faces are STABLY sorted by batch-wide component id; a component's run is cut into chunks of sfmi_cc_chunk()
+ *             faces counted from the run's own start; in a chunk lane l of a wave64 adds entries l, l+64, ... in that order and the lanes
+ *             are added by the xor butterfly 32, 16, .., 1; the chunk sums are added the same way (lane l: chunks l, l+64, ...).
+ *   Keep      given a flag per batch-wide component: the vertices whose component is kept, in input order (unreferenced vertices are
+ *             dropped), and the faces whose component is kept, in input order, re-indexed to the new local vertex numbers.  Slots come
+ *             from exclusive prefix counts; nothing allocates with an atomic.
+ *   Status    per shape: 0 ok; 1 no vertices; 2 a face index outside [0, V_b); 3 a non-finite vertex (the lowest code that applies).  A shape
+ *             with status != 0 has zero components, labels -1 throughout and yields no vertices and no faces.
+ *   Determinism  the union-find keeps parent[v] <= v and links only by compare-and-swap on a root's slot, so the root of a finished tree is
+ *             its smallest index in whatever order the faces arrive; integer atomics only; no floating-point atomics: bit-identical from
+ *             run to run, and a shape's output depends on that shape only (a batch equals per-shape calls bitwise).
+ * The launches are init, hook, flatten, number, stats, mark, emit, with prefix sums and one stable sort between them; their number does
+ * not depend on the mesh.  nC is the CAPACITY of the component tables (any value above the number of components: min(V, T) + 1 always
+ * is), so that no size has to reach the host between the passes.  Every entry returns SFMI_EINVAL before any launch for a NULL pointer
+ * it would use, B <= 0, a negative count or V + T + B >= 2^31. */
+/* faces per chunk of the statistics' sums (1024) */
+int sfmi_cc_chunk(void);
+/* clears flags and ref; parent[v] = v (batch-wide indices); flags (B): bit 0 no vertices, bit 1 a bad face index, bit 2 a non-finite
+ * vertex.  ref (V) uint8 */
+int sfmi_cc_init_f32(const float* verts, const int* faces, const int* voff, const int* toff, int B, int V, int T, int* parent,
+                     unsigned char* ref, int* flags, void* stream);
+/* one thread per face of the unflagged shapes: ref = 1 at its corners, its corners' trees linked */
+int sfmi_cc_hook_i32(const int* faces, const int* voff, const int* toff, const int* flags, int B, int V, int T, int* parent,
+                     unsigned char* ref, void* stream);
+/* root (V): the root above every vertex; isroot (V) int32: 1 where a referenced vertex is its own root */
+int sfmi_cc_flatten_i32(const int* parent, const unsigned char* ref, int V, int* root, int* isroot, void* stream);
+/* rank (V): the INCLUSIVE prefix sum of isroot; coff (B+1) [device]: the roots before each shape's first vertex.  vlabel (V), flabel (T):
+ * the labels; vkey (V), fkey (T): the batch-wide component id of every vertex and face, INT_MAX for an unreferenced vertex and in a
+ * flagged shape: sorted, their runs give n_vert and n_face, and fkey is the sort key of the statistics; status (B) */
+int sfmi_cc_number_i32(const int* faces, const int* voff, const int* toff, const int* flags, const int* root, const unsigned char* ref,
+                       const int* rank, const int* coff, int B, int V, int T, int* vlabel, int* flabel, int* vkey, int* fkey, int* status,
+                       void* stream);
+/* forder (T): the faces stably sorted by fkey; seg (nC+1): where each component's run starts in that order (its differences: n_face);
+ * choff (nC+1): the exclusive prefix sum of ceil(faces / chunk); nW >= choff[nC]: the capacity of part (2 nW doubles of work space).
+ * area, volume (nC) f64 (0 for a table entry without faces) */
+int sfmi_cc_stats_f64(const float* verts, const int* faces, const int* voff, const int* toff, const int* forder, const int* seg,
+                      const int* choff, int B, int V, int T, int nC, int nW, double* part, double* area, double* volume, void* stream);
+/* keep (nC) uint8 per batch-wide component -> vkeep (V), fkeep (T) uint8 */
+int sfmi_cc_mark_i32(const int* vlabel, const int* flabel, const int* voff, const int* toff, const int* coff, const unsigned char* keep,
+                     int B, int V, int T, int nC, unsigned char* vkeep, unsigned char* fkeep, void* stream);
+/* vincl (V) / fincl (T): inclusive prefix sums of vkeep / fkeep; nvoff (B+1) [device]: the kept vertices before each shape; out_v (nVo,3),
+ * out_f (nTo,3): the kept vertices and the kept faces with indices local per shape */
+int sfmi_cc_emit_f32(const float* verts, const int* faces, const int* voff, const int* toff, const unsigned char* vkeep,
+                     const unsigned char* fkeep, const int* vincl, const int* fincl, const int* nvoff, int B, int V, int T, int nVo, int nTo,
+                     float* out_v, int* out_f, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

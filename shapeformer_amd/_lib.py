@@ -204,6 +204,15 @@ PROTOTYPES = {
     "sfmi_simplify_faces_i32": (i32, [c_ptr] * 5 + [i32] * 2 + [c_ptr] * 4),
     "sfmi_simplify_solve_f32": (i32, [c_ptr] * 10 + [i32] * 2 + [c_ptr] * 2 + [C.c_double] + [c_ptr] * 2),
     "sfmi_simplify_emit_i32": (i32, [c_ptr] * 7 + [i32] * 3 + [c_ptr] * 2),
+    # mesh connected components (csrc/components.hip)
+    "sfmi_cc_chunk": (i32, []),
+    "sfmi_cc_init_f32": (i32, [c_ptr] * 4 + [i32] * 3 + [c_ptr] * 4),
+    "sfmi_cc_hook_i32": (i32, [c_ptr] * 4 + [i32] * 3 + [c_ptr] * 3),
+    "sfmi_cc_flatten_i32": (i32, [c_ptr] * 2 + [i32] + [c_ptr] * 3),
+    "sfmi_cc_number_i32": (i32, [c_ptr] * 8 + [i32] * 3 + [c_ptr] * 6),
+    "sfmi_cc_stats_f64": (i32, [c_ptr] * 7 + [i32] * 5 + [c_ptr] * 4),
+    "sfmi_cc_mark_i32": (i32, [c_ptr] * 6 + [i32] * 4 + [c_ptr] * 3),
+    "sfmi_cc_emit_f32": (i32, [c_ptr] * 9 + [i32] * 5 + [c_ptr] * 3),
 }
 
 

@@ -104,8 +104,16 @@ class VisSparseRecon3D(VisCallback):
 
     def __init__(self, samples=32, Xct_as_Xbd=False, quant_grid_depth=4, decoder_resolution=128, vocab_size=4096,
                  max_length=512, end_tokens=(4096, 4096), resolution=(512, 512), vis_Ytg=True, thresh=0.5, decimate_face=None,
-                 refine_steps=0, vertex_normals=False, **kw):
+                 refine_steps=0, vertex_normals=False, keep_components=None, **kw):
         super().__init__(**kw)
+        # keep_components: drop the floaters of the extracted mesh on the device (components.keep_components_dev) after the
+        # refinement and before everything else, so that eval_pc, the fewer-than-10-vertices rule, the decimation and the PLY see the
+        # filtered mesh.  "largest", an int k (the k largest pieces), a float in (0, 1] (pieces of at least that share of the largest
+        # one's area) or a dict of keep_components_dev's keyword arguments; the returned dict then has `components` (count before
+        # filtering, pieces kept, area share removed).  None: off, unchanged
+        from .components import parse_keep
+        parse_keep(keep_components)
+        self.keep_components = keep_components
         # refine_steps: that many Newton steps of the mesh vertices onto the decoder's iso-surface (VQDIF.refine_mesh_dev),
         # each at most half a lattice cell; vertex_normals: the PLY carries the field's unit normals at its vertices.  The order is
         # extract -> refine -> decimate -> normals at the final vertices; eval_pc samples the refined, undecimated mesh.  0 / False: off,
@@ -156,6 +164,10 @@ class VisSparseRecon3D(VisCallback):
             grid = vq.decoder_grid_cl(vq.get_code_cl(torch.as_tensor(computed["dense"])[:1].to(vq.dev)))
             if self.refine_steps and len(v):
                 v = vq.refine_mesh_dev(grid, v, voff, thresh=self.thresh, steps=self.refine_steps, max_step=1.0 / (Q - 1))
+        report = None
+        if self.keep_components is not None:
+            from .components import filter_components_dev
+            v, f, voff, toff, _, report = filter_components_dev(v, f, voff, toff, self.keep_components)
         vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
         full = (vert, face)                                                                # what eval_pc samples
         if self.decimate_face is not None:
@@ -167,6 +179,8 @@ class VisSparseRecon3D(VisCallback):
             normal = vq.vertex_normals_dev(grid, v, voff).cpu().numpy().astype(np.float64)
         path = meshio.write_mesh(data_dir, vert, face, input_name, normal=normal)          # geoutil.write_mesh
         out = {"recon_mesh": {"vert": vert, "face": face}, "mesh_path": path}
+        if report is not None:
+            out["components"] = report[0]
         if normal is not None:
             out["recon_mesh"]["normal"] = normal
         if len(full[1]):
@@ -186,8 +200,14 @@ class VisShapeFormer(VisCallback):
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
                  thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
                  eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, refine_steps=0,
-                 vertex_normals=False, **kw):
+                 vertex_normals=False, keep_components=None, **kw):
         super().__init__(**kw)
+        # keep_components: as VisSparseRecon3D's, on the dense and the sparse_decode route alike: extract -> refine -> components ->
+        # decimate -> normals; eval_pc, recon_<i>, eval_metrics, the fewer-than-10-vertices rule, the decimation and the PLY see the
+        # filtered meshes, and the returned dict (with eval_metrics also eval/<name>_metrics.json) has `components` per mesh key.  None: off
+        from .components import parse_keep
+        parse_keep(keep_components)
+        self.keep_components = keep_components
         # refine_steps / vertex_normals: as VisSparseRecon3D's, on the dense and the sparse_decode route alike: extract -> refine ->
         # decimate -> normals at the final vertices; eval_pc, recon_<i> and eval_metrics sample the refined, undecimated meshes
         self.refine_steps, self.vertex_normals = int(refine_steps), bool(vertex_normals)
@@ -296,8 +316,12 @@ class VisShapeFormer(VisCallback):
                 grid = vq.decoder_grid_cl(vq.get_code_cl(codes))                    # final (applied-affine) form, whatever form the lattice query took
                 if self.refine_steps and len(vd):
                     vd = vq.refine_mesh_dev(grid, vd, voff, thresh=self.thresh, steps=self.refine_steps, max_step=1.0 / (Q - 1))
+        report = None
+        if self.keep_components is not None:
+            from .components import filter_components_dev
+            vd, fd, voff, toff, _, report = filter_components_dev(vd, fd, voff, toff, self.keep_components)
         if self.eval_metrics:
-            out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir))
+            out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir, report))
         v, f = vd.cpu().numpy().astype(np.float64), fd.cpu().numpy().astype(int)
         if self.decimate_face is not None:
             from .simplify import decimate_dev
@@ -319,6 +343,8 @@ class VisShapeFormer(VisCallback):
             out[key + "_mesh"] = {"vert": wv, "face": wf, "path": path}
             if wn is not None:
                 out[key + "_mesh"]["normal"] = wn[woff[j]:woff[j + 1]]
+            if report is not None:
+                out.setdefault("components", {})[key + "_mesh"] = report[j]
             if key[0] == "s":
                 eval_pcs.append(meshio.sample_mesh(vert, face, 10 ** 5))
         if eval_pcs:
@@ -329,7 +355,7 @@ class VisShapeFormer(VisCallback):
             np.savez(os.path.join(data_dir, "eval", f"{input_name}.npz"), **ed)
         return out
 
-    def _score(self, computed, sets, vd, fd, voff, toff, input_name, data_dir):
+    def _score(self, computed, sets, vd, fd, voff, toff, input_name, data_dir, report=None):
         """eval_metrics: the completion meshes that are exported (key s<i>, >= 10 vertices) sampled on the device with their own
         counter-hash stream (seed = self.seed; the numpy RNG is untouched), scored against Xct (and Xbd) in the mesh frame
         (bbox (-1,1)^3, as vis_ind).  -> {"metrics": dict, "metrics_pc": (k, eval_points, 3) device samples}."""
@@ -348,6 +374,8 @@ class VisShapeFormer(VisCallback):
         Xbd = batch["Xbd"][0] if "Xbd" in batch else None
         res = metrics.evaluate(batch["Xct"][0], pc, Xbd=Xbd, tau=self.eval_tau)
         res["keys"] = [sets[j][0] for j in keep]
+        if report is not None:                  # keep_components: what the filter removed from each scored mesh
+            res["components"] = {sets[j][0] + "_mesh": report[j] for j in keep}
         os.makedirs(os.path.join(data_dir, "eval"), exist_ok=True)
         with open(os.path.join(data_dir, "eval", f"{input_name}_metrics.json"), "w") as fh:
             json.dump(res, fh, indent=1)

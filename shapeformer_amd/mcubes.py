@@ -39,10 +39,12 @@ def marching_cubes_dev(occ: torch.Tensor, thresh: float = 0.5, bbox=((-1.0, -1.0
 
 
 def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), device="cuda:0", if_decimate=False,
-               decimate_face=4096):
+               decimate_face=4096, keep_components=None):
     """geoutil.array2mesh(array, thresh, dim=3, coords=..., if_decimate=..., decimate_face=...) for ONE flattened or cubic grid ->
     (verts (V,3) float64, faces (T,3) int) numpy, like the reference returns (`verts*(bbmax-bbmin)+bbmin`, faces.astype(int)).
-    if_decimate: a mesh with more than `decimate_face` faces is decimated on the device, over the same box, before the copy."""
+    if_decimate: a mesh with more than `decimate_face` faces is decimated on the device, over the same box, before the copy.
+    keep_components: "largest", an int k, a float in (0, 1] or a dict of components.keep_components_dev's keyword arguments: the mesh's
+    connected components are filtered on the device before the decimation; None: off."""
     a = torch.as_tensor(occupancy, dtype=torch.float32)
     if a.dim() != 3:
         Q = round(a.numel() ** (1.0 / 3))
@@ -52,6 +54,9 @@ def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.
         c = np.asarray(coords).reshape(-1, 3)
         bbox = (c.min(0), c.max(0))                # nputil.arrayBBox
     v, f, voff, toff = marching_cubes_dev(a[None].to(device), thresh, bbox)
+    if keep_components is not None:
+        from .components import keep_components_dev, parse_keep
+        v, f, voff, toff = keep_components_dev(v, f, voff, toff, **parse_keep(keep_components))[:4]
     if if_decimate:
         from .simplify import decimate_dev
         v, f = decimate_dev(v, f, voff, toff, decimate_face, bbox)[:2]
