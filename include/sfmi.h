@@ -737,6 +737,46 @@ int sfmi_cc_emit_f32(const float* verts, const int* faces, const int* voff, cons
                      const unsigned char* fkeep, const int* vincl, const int* fincl, const int* nvoff, int B, int V, int T, int nVo, int nTo,
                      float* out_v, int* out_f, void* stream);
 
+/* ---- Watertight voxelization of triangle soups (csrc/morph.hip): point -> voxel scatter, binary morphology with a
+ *      discrete ball and a lattice flood fill, the three steps that xgutils/geoutil.py:383-401 (morph_voxelization) runs on one core
+ *      with skimage.  The winding-number occupancy above needs closed, consistently oriented meshes; this one takes any soup.
+ * CONTRACT
+ *   Grid      a batch of B grids of G^3 voxels as bit sets: `bits` is (B, G, G, Wz) uint32 with Wz = ceil(G / 32); voxel [i][j][k]
+ *             (= x, y, z as in ptutil.point2voxel) is bit k % 32 of word ((b*G + i)*G + j)*Wz + k / 32.  Pad bits (k >= G) are never
+ *             treated as lattice points on input and are 0 in every word an entry writes.  B * G^3 < 2^31.
+ *   Voxelize  a point sets the voxel clamp(rint(((p + 1) / 2) * G - 0.5), 0, G - 1) per coordinate, every operation rounded to f32 on its
+ *             own (no fused multiply-add), rint = round half to even: ptutil.point2index:446-449 as torch evaluates it.  A point with a
+ *             non-finite coordinate sets no voxel.  Points are ragged: (N,3) f32 with (B+1) int32 offsets [device].
+ *   Dilate    out[v] = 1 iff some set voxel u of the same grid has |u - v|^2 <= r^2 in integers; outside the lattice counts as 0:
+ *             skimage.morphology.binary_dilation with ball(r), 0 <= r <= sfmi_morph_max_radius() (16).  invert_in / invert_out complement
+ *             the grid (lattice bits only) before / after, so that erosion, with the border counted as set (border_value=True), is
+ *             dilate(invert_in = 1, invert_out = 1).
+ *   Flood     region[v] = 1 iff v has the value of the grid's voxel (0,0,0) and is joined to it by a chain of such voxels under
+ *             26-connectivity: skimage.morphology.flood(grid, (0,0,0)) with its default connectivity.  status (B): 0 ok; 3 the seed
+ *             voxel was set, so the flood ran over the set voxels.
+ *   Determinism  integer atomics only (atomicOr; compare-and-swap on union-find roots whose final root is the component's smallest
+ *             index): every output is a function of the input bits, bit-identical from run to run and between a batch and per-shape
+ *             calls.  The number of launches does not depend on the grid's content (2 per dilation, 3 per flood).
+ * Every entry returns SFMI_EINVAL before any launch for a NULL pointer it would use, B <= 0, G <= 0, B * G^3 >= 2^31 or r outside
+ * [0, 16].  ws: sfmi_morph_workspace_bytes(B, G, r) bytes (r = 0 for the flood alone), caller-owned like every buffer. */
+int sfmi_morph_max_radius(void);
+/* B * G * G * ceil(G / 32): the uint32 words of a batch (0 for sizes the entries refuse) */
+long long sfmi_morph_words(int B, int G);
+/* max((r + 1) bit planes of the batch, one int32 parent per voxel); 0 for sizes the entries refuse */
+size_t sfmi_morph_workspace_bytes(int B, int G, int r);
+/* ptutil.point2voxel:520-550.  points (N,3) f32, off (B+1) int32 [device]; clears bits, then one atomicOr per finite point */
+int sfmi_voxelize_points_f32(const float* points, const int* off, int B, long long N, int G, unsigned* bits, void* stream);
+/* out (N) uint8: the voxel of the cell that holds each point (the same index; 0 for a non-finite point): a gather of the grid at points */
+int sfmi_voxelize_lookup_f32(const float* points, const int* off, int B, long long N, int G, const unsigned* bits, unsigned char* out,
+                             void* stream);
+/* geoutil.py:396-399 (ball, binary_dilation, binary_erosion).  out may be in */
+int sfmi_morph_dilate_u32(const unsigned* in, int B, int G, int r, int invert_in, int invert_out, unsigned* out, void* ws, void* stream);
+/* geoutil.py:394,398 (flood from (0,0,0)).  region must not be in */
+int sfmi_morph_flood_u32(const unsigned* in, int B, int G, unsigned* region, int* status, void* ws, void* stream);
+/* vox (B,G,G,G) uint8 <-> bits: bit = (vox != 0); vox = 0 / 1 */
+int sfmi_morph_pack_u8(const unsigned char* vox, int B, int G, unsigned* bits, void* stream);
+int sfmi_morph_unpack_u8(const unsigned* bits, int B, int G, unsigned char* vox, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

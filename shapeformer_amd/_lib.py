@@ -213,6 +213,16 @@ PROTOTYPES = {
     "sfmi_cc_stats_f64": (i32, [c_ptr] * 7 + [i32] * 5 + [c_ptr] * 4),
     "sfmi_cc_mark_i32": (i32, [c_ptr] * 6 + [i32] * 4 + [c_ptr] * 3),
     "sfmi_cc_emit_f32": (i32, [c_ptr] * 9 + [i32] * 5 + [c_ptr] * 3),
+    # watertight voxelization of triangle soups (csrc/morph.hip)
+    "sfmi_morph_max_radius": (i32, []),
+    "sfmi_morph_words": (i64, [i32, i32]),
+    "sfmi_morph_workspace_bytes": (sz, [i32, i32, i32]),
+    "sfmi_voxelize_points_f32": (i32, [c_ptr, c_ptr, i32, i64, i32, c_ptr, c_ptr]),
+    "sfmi_voxelize_lookup_f32": (i32, [c_ptr, c_ptr, i32, i64, i32, c_ptr, c_ptr, c_ptr]),
+    "sfmi_morph_dilate_u32": (i32, [c_ptr, i32, i32, i32, i32, i32, c_ptr, c_ptr, c_ptr]),
+    "sfmi_morph_flood_u32": (i32, [c_ptr, i32, i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "sfmi_morph_pack_u8": (i32, [c_ptr, i32, i32, c_ptr, c_ptr]),
+    "sfmi_morph_unpack_u8": (i32, [c_ptr, i32, i32, c_ptr, c_ptr]),
 }
 
 

@@ -2,11 +2,16 @@
 shapeformer/data/imnet_datasets/utils.py:33-70, with the occupancy the IMNet2 stores carry).
 
     python -m shapeformer_amd.make_dataset MESH... --out ROOT --dataset NAME --split train [--grid 64] [--boundary-n 32768]
-                                           [--cate NAME=GLOB ...] [--seed 0] [--batch K]
+                                           [--cate NAME=GLOB ...] [--seed 0] [--batch K] [--scale 1.0]
+                                           [--occupancy winding|morph] [--morph-grid 128] [--selem 6] [--morph-samples 1000000]
 
-Each mesh (.obj / .off / .ply) is normalised with normalize_point_set (bounding box centred, longest side 2), then batches of K
-meshes go through the device: lattice occupancy (mesh_occupancy_dev on the grid^3 makeGrid lattice of [-1, 1]^3) and area-weighted
-surface samples (sample_mesh_dev).  The store is what data.Imnet2LowResDataset reads:
+Each mesh (.obj / .off / .ply) is normalised with normalize_point_set (bounding box centred, longest side 2) and multiplied by
+--scale, then batches of K meshes go through the device: lattice occupancy on the grid^3 makeGrid lattice of [-1, 1]^3 and
+area-weighted surface samples (sample_mesh_dev).  --occupancy winding (the default) is mesh_occupancy_dev's inside test |W| > 0.5: for
+closed, consistently oriented meshes.  --occupancy morph is for triangle soups (open shells, interior partitions, doubled and flipped
+faces): morph_voxelization_dev's watertight voxels on a --morph-grid^3 grid (closing with a ball of --selem cells over --morph-samples
+surface samples), read at each lattice point from the cell that holds it; the outside is flooded from voxel (0,0,0), so a shape that
+fills the box needs --scale 0.9 or so to keep that corner empty.  The store is what data.Imnet2LowResDataset reads:
 
     ROOT/NAME/SPLIT/Xbd.npy          (n, boundary_n, 3) float32 surface samples
     ROOT/NAME/SPLIT/Ytg.npy          (n, grid^3 / 8) uint8 = np.packbits(occupancy.reshape(n, -1), axis=-1)
@@ -20,6 +25,9 @@ import os
 import sys
 
 import numpy as np
+
+
+OCCUPANCY = ("winding", "morph")
 
 
 def write_imnet_store(root, dataset, split, Xbd, occ, cates=None):
@@ -55,23 +63,51 @@ def _batch(meshes, dev):
     return verts, faces, voff, toff
 
 
+def _morph_occupancy(v, f, voff, toff, names, lattice, grid, morph_grid, selem, morph_samples, seed):
+    """(B, grid, grid, grid) uint8: the watertight voxel of the cell that holds each lattice point; status (B,) on the device"""
+    from . import morph
+    vox, st = morph.morph_voxelization_dev(v, f, voff, toff, sampleN=morph_samples, grid_dim=morph_grid, selem_size=selem, seed=seed,
+                                           return_status=True)
+    seed_set = (st == morph.STATUS_SEED_SET).cpu().numpy()
+    if seed_set.any():
+        raise ValueError(f"{[names[i] for i in np.nonzero(seed_set)[0]]}: the closed shape reaches the corner voxel (0,0,0) that the "
+                         "outside is flooded from; shrink it, e.g. --scale 0.9")
+    B = len(names)
+    o = morph.voxel_lookup_dev(vox, lattice[None].expand(B, -1, -1))
+    return o.reshape(B, grid, grid, grid), st
+
+
 def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, cates=None, seed=0, batch=8, device="cuda:0",
-                 log=None):
-    """Read, normalise and sample every mesh of `paths`; write the store.  cates: {name: glob} matched against each path."""
+                 log=None, occupancy="winding", morph_grid=128, selem=6, morph_samples=1_000_000, scale=1.0):
+    """Read, normalise and sample every mesh of `paths`; write the store.  cates: {name: glob} matched against each path.
+    occupancy: "winding" (mesh_occupancy_dev) or "morph" (morph_voxelization_dev on a morph_grid^3 grid, ball of selem cells,
+    morph_samples surface samples); scale multiplies the normalised vertices on both routes."""
     import torch
     from . import meshio, meshsdf
     from .metrics import sample_mesh_dev
+    if occupancy not in OCCUPANCY:
+        raise ValueError(f"occupancy = {occupancy!r} must be one of {OCCUPANCY}")
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"scale = {scale!r} must be a positive number")
     dev = torch.device(device)
     Xbd, occ = [], []
+    lattice = None
+    if occupancy == "morph":
+        from .data import make_grid
+        lattice = torch.from_numpy(make_grid([-1, -1, -1.], [1., 1, 1], [grid] * 3).astype(np.float32)).to(dev)
     for s in range(0, len(paths), batch):
         meshes = []
         for p in paths[s:s + batch]:
             v, f = meshio.read_mesh(p)
             if len(f) == 0:
                 raise ValueError(f"{p}: no faces")
-            meshes.append((meshsdf.normalize_point_set(v), f))
+            v = meshsdf.normalize_point_set(v)
+            meshes.append((v if scale == 1.0 else v * scale, f))
         v, f, voff, toff = _batch(meshes, dev)
-        o, st = meshsdf.mesh_occupancy_dev(v, f, voff, toff, grid_dim=grid, return_status=True)
+        if occupancy == "morph":
+            o, st = _morph_occupancy(v, f, voff, toff, paths[s:s + batch], lattice, grid, morph_grid, selem, morph_samples, seed + s)
+        else:
+            o, st = meshsdf.mesh_occupancy_dev(v, f, voff, toff, grid_dim=grid, return_status=True)
         x, st2 = sample_mesh_dev(v, f, voff, toff, boundary_n, seed=seed + s)
         bad = ((st != 0) | (st2 != 0)).cpu().numpy()
         if bad.any():
@@ -84,7 +120,7 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
     return write_imnet_store(out, dataset, split, np.concatenate(Xbd), np.concatenate(occ), ci)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m shapeformer_amd.make_dataset", description=__doc__.split("\n\n")[0])
     ap.add_argument("meshes", nargs="+", help=".obj / .off / .ply files")
     ap.add_argument("--out", required=True, help="store root")
@@ -95,15 +131,34 @@ def main(argv=None):
     ap.add_argument("--cate", action="append", default=[], metavar="NAME=GLOB")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--occupancy", choices=OCCUPANCY, default="winding",
+                    help="winding: |W| > 0.5, for closed oriented meshes; morph: watertight voxelization, for triangle soups")
+    ap.add_argument("--morph-grid", type=int, default=128, help="morph: voxels per axis of the watertight grid")
+    ap.add_argument("--selem", type=int, default=6, help="morph: radius in voxels of the closing's ball (0 .. 16)")
+    ap.add_argument("--morph-samples", type=int, default=1_000_000, help="morph: surface samples per mesh")
+    ap.add_argument("--scale", type=float, default=1.0, help="multiplies the normalised vertices (both routes)")
     a = ap.parse_args(argv)
+    if a.morph_grid < 1 or a.morph_samples < 1:
+        ap.error("--morph-grid and --morph-samples must be >= 1")
+    if not 0 <= a.selem <= 16:
+        ap.error("--selem must lie in [0, 16]")
+    if not (np.isfinite(a.scale) and a.scale > 0):
+        ap.error("--scale must be a positive number")
     cates = {}
     for c in a.cate:
         name, sep, g = c.partition("=")
         if not sep or not name:
             ap.error(f"--cate {c!r}: expected NAME=GLOB")
         cates[name] = g
-    d = make_dataset(a.meshes, a.out, a.dataset, a.split, a.grid, a.boundary_n, cates, a.seed, max(1, a.batch),
-                     log=lambda m: print(m, file=sys.stderr))
+    a.cates = cates
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    d = make_dataset(a.meshes, a.out, a.dataset, a.split, a.grid, a.boundary_n, a.cates, a.seed, max(1, a.batch),
+                     log=lambda m: print(m, file=sys.stderr), occupancy=a.occupancy, morph_grid=a.morph_grid, selem=a.selem,
+                     morph_samples=a.morph_samples, scale=a.scale)
     print(d)
 
 
