@@ -1,0 +1,128 @@
+"""Shared pieces of the mesh tools, host side (the device side is csrc/sfmi_ragged.h).
+
+Argument handling and small tensor idioms of metrics / meshsdf / hpr / iso_sparse / simplify / components / morph / make_dataset.
+
+A ragged batch is B sets stored back to back with (B+1,) exclusive offsets: off[0] = 0, nondecreasing, off[B] = the row count; None
+means one set.  Every check here runs on the host and raises SfmiError before the library is loaded, so a refused call launches
+nothing.  Where the tensors live is NOT part of `mesh_args` / `point_sets`: a caller finishes its own host checks and then calls
+`on_device`, last, so a CPU tensor reports the first wrong argument and not the device.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+
+# ---- argument handling (host only: everything here runs before any launch) -------------------------------------------------
+
+def host_offsets(off, n, what, empty_ok=False, flatten=False):
+    """-> (B+1,) int64 numpy exclusive offsets, validated against the n rows they cut.  None: one set.  empty_ok admits the
+    one-element [0] (B = 0); flatten takes an array of any shape as its elements in order (components / simplify always did)."""
+    if off is None:
+        return np.array([0, n], np.int64)
+    o = off.detach().cpu().numpy() if isinstance(off, torch.Tensor) else np.asarray(off)
+    if flatten:
+        o = o.reshape(-1)
+    if o.ndim != 1 or o.shape[0] < (1 if empty_ok else 2) or not np.issubdtype(o.dtype, np.integer):
+        raise L.SfmiError(f"{what}: offsets must be a 1-D integer array of length B+1")
+    o = o.astype(np.int64)
+    if o[0] != 0 or o[-1] != n or (np.diff(o) < 0).any():
+        raise L.SfmiError(f"{what}: offsets must start at 0, be nondecreasing and end at {n}")
+    return o
+
+
+def on_device(what, *tensors):
+    """-> the one HIP device all the tensors are on.  Every caller's last check."""
+    dev = tensors[0].device
+    for t in tensors:
+        if t.device.type != "cuda":
+            raise L.SfmiError(f"{what} needs HIP device tensors (no CPU fallback)")
+        if t.device != dev:
+            raise L.SfmiError(f"{what}: all tensors must be on one device")
+    return dev
+
+
+def points_arg(x, what):
+    if not isinstance(x, torch.Tensor):
+        raise L.SfmiError(f"{what}: expected a torch tensor on the HIP device (no CPU fallback)")
+    if x.shape[-1:] != (3,) or x.dim() not in (2, 3):
+        raise L.SfmiError(f"{what}: expected (N,3) or (B,N,3) points, got {tuple(x.shape)}")
+    return x
+
+
+def point_sets(points, off, what):
+    """(B,N,3) points (off must be None), or (N,3) points with offsets -> (points as (N,3), host offsets (B+1,), (B,N) or None)."""
+    x = points_arg(points, what)
+    if x.dim() == 3:
+        if off is not None:
+            raise L.SfmiError(f"{what}: offsets go with (N,3) points, not with (B,N,3)")
+        B, n = x.shape[:2]
+        return x.reshape(B * n, 3), np.arange(B + 1, dtype=np.int64) * n, (B, n)
+    return x, host_offsets(off, x.shape[0], f"{what} offsets"), None
+
+
+def mesh_args(verts, faces, voff, toff, what, index32=False, empty_ok=False, flatten_offsets=False):
+    """A ragged batch of indexed meshes -> (verts f32 contiguous, faces int32 contiguous, host voff, host toff) after the host checks:
+    tensors, (V,3) / (T,3), integer faces, offsets (host_offsets), equal shape counts, and the size bound - with index32 the whole batch
+    in 32-bit indices (components, simplify), else each shape's faces (meshsdf, morph).  A tensor that already has the dtype and
+    layout comes back as it is."""
+    if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
+        raise L.SfmiError(f"{what}: verts / faces must be torch tensors on the HIP device (no CPU fallback)")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise L.SfmiError(f"{what}: expected verts (V,3) and faces (T,3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise L.SfmiError(f"{what}: faces must be an integer tensor")
+    vo = host_offsets(voff, verts.shape[0], f"{what} voff", empty_ok, flatten_offsets)
+    to = host_offsets(toff, faces.shape[0], f"{what} toff", empty_ok, flatten_offsets)
+    if len(vo) != len(to):
+        raise L.SfmiError(f"{what}: voff and toff describe different batch sizes ({len(vo) - 1} and {len(to) - 1} shapes)")
+    if index32:
+        if verts.shape[0] + faces.shape[0] + len(vo) >= 2 ** 31 or 3 * faces.shape[0] >= 2 ** 31:
+            raise L.SfmiError(f"{what}: the batch is too large for 32-bit indices")
+    elif (np.diff(to) >= 2 ** 31).any():
+        raise L.SfmiError(f"{what}: a shape has 2^31 faces or more")
+    return verts.float().contiguous(), faces.to(torch.int32).contiguous(), vo, to
+
+
+# ---- host arrays -> device tensors -----------------------------------------------------------------------------------------
+
+def i32_dev(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.int32))).to(dev)
+
+
+def f32_dev(x, dev=None):
+    """a tensor as it is; anything else as a contiguous f32 array on dev (None: the current HIP device)"""
+    if isinstance(x, torch.Tensor):
+        return x
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32))).to(dev or torch.device("cuda"))
+
+
+def batch_meshes(meshes, dev):
+    """[(verts (n_i,3), faces (t_i,3)) numpy, indices local] -> verts f32, faces int32 on dev, host voff, toff (B+1,)"""
+    verts = torch.from_numpy(np.concatenate([v for v, _ in meshes]).astype(np.float32)).to(dev)
+    faces = torch.from_numpy(np.concatenate([f for _, f in meshes]).astype(np.int32)).to(dev)
+    voff = np.concatenate([[0], np.cumsum([len(v) for v, _ in meshes])]).astype(np.int64)
+    toff = np.concatenate([[0], np.cumsum([len(f) for _, f in meshes])]).astype(np.int64)
+    return verts, faces, voff, toff
+
+
+# ---- prefix sums and sorted runs (any device) ------------------------------------------------------------------------------
+
+def excl(x):
+    """(n,) counts -> (n+1,) int32 exclusive prefix sums"""
+    return torch.cat([x.new_zeros(1, dtype=torch.int32), torch.cumsum(x, 0, dtype=torch.int32)])
+
+
+def excl_at(incl, off):
+    """exclusive prefix at the (B+1) offsets `off` of an inclusive prefix sum (its total at off[B])"""
+    return torch.cat([incl.new_zeros(1), incl])[off.long()]
+
+
+def runs(keys, n):
+    """stable sort of the records by key -> (order int32, (n+1) int32 run starts: the records of key k are order[seg[k]:seg[k+1]];
+    keys >= n sort behind every run)"""
+    s = torch.sort(keys, stable=True)
+    seg = torch.searchsorted(s.values, torch.arange(n + 1, device=keys.device, dtype=torch.int32))
+    return s.indices.to(torch.int32), seg.to(torch.int32)

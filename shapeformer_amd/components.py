@@ -10,10 +10,11 @@ tests/components_ref.py.  There is no CPU fallback.
   keep_components_dev(verts, faces, voff, toff, top=None, min_share=0.0, by="area") -> verts, faces, voff, toff, status, kept, coff
   filter_components_dev(verts, faces, voff, toff, spec)                           -> verts, faces, voff, toff, status, report
 
-verts (V,3) f32 and faces (T,3) int32 (indices local per shape) are device tensors, voff / toff (B+1) host offsets.  Labels are local per
-shape, -1 for a vertex no face names; the components of a shape are numbered by their smallest vertex index.  status (B) int32 on the
-device: 0 ok, 1 no vertices, 2 a face index outside the shape, 3 a non-finite vertex (such a shape has no components and comes back
-empty).  Results are bit-identical from run to run and a batch equals per-shape calls.  Each call reads sizes back once.
+verts (V,3) f32 and faces (T,3) int32 (indices local per shape) are device tensors, voff / toff (B+1) host offsets (None: one shape;
+the argument checks are _ragged.py's).  Labels are local per shape, -1 for a vertex no face names; the components of a
+shape are numbered by their smallest vertex index.  status (B) int32 on the device: 0 ok, 1 no vertices, 2 a face index outside the
+shape, 3 a non-finite vertex (such a shape has no components and comes back empty).  Results are bit-identical from run to run and a
+batch equals per-shape calls.  Each call reads sizes back once.
 """
 from __future__ import annotations
 
@@ -23,39 +24,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._ragged import excl, i32_dev, mesh_args, on_device, runs
 
 MEASURES = ("area", "faces", "volume")
 read_backs = 0          # device -> host size read-backs so far (tools/kbench_components.py reports the number per call)
 
 
-def _offsets(off, n, what):
-    o = off.detach().cpu().numpy() if isinstance(off, torch.Tensor) else np.asarray(off)
-    o = o.astype(np.int64).reshape(-1)
-    if len(o) < 1 or o[0] != 0 or o[-1] != n or (np.diff(o) < 0).any():
-        raise L.SfmiError(f"components: {what} must be (B+1) exclusive offsets from 0 to {n}")
-    return o
-
-
-def _mesh(verts, faces, voff, toff, what):
-    """Checked on the host before anything touches the device: shapes, offsets, then where the tensors live."""
-    for name, t in (("verts", verts), ("faces", faces)):
-        if not isinstance(t, torch.Tensor):
-            raise L.SfmiError(f"{what}: {name} must be a torch tensor on the HIP device (no CPU fallback)")
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        raise L.SfmiError(f"{what}: verts must be (V,3), got {tuple(verts.shape)}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise L.SfmiError(f"{what}: faces must be (T,3), got {tuple(faces.shape)}")
-    vo, to = _offsets(voff, verts.shape[0], "voff"), _offsets(toff, faces.shape[0], "toff")
-    if len(vo) != len(to):
-        raise L.SfmiError(f"{what}: voff and toff name {len(vo) - 1} and {len(to) - 1} shapes")
-    if verts.shape[0] + faces.shape[0] + len(vo) >= 2 ** 31 or 3 * faces.shape[0] >= 2 ** 31:
-        raise L.SfmiError(f"{what}: the batch is too large for 32-bit indices")
-    for name, t in (("verts", verts), ("faces", faces)):
-        if t.device.type != "cuda":
-            raise L.SfmiError(f"{what}: {name} must be on the HIP device (no CPU fallback)")
-    verts = verts.contiguous() if verts.dtype == torch.float32 else verts.float().contiguous()
-    faces = faces.contiguous() if faces.dtype == torch.int32 else faces.to(torch.int32).contiguous()
-    return verts, faces, vo, to
+# how this module calls mesh_args: 32-bit batch-wide indices; B = 0 is a batch (it comes back empty); offsets of any array shape
+_MESH = dict(index32=True, empty_ok=True, flatten_offsets=True)
 
 
 def _selection(top, min_share, by):
@@ -102,15 +78,6 @@ def parse_keep(spec):
     return kw
 
 
-def _i32(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.int32))).to(dev)
-
-
-def _excl(x):
-    """(n,) counts -> (n+1,) int32 exclusive prefix sums"""
-    return torch.cat([x.new_zeros(1, dtype=torch.int32), torch.cumsum(x, 0, dtype=torch.int32)])
-
-
 def _label(verts, faces, vo, to):
     """The labelling and statistics passes of csrc/components.hip on a checked batch of B >= 1 shapes.  No read-back: the component
     tables have the capacity nC = min(V, T) + 1; the entries from coff[B] on are empty (no vertices, no faces, zero sums)."""
@@ -118,7 +85,7 @@ def _label(verts, faces, vo, to):
     B, V, T = len(vo) - 1, verts.shape[0], faces.shape[0]
     nC = min(V, T) + 1
     i32 = dict(device=dev, dtype=torch.int32)
-    voff, toff = _i32(vo, dev), _i32(to, dev)
+    voff, toff = i32_dev(vo, dev), i32_dev(to, dev)
     parent, root, isroot, vlabel, vkey = (torch.empty(max(V, 1), **i32) for _ in range(5))
     flabel, fkey = (torch.empty(max(T, 1), **i32) for _ in range(2))
     ref = torch.empty(max(V, 1), device=dev, dtype=torch.uint8)
@@ -129,18 +96,15 @@ def _label(verts, faces, vo, to):
             "sfmi_cc_hook_i32")
     L.check(lib.sfmi_cc_flatten_i32(L.ptr(parent), L.ptr(ref), V, L.ptr(root), L.ptr(isroot), st()), "sfmi_cc_flatten_i32")
     rank = torch.cumsum(isroot[:V], 0, dtype=torch.int32)
-    coff = _excl(isroot[:V])[voff.long()].contiguous()                       # (B+1): the roots before each shape
+    coff = excl(isroot[:V])[voff.long()].contiguous()                       # (B+1): the roots before each shape
     L.check(lib.sfmi_cc_number_i32(L.ptr(faces), L.ptr(voff), L.ptr(toff), L.ptr(flags), L.ptr(root), L.ptr(ref), L.ptr(rank), L.ptr(coff),
                                    B, V, T, L.ptr(vlabel), L.ptr(flabel), L.ptr(vkey), L.ptr(fkey), L.ptr(status), st()), "sfmi_cc_number_i32")
     # the runs of the sorted keys: where each component's faces start (the order of the sums) and how many vertices / faces it has
-    ids = torch.arange(nC + 1, **i32)
-    fsort = torch.sort(fkey[:T], stable=True)
-    forder, seg = fsort.indices.to(torch.int32), torch.searchsorted(fsort.values, ids).to(torch.int32)
-    n_face = seg[1:] - seg[:-1]
-    n_vert = torch.diff(torch.searchsorted(torch.sort(vkey[:V]).values, ids)).to(torch.int32)
+    forder, seg = runs(fkey[:T], nC)
+    n_face, n_vert = torch.diff(seg), torch.diff(runs(vkey[:V], nC)[1])
     K = int(lib.sfmi_cc_chunk())
     nW = T // K + min(nC, T)                                                 # sum of ceil(n_c / K) <= T / K + components with faces
-    choff = _excl((n_face + (K - 1)) // K)
+    choff = excl((n_face + (K - 1)) // K)
     part = torch.empty(2 * max(nW, 1), device=dev, dtype=torch.float64)
     area, volume = torch.empty(nC, device=dev, dtype=torch.float64), torch.empty(nC, device=dev, dtype=torch.float64)
     L.check(lib.sfmi_cc_stats_f64(L.ptr(verts), L.ptr(faces), L.ptr(voff), L.ptr(toff), L.ptr(forder), L.ptr(seg), L.ptr(choff), B, V, T,
@@ -160,7 +124,8 @@ def mesh_components_dev(verts, faces, voff, toff):
     coff (B+1) host offsets into the component table, stats: dict of device tensors over the component table (n_vert, n_face int32,
     area, volume f64), status (B) int32 (device)."""
     global read_backs
-    verts, faces, vo, to = _mesh(verts, faces, voff, toff, "mesh_components_dev")
+    verts, faces, vo, to = mesh_args(verts, faces, voff, toff, "mesh_components_dev", **_MESH)
+    on_device("mesh_components_dev", verts, faces)
     if len(vo) == 1:
         e, stats = _empty_batch(verts, faces)
         return e, e.clone(), np.zeros(1, np.int64), stats, e.clone()
@@ -215,7 +180,7 @@ def _keep(verts, faces, vo, to, top, share, by):
     vkeep, fkeep = torch.empty(max(V, 1), device=dev, dtype=torch.uint8), torch.empty(max(T, 1), device=dev, dtype=torch.uint8)
     L.check(lib.sfmi_cc_mark_i32(L.ptr(r["vlabel"]), L.ptr(r["flabel"]), L.ptr(r["voff"]), L.ptr(r["toff"]), L.ptr(r["coff"]), L.ptr(k8),
                                  B, V, T, nC, L.ptr(vkeep), L.ptr(fkeep), st()), "sfmi_cc_mark_i32")
-    vex, fex = _excl(vkeep[:V]), _excl(fkeep[:T])
+    vex, fex = excl(vkeep[:V]), excl(fkeep[:T])
     nvoff, ntoff = vex[r["voff"].long()].contiguous(), fex[r["toff"].long()].contiguous()
     h = torch.cat([r["coff"], nvoff, ntoff]).cpu().numpy().astype(np.int64)  # the one read-back: sizes
     read_backs += 1
@@ -236,7 +201,8 @@ def keep_components_dev(verts, faces, voff, toff, top=None, min_share=0.0, by="a
     no face names are dropped; a shape whose components are all kept and that has no such vertex comes back bit for bit.
     -> verts, faces (device), voff, toff (host), status (B) int32 (device), kept (C_total) bool (device), coff (B+1) host."""
     top, share, by = _selection(top, min_share, by)
-    verts, faces, vo, to = _mesh(verts, faces, voff, toff, "keep_components_dev")
+    verts, faces, vo, to = mesh_args(verts, faces, voff, toff, "keep_components_dev", **_MESH)
+    on_device("keep_components_dev", verts, faces)
     o = _keep(verts, faces, vo, to, top, share, by)
     return o["verts"], o["faces"], o["voff"], o["toff"], o["status"], o["kept"], o["coff"]
 
@@ -249,7 +215,8 @@ def filter_components_dev(verts, faces, voff, toff, spec):
     if kw is None:
         raise L.SfmiError("filter_components_dev: keep_components is None (off)")
     top, share, by = _selection(kw.get("top"), kw.get("min_share", 0.0), kw.get("by", "area"))
-    verts, faces, vo, to = _mesh(verts, faces, voff, toff, "filter_components_dev")
+    verts, faces, vo, to = mesh_args(verts, faces, voff, toff, "filter_components_dev", **_MESH)
+    on_device("filter_components_dev", verts, faces)
     o = _keep(verts, faces, vo, to, top, share, by)
     area, kept, coff = o["area"].cpu().numpy(), o["kept"].cpu().numpy(), o["coff"]
     report = []

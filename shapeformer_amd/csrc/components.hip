@@ -3,10 +3,10 @@
 // (filterMesh, a vertex-mask filter with "# TODO filterF").  The contract is in include/sfmi.h, its numpy statement in
 // tests/components_ref.py.
 //
-// One int32 `parent` array over the batch's vertices (batch-wide indices), a lock-free union-find in the manner of ECL-CC:
+// One int32 `parent` array over the batch's vertices (batch-wide indices), the lock-free union-find of csrc/sfmi_ragged.h (DESIGN.md
+// §5.5a, where its race argument is written down once):
 //   init     parent[v] = v; the shape's flags: no vertices, a face index outside the shape, a non-finite vertex
-//   hook     one thread per face: find (path halving) on the corners, the larger root linked under the smaller by atomicCAS on the larger
-//            root's slot; marks the vertices a face names
+//   hook     one thread per face: the union of its corners; marks the vertices a face names
 //   flatten  a launch of its own (the kernel boundary makes every hook visible): root[v], and which vertices are roots
 //   number   labels from the exclusive count of roots (a prefix sum between the launches), and the batch-wide component of every vertex
 //            and face: the sort keys whose runs give the vertices / faces per component (no counter that every wave would add to)
@@ -16,7 +16,7 @@
 //   emit     kept vertices and re-indexed kept faces at the slots an exclusive count gives
 // parent[v] <= v always holds, so the root of a finished tree is the smallest index of its component whatever order the hooks came
 // in: the labels are a function of the mesh.  Integer atomics only; every f64 sum runs in a fixed order over a fixed tree.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"
 
 // the f64 face terms are written once, here and in numpy: no contraction into fused multiply-adds
 #pragma clang fp contract(off)
@@ -25,48 +25,6 @@ namespace {
 
 constexpr int CC_CHUNK = 1024;          // faces per chunk of a component's run, counted from the run's own start
 constexpr int CC_NONE = 0x7fffffff;     // the sort key of a flagged shape's faces: sorts behind every component
-constexpr int CC_NO_VERTS = 1, CC_BAD_INDEX = 2, CC_NON_FINITE = 4;   // flag bits; the status is the lowest one set
-
-__device__ __forceinline__ int cc_shape_of(const int* __restrict__ off, int B, int j) {
-  int b = 0;
-  for (int i = 1; i < B; ++i) b += (j >= off[i]);
-  return b;
-}
-
-__device__ __forceinline__ int cc_status(int flags) {
-  return (flags & CC_NO_VERTS) ? 1 : ((flags & CC_BAD_INDEX) ? 2 : ((flags & CC_NON_FINITE) ? 3 : 0));
-}
-
-// parent is read and written by other workgroups during the hook launch: relaxed agent-scope accesses (they pass the CU's L1).  A stale
-// value is an older value of the slot, which is the vertex itself or an ancestor of it: it costs steps, never correctness
-__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cc_store(int* p, int x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root above v as this thread sees it, halving the path on the way (a slot that is not a root never becomes one again, and only root
-// slots are targets of the CAS, so the plain store of a grandparent into a non-root slot races with nothing that matters)
-__device__ __forceinline__ int cc_find(int* parent, int v) {
-  int cur = v, p = cc_load(parent + cur);
-  while (p != cur) {
-    const int g = cc_load(parent + p);
-    if (g != p) cc_store(parent + cur, g);
-    cur = p;
-    p = g;
-  }
-  return cur;
-}
-
-__device__ __forceinline__ void cc_hook(int* parent, int u, int v) {
-  int ru = cc_find(parent, u), rv = cc_find(parent, v);
-  while (ru != rv) {
-    const int hi = max(ru, rv), lo = min(ru, rv);
-    const int old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) return;
-    // hi had stopped being a root: `old` is its parent as memory holds it, so the walk goes on from there even if this CU's view of
-    // the slot is stale
-    ru = cc_find(parent, old);
-    rv = cc_find(parent, lo);
-  }
-}
 
 // threads [0,V): vertices; [V,V+T): faces; [V+T,V+T+B): shapes
 __global__ __launch_bounds__(256) void cc_init_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -77,9 +35,9 @@ __global__ __launch_bounds__(256) void cc_init_kernel(const float* __restrict__ 
     const int i = (int)t;
     parent[i] = i;
     if (!(isfinite(verts[3ll * i]) && isfinite(verts[3ll * i + 1]) && isfinite(verts[3ll * i + 2])))
-      atomicOr(&flags[cc_shape_of(voff, B, i)], CC_NON_FINITE);
+      atomicOr(&flags[sfmi_shape_of(voff, B, i)], SFMI_MESH_NON_FINITE);
   } else if (t < (long long)V + T) {
-    const int j = (int)(t - V), b = cc_shape_of(toff, B, j);
+    const int j = (int)(t - V), b = sfmi_shape_of(toff, B, j);
     const int nv = voff[b + 1] - voff[b];
     bool ok = true;
 #pragma unroll
@@ -87,10 +45,10 @@ __global__ __launch_bounds__(256) void cc_init_kernel(const float* __restrict__ 
       const int a = faces[3ll * j + k];
       ok = ok && a >= 0 && a < nv;
     }
-    if (!ok) atomicOr(&flags[b], CC_BAD_INDEX);
+    if (!ok) atomicOr(&flags[b], SFMI_MESH_BAD_INDEX);
   } else if (t < (long long)V + T + B) {
     const int b = (int)(t - V - T);
-    if (voff[b + 1] <= voff[b]) atomicOr(&flags[b], CC_NO_VERTS);
+    if (voff[b + 1] <= voff[b]) atomicOr(&flags[b], SFMI_MESH_NO_VERTS);
   }
 }
 
@@ -99,13 +57,13 @@ __global__ __launch_bounds__(256) void cc_hook_kernel(const int* __restrict__ fa
                                                       int* parent, unsigned char* __restrict__ ref) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= T) return;
-  const int b = cc_shape_of(toff, B, j);
+  const int b = sfmi_shape_of(toff, B, j);
   if (flags[b]) return;          // the indices of an unflagged shape are all inside it
   const int vb = voff[b];
   const int a = vb + faces[3ll * j], c = vb + faces[3ll * j + 1], d = vb + faces[3ll * j + 2];
   ref[a] = 1; ref[c] = 1; ref[d] = 1;
-  if (c != a) cc_hook(parent, a, c);
-  if (d != a && d != c) cc_hook(parent, a, d);
+  if (c != a) sfmi_uf_hook(parent, a, c);
+  if (d != a && d != c) sfmi_uf_hook(parent, a, d);
 }
 
 // parent is only read here
@@ -133,12 +91,12 @@ __global__ __launch_bounds__(256) void cc_number_kernel(const int* __restrict__ 
     int lab = -1, key = CC_NONE;
     if (ref[v]) {
       key = rank[root[v]] - 1;
-      lab = key - coff[cc_shape_of(voff, B, v)];
+      lab = key - coff[sfmi_shape_of(voff, B, v)];
     }
     vlabel[v] = lab;
     vkey[v] = key;
   } else if (t < (long long)V + T) {
-    const int j = (int)(t - V), b = cc_shape_of(toff, B, j);
+    const int j = (int)(t - V), b = sfmi_shape_of(toff, B, j);
     int lab = -1, key = CC_NONE;
     if (!flags[b]) {
       key = rank[root[voff[b] + faces[3ll * j]]] - 1;
@@ -148,14 +106,8 @@ __global__ __launch_bounds__(256) void cc_number_kernel(const int* __restrict__ 
     fkey[j] = key;
   } else if (t < (long long)V + T + B) {
     const int b = (int)(t - V - T);
-    status[b] = cc_status(flags[b]);
+    status[b] = sfmi_mesh_status(flags[b]);
   }
-}
-
-__device__ __forceinline__ double cc_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // one wave64 per chunk.  forder: the faces stably sorted by fkey; seg (nC+1): where each component's run starts; choff (nC+1): where its
@@ -176,7 +128,7 @@ __global__ __launch_bounds__(256) void cc_partial_kernel(const float* __restrict
   const int c = lo;
   const int s = seg[c] + (w - choff[c]) * CC_CHUNK, e = min(seg[c + 1], s + CC_CHUNK);
   if (s < 0 || e > T || s >= e) { if (!lane) { part[2ll * w] = 0.0; part[2ll * w + 1] = 0.0; } return; }
-  const int vb = voff[cc_shape_of(toff, B, forder[s])];
+  const int vb = voff[sfmi_shape_of(toff, B, forder[s])];
   double area = 0.0, vol = 0.0;
   for (int i = s + lane; i < e; i += 64) {
     const int* f = faces + 3ll * forder[i];
@@ -188,8 +140,8 @@ __global__ __launch_bounds__(256) void cc_partial_kernel(const float* __restrict
     const double x0 = p[1] * q[2] - p[2] * q[1], x1 = p[2] * q[0] - p[0] * q[2], x2 = p[0] * q[1] - p[1] * q[0];
     vol += (a[0] * x0 + a[1] * x1 + a[2] * x2) / 6.0;
   }
-  area = cc_wave_sum(area);
-  vol = cc_wave_sum(vol);
+  area = wave_sum_f64(area);
+  vol = wave_sum_f64(vol);
   if (!lane) { part[2ll * w] = area; part[2ll * w + 1] = vol; }
 }
 
@@ -209,8 +161,8 @@ __global__ __launch_bounds__(256) void cc_total_kernel(const double* __restrict_
     a += part[2ll * i];
     v += part[2ll * i + 1];
   }
-  a = cc_wave_sum(a);
-  v = cc_wave_sum(v);
+  a = wave_sum_f64(a);
+  v = wave_sum_f64(v);
   if (!lane) { area[c] = a; volume[c] = v; }
 }
 
@@ -222,11 +174,11 @@ __global__ __launch_bounds__(256) void cc_mark_kernel(const int* __restrict__ vl
   const long long t = blockIdx.x * 256ll + threadIdx.x;
   if (t < V) {
     const int v = (int)t, lab = vlabel[v];
-    const int gc = lab < 0 ? -1 : lab + coff[cc_shape_of(voff, B, v)];
+    const int gc = lab < 0 ? -1 : lab + coff[sfmi_shape_of(voff, B, v)];
     vkeep[v] = (gc >= 0 && gc < nC && keep[gc]) ? 1 : 0;
   } else if (t < (long long)V + T) {
     const int j = (int)(t - V), lab = flabel[j];
-    const int gc = lab < 0 ? -1 : lab + coff[cc_shape_of(toff, B, j)];
+    const int gc = lab < 0 ? -1 : lab + coff[sfmi_shape_of(toff, B, j)];
     fkeep[j] = (gc >= 0 && gc < nC && keep[gc]) ? 1 : 0;
   }
 }
@@ -252,13 +204,11 @@ __global__ __launch_bounds__(256) void cc_emit_kernel(const float* __restrict__ 
     if (!fkeep[j]) return;
     const int dst = fincl[j] - 1;
     if (dst < 0 || dst >= nTo) return;
-    const int b = cc_shape_of(toff, B, j), vb = voff[b], nb = nvoff[b];
+    const int b = sfmi_shape_of(toff, B, j), vb = voff[b], nb = nvoff[b];
 #pragma unroll
     for (int k = 0; k < 3; ++k) out_f[3ll * dst + k] = vincl[vb + faces[3ll * j + k]] - 1 - nb;
   }
 }
-
-inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 inline bool cc_sizes(int B, int V, int T) {
   return B > 0 && V >= 0 && T >= 0 && (long long)V + T + B < (1ll << 31) && 3ll * T < (1ll << 31);
@@ -276,7 +226,7 @@ int sfmi_cc_init_f32(const float* verts, const int* faces, const int* voff, cons
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(flags, 0, (size_t)B * 4, st);
   if (V > 0) hipMemsetAsync(ref, 0, (size_t)V, st);
-  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks((long long)V + T + B)), dim3(256), 0, st, verts, faces, voff, toff, B, V, T, parent, flags);
+  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks256((long long)V + T + B)), dim3(256), 0, st, verts, faces, voff, toff, B, V, T, parent, flags);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -285,7 +235,7 @@ int sfmi_cc_hook_i32(const int* faces, const int* voff, const int* toff, const i
                      unsigned char* ref, void* stream) {
   if (!cc_sizes(B, V, T) || !voff || !toff || !flags || (T > 0 && (!faces || !parent || !ref))) return SFMI_EINVAL;
   if (T == 0 || V == 0) return SFMI_OK;
-  hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks(T)), dim3(256), 0, (hipStream_t)stream, faces, voff, toff, flags, B, T, parent, ref);
+  hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks256(T)), dim3(256), 0, (hipStream_t)stream, faces, voff, toff, flags, B, T, parent, ref);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -293,7 +243,7 @@ int sfmi_cc_hook_i32(const int* faces, const int* voff, const int* toff, const i
 int sfmi_cc_flatten_i32(const int* parent, const unsigned char* ref, int V, int* root, int* isroot, void* stream) {
   if (V < 0 || (V > 0 && (!parent || !ref || !root || !isroot))) return SFMI_EINVAL;
   if (V == 0) return SFMI_OK;
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks(V)), dim3(256), 0, (hipStream_t)stream, parent, ref, V, root, isroot);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks256(V)), dim3(256), 0, (hipStream_t)stream, parent, ref, V, root, isroot);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -303,7 +253,7 @@ int sfmi_cc_number_i32(const int* faces, const int* voff, const int* toff, const
                        void* stream) {
   if (!cc_sizes(B, V, T) || !voff || !toff || !flags || !coff || !status) return SFMI_EINVAL;
   if ((V > 0 && (!root || !ref || !rank || !vlabel || !vkey)) || (T > 0 && (!faces || !flabel || !fkey))) return SFMI_EINVAL;
-  hipLaunchKernelGGL(cc_number_kernel, dim3(blocks((long long)V + T + B)), dim3(256), 0, (hipStream_t)stream, faces, voff, toff, flags, root, ref,
+  hipLaunchKernelGGL(cc_number_kernel, dim3(blocks256((long long)V + T + B)), dim3(256), 0, (hipStream_t)stream, faces, voff, toff, flags, root, ref,
                      rank, coff, B, V, T, vlabel, flabel, vkey, fkey, status);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -327,7 +277,7 @@ int sfmi_cc_mark_i32(const int* vlabel, const int* flabel, const int* voff, cons
   if (!cc_sizes(B, V, T) || nC < 1 || !voff || !toff || !coff || !keep || (V > 0 && (!vlabel || !vkeep)) || (T > 0 && (!flabel || !fkeep)))
     return SFMI_EINVAL;
   if (V + T == 0) return SFMI_OK;
-  hipLaunchKernelGGL(cc_mark_kernel, dim3(blocks((long long)V + T)), dim3(256), 0, (hipStream_t)stream, vlabel, flabel, voff, toff, coff, keep, B,
+  hipLaunchKernelGGL(cc_mark_kernel, dim3(blocks256((long long)V + T)), dim3(256), 0, (hipStream_t)stream, vlabel, flabel, voff, toff, coff, keep, B,
                      V, T, nC, vkeep, fkeep);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -340,7 +290,7 @@ int sfmi_cc_emit_f32(const float* verts, const int* faces, const int* voff, cons
   if ((V > 0 && (!verts || !vkeep || !vincl)) || (T > 0 && (!faces || !fkeep || !fincl)) || (nVo > 0 && !out_v) || (nTo > 0 && !out_f))
     return SFMI_EINVAL;
   if (nVo + nTo == 0) return SFMI_OK;
-  hipLaunchKernelGGL(cc_emit_kernel, dim3(blocks((long long)V + T)), dim3(256), 0, (hipStream_t)stream, verts, faces, voff, toff, vkeep, fkeep,
+  hipLaunchKernelGGL(cc_emit_kernel, dim3(blocks256((long long)V + T)), dim3(256), 0, (hipStream_t)stream, verts, faces, voff, toff, vkeep, fkeep,
                      vincl, fincl, nvoff, B, V, T, nVo, nTo, out_v, out_f);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

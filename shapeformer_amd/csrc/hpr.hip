@@ -29,7 +29,7 @@
 //    a tolerance, never by `> 0`.
 // 3. Resample for the selector: row k of shape b is the floor(u n_vis)-th visible point in ascending index order, u a counter
 //    hash of (seed, shape, k); optional hash-normal jitter clipped to [-1, 1] (partial.py's _jitter); n_vis <= 2: all points.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
 
 namespace {
 
@@ -40,19 +40,6 @@ constexpr double HPR_PAR_REL = 1e-13;  // a determinant this small against its t
 constexpr int HV_WAVES = 4;            // points (waves) per workgroup of the visibility launch
 constexpr int HV_UN = 4;               // 64-constraint chunks in flight per wave
 constexpr int HS_THREADS = 1024;
-
-__host__ __device__ inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
-// largest b in [0, B) with off[b] <= x (off nondecreasing, off[0] <= x < off[B])
-__device__ __forceinline__ int owner(const long long* __restrict__ off, int B, long long x) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // ---- setup ------------------------------------------------------------------------------------------------------------------
 
@@ -115,7 +102,7 @@ __global__ void hpr_flip_kernel(const T* __restrict__ X, const long long* __rest
 #pragma clang fp contract(off)
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const int b = owner(off, B, i);
+  const int b = sfmi_owner(off, B, i);
   const long long s0 = off[b], nb = off[b + 1] - s0;
   long long o = order ? (long long)order[i] : i - s0;            // slot i of the constraint order holds point o of its shape
   o = o < 0 ? 0 : (o >= nb ? nb - 1 : o);                        // a bad entry stays inside the shape
@@ -155,17 +142,6 @@ __device__ __forceinline__ void constraint(const Basis& s, double gx, double gy,
   ga = d2 * r;
 }
 
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // the r-th 64-slot chunk of a point's constraint sequence: its own chunk ci, then outwards ci + 1, ci - 1, ci + 2, ... and, once one
 // end of the shape is reached, on along the other side
 __device__ __forceinline__ int chunk_at(int r, int ci, int nch) {
@@ -185,7 +161,7 @@ __global__ __launch_bounds__(HV_WAVES * 64) void hpr_visible_kernel(const double
   // the wave index through readfirstlane: everything derived from it (shape, slot, chunk sequence, loop bounds) stays in scalar registers
   const long long i = (long long)blockIdx.x * HV_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (i >= N) return;
-  const int b = owner(off, B, i);
+  const int b = sfmi_owner(off, B, i);
   const long long s0 = off[b];
   const int n = (int)(off[b + 1] - s0), li = (int)(i - s0);      // N_b < 2^31 (checked on the host)
   const int* __restrict__ O = orig + s0;
@@ -400,7 +376,7 @@ extern "C" {
 // workspace: flipped x | y | z (N f64 each, in constraint order) | R (B f64) | the point of each slot (N int32)
 size_t sfmi_hpr_workspace_bytes(int B, long long N) {
   if (B <= 0 || N < 0) return 0;
-  return 3 * al((size_t)(N > 0 ? N : 1) * 8) + al((size_t)B * 8) + al((size_t)(N > 0 ? N : 1) * 4);
+  return 3 * align256((size_t)(N > 0 ? N : 1) * 8) + align256((size_t)B * 8) + align256((size_t)(N > 0 ? N : 1) * 4);
 }
 
 int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const double* cam, const int* order, int B, long long N, double param,
@@ -408,10 +384,10 @@ int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const doub
   if (B <= 0 || N < 0 || N >= (1ll << 31) || !off || !cam || !count || !status || !workspace) return SFMI_EINVAL;
   if (N > 0 && (!X || !visible)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const size_t comp = al((size_t)(N > 0 ? N : 1) * 8);
+  const size_t comp = align256((size_t)(N > 0 ? N : 1) * 8);
   char* ws = (char*)workspace;
   double *fx = (double*)ws, *fy = (double*)(ws + comp), *fz = (double*)(ws + 2 * comp), *R = (double*)(ws + 3 * comp);
-  int* orig = (int*)(ws + 3 * comp + al((size_t)B * 8));
+  int* orig = (int*)(ws + 3 * comp + align256((size_t)B * 8));
   if (N > 0 && order) (void)hipMemsetAsync(visible, 0, (size_t)N, st);     // an `order` that is no permutation leaves no byte unwritten
   const double scale = pow(10.0, param);
   const unsigned fb = (unsigned)cdiv(N, 256), vb = (unsigned)cdiv(N, HV_WAVES);

@@ -17,7 +17,7 @@
 //   mc_emit   vertices by (shape, p, axis), triangles by (shape, cell p, table order): the dense order of csrc/mcubes.hip, the vertex
 //             id of an edge found through its low point's slot, and the same vertex expressions
 // Integer atomicOr only: the result does not depend on the order in which threads run.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
 
 namespace {
 #include "mc_table.h"   // internal linkage: csrc/mcubes.hip owns the exported copy
@@ -26,12 +26,6 @@ struct IsoLat {
   int B, Q;
   unsigned W;   // bitmap words per shape
 };
-
-__device__ __forceinline__ int iso_shape_of(const int* __restrict__ off, int B, int j) {
-  int b = 0;
-  for (int i = 1; i < B; ++i) b += (j >= off[i]);
-  return b;
-}
 
 // slot of key p of shape b in the batch-wide ascending list: inclusive count up to p's word minus the bits at or above p
 __device__ __forceinline__ int iso_slot(const IsoLat g, const unsigned* __restrict__ bits, const int* __restrict__ rank, int b, int p, int n) {
@@ -98,7 +92,7 @@ __global__ __launch_bounds__(256) void iso_carry_kernel(IsoLat g, const int* __r
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   const int p = keys[j];
-  const unsigned w = (unsigned)iso_shape_of(off, g.B, j) * g.W + ((unsigned)p >> 5);
+  const unsigned w = (unsigned)sfmi_shape_of(off, g.B, j) * g.W + ((unsigned)p >> 5);
   const unsigned up = bits[w] >> (p & 31);
   dst[j] = (up & 1) ? rank[w] - __popc(up) : -1;
 }
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void iso_classify_kernel(IsoLat g, const int* 
                                                            const float* __restrict__ vals, int nP, float iso, unsigned char* __restrict__ flag) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= nC) return;
-  const int ci = iso_cube_index(g, pbits, prank, vals, nP, iso, iso_shape_of(coff, g.B, j), cells[j], s);
+  const int ci = iso_cube_index(g, pbits, prank, vals, nP, iso, sfmi_shape_of(coff, g.B, j), cells[j], s);
   flag[j] = (unsigned char)(ci == 255 ? 0 : ci);   // the cube index of a cut cell (1..254), 0 where the cell is not cut
 }
 
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(256) void iso_refine_kernel(IsoLat g, const int* __
                                                          unsigned* __restrict__ pbits, unsigned* __restrict__ cbits) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= nC || !flag[j]) return;
-  const int b = iso_shape_of(coff, g.B, j);
+  const int b = sfmi_shape_of(coff, g.B, j);
   const unsigned p = (unsigned)cells[j], uq = (unsigned)g.Q;
   const unsigned r = p / uq;
   const int i2 = (int)(p - r * uq), i0 = (int)(r / uq), i1 = (int)(r - (unsigned)i0 * uq);
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(256) void iso_mc_count_kernel(IsoLat g, const int* 
   const int ci = flag[j];                  // the cube index classify stored
   ntri[j] = MC_NTRI[ci];
   if (!ci) return;
-  const int b = iso_shape_of(coff, g.B, j), p = cells[j];
+  const int b = sfmi_shape_of(coff, g.B, j), p = cells[j];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(256) void iso_mc_verts_kernel(IsoLat g, const int* 
   idx[2] = (int)(p - r * uq); idx[0] = (int)(r / uq); idx[1] = (int)(r - (unsigned)idx[0] * uq);
   if (idx[a] + 1 >= g.Q) return;
   const int step = a == 0 ? g.Q * g.Q : (a == 1 ? g.Q : 1);
-  const int b = iso_shape_of(poff, g.B, j);
+  const int b = sfmi_shape_of(poff, g.B, j);
   const float f0 = vals[j], f1 = vals[iso_slot(g, pbits, prank, b, (int)p + step, nP)];
   const float t = __fdiv_rn(iso - f0, f1 - f0);
   float* o = verts + 3ll * (vincl[j] - __popc(m) + __popc(m & ((1 << a) - 1)));
@@ -233,7 +227,7 @@ __global__ __launch_bounds__(256) void iso_mc_faces_kernel(IsoLat g, const int* 
   const int ci = flag[j];
   const int nt = MC_NTRI[ci];
   if (!nt) return;
-  const int b = iso_shape_of(coff, g.B, j), p = cells[j];
+  const int b = sfmi_shape_of(coff, g.B, j), p = cells[j];
   const int vbase = voff[b];
   int* o = faces + 3ll * (tincl[j] - nt);
   for (int k = 0; k < 3 * nt; ++k) {
@@ -247,8 +241,6 @@ __global__ __launch_bounds__(256) void iso_mc_faces_kernel(IsoLat g, const int* 
   }
 }
 
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 // Q = (Q0-1) 2^L + 1, Q0 >= 2, L >= 1, Q^3 < 2^31, B >= 1 and the batch's bitmap words countable in 32 bits
 inline bool iso_ok(int B, int Q0, int L, int Q) {
   if (B <= 0 || Q0 < 2 || L < 1 || L > 30 || Q < 3) return false;
@@ -257,7 +249,6 @@ inline bool iso_ok(int B, int Q0, int L, int Q) {
   return (long long)B * (((long long)Q * Q * Q + 31) >> 5) < (1ll << 31);
 }
 inline IsoLat iso_lat(int B, int Q) { return IsoLat{B, Q, (unsigned)(((long long)Q * Q * Q + 31) >> 5)}; }
-inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
@@ -266,7 +257,7 @@ extern "C" {
 // [point bits | point rank | cell bits | cell rank], a quarter of the size each
 size_t sfmi_iso_sparse_workspace_bytes(int B, int Q) {
   if (B <= 0 || Q < 2 || (long long)Q * Q * Q >= (1ll << 31)) return 0;
-  return 4 * al((size_t)B * iso_lat(B, Q).W * 4);
+  return 4 * align256((size_t)B * iso_lat(B, Q).W * 4);
 }
 
 int sfmi_iso_seed_i32(int B, int Q0, int L, int Q, unsigned* pbits, unsigned* cbits, void* stream) {
@@ -275,7 +266,7 @@ int sfmi_iso_seed_i32(int B, int Q0, int L, int Q, unsigned* pbits, unsigned* cb
   const IsoLat g = iso_lat(B, Q);
   hipMemsetAsync(pbits, 0, (size_t)B * g.W * 4, st);
   hipMemsetAsync(cbits, 0, (size_t)B * g.W * 4, st);
-  hipLaunchKernelGGL(iso_seed_kernel, dim3(blocks((long long)B * Q0 * Q0 * Q0)), dim3(256), 0, st, g, Q0, 1 << L, pbits, cbits);
+  hipLaunchKernelGGL(iso_seed_kernel, dim3(blocks256((long long)B * Q0 * Q0 * Q0)), dim3(256), 0, st, g, Q0, 1 << L, pbits, cbits);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -283,7 +274,7 @@ int sfmi_iso_seed_i32(int B, int Q0, int L, int Q, unsigned* pbits, unsigned* cb
 int sfmi_iso_popc_i32(const unsigned* bits, int* cnt, int B, int Q0, int L, int Q, void* stream) {
   if (!bits || !cnt || !iso_ok(B, Q0, L, Q)) return SFMI_EINVAL;
   const IsoLat g = iso_lat(B, Q);
-  hipLaunchKernelGGL(iso_popc_kernel, dim3(blocks((long long)B * g.W)), dim3(256), 0, (hipStream_t)stream, bits, cnt, (unsigned)B * g.W);
+  hipLaunchKernelGGL(iso_popc_kernel, dim3(blocks256((long long)B * g.W)), dim3(256), 0, (hipStream_t)stream, bits, cnt, (unsigned)B * g.W);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -292,7 +283,7 @@ int sfmi_iso_compact_i32(const unsigned* bits, const int* rank, int B, int Q0, i
   if (!bits || !rank || !iso_ok(B, Q0, L, Q) || n < 0 || (n > 0 && !keys)) return SFMI_EINVAL;
   if (n == 0) return SFMI_OK;
   const IsoLat g = iso_lat(B, Q);
-  hipLaunchKernelGGL(iso_compact_kernel, dim3(blocks((long long)B * g.W)), dim3(256), 0, (hipStream_t)stream, g, bits, rank, keys, n);
+  hipLaunchKernelGGL(iso_compact_kernel, dim3(blocks256((long long)B * g.W)), dim3(256), 0, (hipStream_t)stream, g, bits, rank, keys, n);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -301,7 +292,7 @@ int sfmi_iso_carry_i32(const int* keys, const int* off, int n, const unsigned* b
                        void* stream) {
   if (!iso_ok(B, Q0, L, Q) || n < 0 || !off || !bits || !rank || (n > 0 && (!keys || !dst))) return SFMI_EINVAL;
   if (n == 0) return SFMI_OK;
-  hipLaunchKernelGGL(iso_carry_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, iso_lat(B, Q), keys, off, n, bits, rank, dst);
+  hipLaunchKernelGGL(iso_carry_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, iso_lat(B, Q), keys, off, n, bits, rank, dst);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -309,7 +300,7 @@ int sfmi_iso_carry_i32(const int* keys, const int* off, int n, const unsigned* b
 int sfmi_iso_carry_apply_f32(const int* dst, const float* old, int n, float* vals, unsigned char* known, int n_new, void* stream) {
   if (n < 0 || n_new < 0 || (n > 0 && (!dst || !old || !vals || !known))) return SFMI_EINVAL;
   if (n == 0 || n_new == 0) return SFMI_OK;
-  hipLaunchKernelGGL(iso_carry_apply_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, dst, old, n, vals, known, n_new);
+  hipLaunchKernelGGL(iso_carry_apply_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, dst, old, n, vals, known, n_new);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -317,7 +308,7 @@ int sfmi_iso_carry_apply_f32(const int* dst, const float* old, int n, float* val
 int sfmi_iso_select_i32(const unsigned char* known, const int* uincl, int n, int* sel, int n_sel, void* stream) {
   if (n < 0 || n_sel < 0 || (n > 0 && (!known || !uincl)) || (n_sel > 0 && !sel)) return SFMI_EINVAL;
   if (n == 0 || n_sel == 0) return SFMI_OK;
-  hipLaunchKernelGGL(iso_select_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, known, uincl, n, sel, n_sel);
+  hipLaunchKernelGGL(iso_select_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, known, uincl, n, sel, n_sel);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -327,7 +318,7 @@ int sfmi_iso_classify_f32(const int* cells, const int* coff, int nC, int level, 
   if (!iso_ok(B, Q0, L, Q) || level < 0 || level > L || nC < 0 || nP < 0 || !coff || !pbits || !prank) return SFMI_EINVAL;
   if (nC > 0 && (!cells || !vals || !flag || nP == 0)) return SFMI_EINVAL;
   if (nC == 0) return SFMI_OK;
-  hipLaunchKernelGGL(iso_classify_kernel, dim3(blocks(nC)), dim3(256), 0, (hipStream_t)stream, iso_lat(B, Q), cells, coff, nC, 1 << (L - level),
+  hipLaunchKernelGGL(iso_classify_kernel, dim3(blocks256(nC)), dim3(256), 0, (hipStream_t)stream, iso_lat(B, Q), cells, coff, nC, 1 << (L - level),
                      pbits, prank, vals, nP, iso, flag);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -342,7 +333,7 @@ int sfmi_iso_refine_i32(const int* cells, const int* coff, const unsigned char* 
   hipMemsetAsync(pbits, 0, (size_t)B * g.W * 4, st);
   hipMemsetAsync(cbits, 0, (size_t)B * g.W * 4, st);
   if (nC > 0)
-    hipLaunchKernelGGL(iso_refine_kernel, dim3(blocks(nC)), dim3(256), 0, st, g, cells, coff, flag, nC, 1 << (L - level), margin, pbits, cbits);
+    hipLaunchKernelGGL(iso_refine_kernel, dim3(blocks256(nC)), dim3(256), 0, st, g, cells, coff, flag, nC, 1 << (L - level), margin, pbits, cbits);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -355,7 +346,7 @@ int sfmi_iso_mc_count_i32(const int* cells, const int* coff, const unsigned char
   hipStream_t st = (hipStream_t)stream;
   if (nP > 0) hipMemsetAsync(emask, 0, (size_t)nP * 4, st);
   if (nC > 0)
-    hipLaunchKernelGGL(iso_mc_count_kernel, dim3(blocks(nC)), dim3(256), 0, st, iso_lat(B, Q), cells, coff, flag, nC, pbits, prank, nP, emask, ntri);
+    hipLaunchKernelGGL(iso_mc_count_kernel, dim3(blocks256(nC)), dim3(256), 0, st, iso_lat(B, Q), cells, coff, flag, nC, pbits, prank, nP, emask, ntri);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -372,9 +363,9 @@ int sfmi_iso_mc_emit_f32(const int* cells, const int* coff, const unsigned char*
   hipStream_t st = (hipStream_t)stream;
   const IsoLat g = iso_lat(B, Q);
   IsoBox box{{lo0, lo1, lo2}, {hi0, hi1, hi2}};
-  hipLaunchKernelGGL(iso_mc_verts_kernel, dim3(blocks(3ll * nP)), dim3(256), 0, st, g, pkeys, poff, nP, pbits, prank, vals, iso, emask, vincl, box,
+  hipLaunchKernelGGL(iso_mc_verts_kernel, dim3(blocks256(3ll * nP)), dim3(256), 0, st, g, pkeys, poff, nP, pbits, prank, vals, iso, emask, vincl, box,
                      verts);
-  hipLaunchKernelGGL(iso_mc_faces_kernel, dim3(blocks(nC)), dim3(256), 0, st, g, cells, coff, flag, nC, pbits, prank, nP, emask, vincl, tincl, voff,
+  hipLaunchKernelGGL(iso_mc_faces_kernel, dim3(blocks256(nC)), dim3(256), 0, st, g, cells, coff, flag, nC, pbits, prank, nP, emask, vincl, tincl, voff,
                      faces);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

@@ -20,7 +20,7 @@
 //    lattice index (makeGrid 'on' mode, numpy linspace in f64, then f32).
 // 3. Merge launch, always: chunk minima in ascending chunk order with a strict `<`, W partials summed in ascending chunk order,
 //    C recomputed from the winning face, the sign applied, bad shapes overwritten.  d2, I and C do not depend on S.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
 
 namespace {
 
@@ -34,9 +34,6 @@ constexpr int SD_MIN_CHUNK = 64;                 // fewest faces (on average) pe
 template <bool OCC> struct SdR { static constexpr int R = 4; };       // queries per lane: full form
 template <> struct SdR<true> { static constexpr int R = 8; };         // winding number only
 
-__host__ __device__ inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 inline long long sd_qblocks(int B, long long N, int R) { return cdiv(N, (long long)SD_THREADS * R) + B; }
 
 inline int sd_splits(int B, long long N, long long T, int R) {
@@ -45,16 +42,6 @@ inline int sd_splits(int B, long long N, long long T, int R) {
   if (s > by_t) s = by_t;
   if (s > SD_MAX_SPLITS) s = SD_MAX_SPLITS;
   return s < 1 ? 1 : (int)s;
-}
-
-// largest b in [0, B) with off[b] <= x (off nondecreasing, off[0] <= x < off[B]): the owner of item x (empty sets skipped)
-__device__ __forceinline__ int owner(const long long* __restrict__ off, int B, long long x) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
@@ -116,7 +103,7 @@ __global__ void sdf_setup_kernel(const float* __restrict__ verts, const int* __r
                                  const long long* __restrict__ toff, int B, long long T, float4* __restrict__ rec) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  const int b = owner(toff, B, t);
+  const int b = sfmi_owner(toff, B, t);
   const long long v0 = voff[b], nv = voff[b + 1] - v0;
   float p[3][3];
   bool ok = true;
@@ -230,7 +217,7 @@ __global__ __launch_bounds__(SD_THREADS) void sdf_kernel(const float* __restrict
     pend = (long long)(b + 1) * G3;
   } else {
     if (g >= block_off[B]) return;
-    b = owner(block_off, B, g);
+    b = sfmi_owner(block_off, B, g);
     qbase = qoff[b] + (g - block_off[b]) * QB;
     pend = qoff[b + 1];
   }
@@ -319,7 +306,7 @@ __global__ void sdf_merge_kernel(const float* __restrict__ Q, const long long* _
                                  float* __restrict__ Sd, int* __restrict__ I, float* __restrict__ C, float* __restrict__ W) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const int b = owner(qoff, B, i);
+  const int b = sfmi_owner(qoff, B, i);
   const float nan = __int_as_float(0x7FC00000);
   if (status[b] != 0) {
     Sd[i] = nan;
@@ -362,13 +349,6 @@ __global__ void occ_merge_kernel(const int* __restrict__ status, long long G3, l
 
 // ---- SDF_sampling's jitter --------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // one thread per coordinate of B*n points: normal(seed, k, axis) * (k < n_near ? near_std : far_std); outside +-0.99 -> uniform
 // in [-1, 1); then clipped to +-0.99.  Sample k of a shape depends on (seed, k) only.
 __global__ void sdf_jitter_kernel(const float* __restrict__ X, int B, long long n, long long n_near, float near_std, float far_std,
@@ -377,8 +357,8 @@ __global__ void sdf_jitter_kernel(const float* __restrict__ X, int B, long long 
   if (g >= (long long)B * n * 3) return;
   const long long p = g / 3, k = p % n;
   const int a = (int)(g - 3 * p);
-  const unsigned long long s0 = mix64(seed), base = 9 * (unsigned long long)k + 3 * (unsigned long long)a;
-  const unsigned long long h1 = mix64(s0 + base), h2 = mix64(s0 + base + 1), h3 = mix64(s0 + base + 2);
+  const unsigned long long s0 = sfmi_mix64(seed), base = 9 * (unsigned long long)k + 3 * (unsigned long long)a;
+  const unsigned long long h1 = sfmi_mix64(s0 + base), h2 = sfmi_mix64(s0 + base + 1), h3 = sfmi_mix64(s0 + base + 2);
   const float u1 = (float)((h1 >> 40) + 1) * 0x1.0p-24f;     // (0, 1]
   const float u2 = (float)(h2 >> 40) * 0x1.0p-24f;           // [0, 1)
   const float z = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
@@ -391,8 +371,8 @@ size_t sdf_ws(int B, long long N, long long T, bool occ, int* splits) {
   const int R = occ ? SdR<true>::R : SdR<false>::R;
   const int S = sd_splits(B, N, T, R);
   if (splits) *splits = S;
-  size_t w = al((size_t)(B + 1) * 8) + al((size_t)(T > 0 ? T : 1) * SD_REC * 16) + al((size_t)S * N * 4);
-  if (!occ) w += 2 * al((size_t)S * N * 4);
+  size_t w = align256((size_t)(B + 1) * 8) + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16) + align256((size_t)S * N * 4);
+  if (!occ) w += 2 * align256((size_t)S * N * 4);
   return w;
 }
 
@@ -418,10 +398,10 @@ int sfmi_mesh_sdf_f32(const float* Q, const long long* qoff, const float* verts,
   sdf_ws(B, N, T, false, &splits);
   char* ws = (char*)workspace;
   long long* block_off = (long long*)ws;
-  float4* rec = (float4*)(ws + al((size_t)(B + 1) * 8));
-  float* pw = (float*)((char*)rec + al((size_t)(T > 0 ? T : 1) * SD_REC * 16));
-  float* pd = (float*)((char*)pw + al((size_t)splits * N * 4));
-  int* pi = (int*)((char*)pd + al((size_t)splits * N * 4));
+  float4* rec = (float4*)(ws + align256((size_t)(B + 1) * 8));
+  float* pw = (float*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
+  float* pd = (float*)((char*)pw + align256((size_t)splits * N * 4));
+  int* pi = (int*)((char*)pd + align256((size_t)splits * N * 4));
   if (T > 0) hipLaunchKernelGGL(sdf_setup_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, st, verts, faces, voff, toff, B, T, rec);
   hipLaunchKernelGGL(sdf_status_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, st, toff, (const float4*)rec, status);
   if (N > 0) {
@@ -447,8 +427,8 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
   int splits;
   sdf_ws(B, N, T, true, &splits);
   char* ws = (char*)workspace;
-  float4* rec = (float4*)(ws + al((size_t)(B + 1) * 8));
-  float* pw = (float*)((char*)rec + al((size_t)(T > 0 ? T : 1) * SD_REC * 16));
+  float4* rec = (float4*)(ws + align256((size_t)(B + 1) * 8));
+  float* pw = (float*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
   Lattice lat;
   lat.G = G;
   for (int a = 0; a < 3; ++a) {

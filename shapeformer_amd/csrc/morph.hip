@@ -9,15 +9,15 @@
 //   dilate    zplanes: for every row word its z-dilations by h = 0..r (shifts and ORs with the two neighbouring words) into r+1 bit planes;
 //             disc: every output word ORs plane floor(sqrt(r^2 - dx^2 - dy^2)) of row (i+dx, j+dy) over the disc dx^2 + dy^2 <= r^2.
 //             invert_in / invert_out complement the grid on the way in / out: erode(M) = NOT dilate(NOT M), border counted as set
-//   flood     the voxels whose value equals the seed voxel's are eligible.  A union-find over them in the manner of csrc/components.hip
-//             (find with path halving, the larger root linked under the smaller by compare-and-swap on the root's slot):
+//   flood     the voxels whose value equals the seed voxel's are eligible.  The union-find of csrc/sfmi_ragged.h
+//             over them; what is specific here is that a run of eligible bits inside a word is linked by its initial parents:
 //               init    one thread per voxel: parent = the start of the voxel's run of eligible bits inside its word
 //               hook    one thread per word: the run across the word boundary, and per forward row (4 of them) the links that the
 //                       runs do not already imply (of the 13 forward neighbours of 26-connectivity)
 //               region  one thread per word: a run belongs to the region iff its root is the shape's voxel 0 (the smallest index
 //                       of the shape, so the root of its tree in whatever order the hooks came)
 // Three launches for a flood whatever the grid holds; integer atomics only: every output is a function of the input bits.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"
 
 // the voxel index is the reference's f32 expression, one rounding per operation: no fused multiply-add
 #pragma clang fp contract(off)
@@ -25,32 +25,6 @@
 namespace {
 
 constexpr int MORPH_MAX_R = 16;
-
-__device__ __forceinline__ int mv_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mv_store(int* p, int x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// see cc_find / cc_hook of csrc/components.hip: parent[v] <= v always, only root slots are targets of the CAS
-__device__ __forceinline__ int mv_find(int* parent, int v) {
-  int cur = v, p = mv_load(parent + cur);
-  while (p != cur) {
-    const int g = mv_load(parent + p);
-    if (g != p) mv_store(parent + cur, g);
-    cur = p;
-    p = g;
-  }
-  return cur;
-}
-
-__device__ __forceinline__ void mv_hook(int* parent, int u, int v) {
-  int ru = mv_find(parent, u), rv = mv_find(parent, v);
-  while (ru != rv) {
-    const int hi = max(ru, rv), lo = min(ru, rv);
-    const int old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) return;
-    ru = mv_find(parent, old);
-    rv = mv_find(parent, lo);
-  }
-}
 
 // the lattice bits of word w of a row
 __device__ __forceinline__ unsigned mv_valid(int w, int G) {
@@ -65,23 +39,13 @@ __device__ __forceinline__ int mv_index(float p, int G) {
   return (int)fminf(fmaxf(rintf(s), 0.0f), (float)(G - 1));
 }
 
-// the shape b with off[b] <= t < off[b+1] (empty sets are skipped: the last b with off[b] <= t)
-__device__ __forceinline__ int mv_shape_of(const int* __restrict__ off, int B, int t) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= t) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void mv_voxelize_kernel(const float* __restrict__ pts, const int* __restrict__ off, int B, int N, int G,
                                                           int Wz, unsigned* __restrict__ bits) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= N) return;
   const float x = pts[3ll * t], y = pts[3ll * t + 1], z = pts[3ll * t + 2];
   if (!(isfinite(x) && isfinite(y) && isfinite(z))) return;
-  const int b = mv_shape_of(off, B, t);
+  const int b = sfmi_owner(off, B, t);
   const int i = mv_index(x, G), j = mv_index(y, G), k = mv_index(z, G);
   // the result is not used: the atomic is issued and not waited for.  Testing the bit first (10^6 samples fall on ~10^5 voxels) puts a
   // load's latency in front of it and was slower on batches (profiles/r17_kbench_morph.txt)
@@ -96,7 +60,7 @@ __global__ __launch_bounds__(256) void mv_lookup_kernel(const float* __restrict_
   const float x = pts[3ll * t], y = pts[3ll * t + 1], z = pts[3ll * t + 2];
   unsigned char o = 0;
   if (isfinite(x) && isfinite(y) && isfinite(z)) {
-    const int b = mv_shape_of(off, B, t);
+    const int b = sfmi_owner(off, B, t);
     const int i = mv_index(x, G), j = mv_index(y, G), k = mv_index(z, G);
     o = (unsigned char)((bits[((b * G + i) * G + j) * Wz + (k >> 5)] >> (k & 31)) & 1u);
   }
@@ -187,7 +151,7 @@ __global__ __launch_bounds__(256) void mv_flood_hook_kernel(const unsigned* __re
   const unsigned Enext = w + 1 < Wz ? mv_elig(in, t + 1, w + 1, G, seed) : 0u;
   const unsigned Em = (E << 1) | (Eprev >> 31), Ep = (E >> 1) | (Enext << 31);
   const int v0 = row * G + w * 32;
-  if ((E & 1u) && (Eprev >> 31)) mv_hook(parent, v0, v0 - 1);
+  if ((E & 1u) && (Eprev >> 31)) sfmi_uf_hook(parent, v0, v0 - 1);
   const int DI[4] = {0, 1, 1, 1}, DJ[4] = {1, -1, 0, 1};
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
@@ -200,9 +164,9 @@ __global__ __launch_bounds__(256) void mv_flood_hook_kernel(const unsigned* __re
     const unsigned Nnext = w + 1 < Wz ? mv_elig(in, nt + 1, w + 1, G, seed) : 0u;
     const unsigned Nm = (N << 1) | (Nprev >> 31), Np = (N >> 1) | (Nnext << 31);
     unsigned H0 = E & N & ~(Em & Nm), Hm = E & Nm & ~N & ~Em, Hp = E & Np & ~N & ~Ep;
-    while (H0) { const int k = __ffs(H0) - 1; H0 &= H0 - 1; mv_hook(parent, v0 + k, n0 + k); }
-    while (Hm) { const int k = __ffs(Hm) - 1; Hm &= Hm - 1; mv_hook(parent, v0 + k, n0 + k - 1); }
-    while (Hp) { const int k = __ffs(Hp) - 1; Hp &= Hp - 1; mv_hook(parent, v0 + k, n0 + k + 1); }
+    while (H0) { const int k = __ffs(H0) - 1; H0 &= H0 - 1; sfmi_uf_hook(parent, v0 + k, n0 + k); }
+    while (Hm) { const int k = __ffs(Hm) - 1; Hm &= Hm - 1; sfmi_uf_hook(parent, v0 + k, n0 + k - 1); }
+    while (Hp) { const int k = __ffs(Hp) - 1; Hp &= Hp - 1; sfmi_uf_hook(parent, v0 + k, n0 + k + 1); }
   }
 }
 
@@ -249,8 +213,6 @@ __global__ __launch_bounds__(256) void mv_unpack_kernel(const unsigned* __restri
   vox[v] = (unsigned char)((bits[row * Wz + (k >> 5)] >> (k & 31)) & 1u);
 }
 
-inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
-
 inline bool mv_sizes(int B, int G) { return B > 0 && G > 0 && (long long)B * G * G * G < (1ll << 31); }
 inline int mv_wz(int G) { return (G + 31) / 32; }
 
@@ -273,7 +235,7 @@ int sfmi_voxelize_points_f32(const float* points, const int* off, int B, long lo
   hipStream_t st = (hipStream_t)stream;
   const int Wz = mv_wz(G);
   hipMemsetAsync(bits, 0, (size_t)B * G * G * Wz * 4, st);
-  if (N > 0) hipLaunchKernelGGL(mv_voxelize_kernel, dim3(blocks(N)), dim3(256), 0, st, points, off, B, (int)N, G, Wz, bits);
+  if (N > 0) hipLaunchKernelGGL(mv_voxelize_kernel, dim3(blocks256(N)), dim3(256), 0, st, points, off, B, (int)N, G, Wz, bits);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -282,7 +244,7 @@ int sfmi_voxelize_lookup_f32(const float* points, const int* off, int B, long lo
                              void* stream) {
   if (!mv_sizes(B, G) || N < 0 || 3 * N >= (1ll << 31) || !off || !bits || (N > 0 && (!points || !out))) return SFMI_EINVAL;
   if (N == 0) return SFMI_OK;
-  hipLaunchKernelGGL(mv_lookup_kernel, dim3(blocks(N)), dim3(256), 0, (hipStream_t)stream, points, off, B, (int)N, G, mv_wz(G), bits, out);
+  hipLaunchKernelGGL(mv_lookup_kernel, dim3(blocks256(N)), dim3(256), 0, (hipStream_t)stream, points, off, B, (int)N, G, mv_wz(G), bits, out);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -291,8 +253,8 @@ int sfmi_morph_dilate_u32(const unsigned* in, int B, int G, int r, int invert_in
   if (!mv_sizes(B, G) || r < 0 || r > MORPH_MAX_R || !in || !out || !ws) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int Wz = mv_wz(G), NW = B * G * G * Wz;
-  hipLaunchKernelGGL(mv_zplanes_kernel, dim3(blocks(NW)), dim3(256), 0, st, in, G, Wz, NW, r, invert_in ? 1 : 0, (unsigned*)ws);
-  hipLaunchKernelGGL(mv_disc_kernel, dim3(blocks(NW)), dim3(256), 0, st, (const unsigned*)ws, G, Wz, NW, r, invert_out ? 1 : 0, out);
+  hipLaunchKernelGGL(mv_zplanes_kernel, dim3(blocks256(NW)), dim3(256), 0, st, in, G, Wz, NW, r, invert_in ? 1 : 0, (unsigned*)ws);
+  hipLaunchKernelGGL(mv_disc_kernel, dim3(blocks256(NW)), dim3(256), 0, st, (const unsigned*)ws, G, Wz, NW, r, invert_out ? 1 : 0, out);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -302,9 +264,9 @@ int sfmi_morph_flood_u32(const unsigned* in, int B, int G, unsigned* region, int
   hipStream_t st = (hipStream_t)stream;
   const int Wz = mv_wz(G), NW = B * G * G * Wz, NV = B * G * G * G;
   int* parent = (int*)ws;
-  hipLaunchKernelGGL(mv_flood_init_kernel, dim3(blocks(NV)), dim3(256), 0, st, in, G, Wz, NV, parent);
-  hipLaunchKernelGGL(mv_flood_hook_kernel, dim3(blocks(NW)), dim3(256), 0, st, in, G, Wz, NW, parent);
-  hipLaunchKernelGGL(mv_flood_region_kernel, dim3(blocks(NW)), dim3(256), 0, st, in, (const int*)parent, G, Wz, NW, region, status);
+  hipLaunchKernelGGL(mv_flood_init_kernel, dim3(blocks256(NV)), dim3(256), 0, st, in, G, Wz, NV, parent);
+  hipLaunchKernelGGL(mv_flood_hook_kernel, dim3(blocks256(NW)), dim3(256), 0, st, in, G, Wz, NW, parent);
+  hipLaunchKernelGGL(mv_flood_region_kernel, dim3(blocks256(NW)), dim3(256), 0, st, in, (const int*)parent, G, Wz, NW, region, status);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -312,7 +274,7 @@ int sfmi_morph_flood_u32(const unsigned* in, int B, int G, unsigned* region, int
 int sfmi_morph_pack_u8(const unsigned char* vox, int B, int G, unsigned* bits, void* stream) {
   if (!mv_sizes(B, G) || !vox || !bits) return SFMI_EINVAL;
   const int Wz = mv_wz(G), NW = B * G * G * Wz;
-  hipLaunchKernelGGL(mv_pack_kernel, dim3(blocks(NW)), dim3(256), 0, (hipStream_t)stream, vox, G, Wz, NW, bits);
+  hipLaunchKernelGGL(mv_pack_kernel, dim3(blocks256(NW)), dim3(256), 0, (hipStream_t)stream, vox, G, Wz, NW, bits);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -320,7 +282,7 @@ int sfmi_morph_pack_u8(const unsigned char* vox, int B, int G, unsigned* bits, v
 int sfmi_morph_unpack_u8(const unsigned* bits, int B, int G, unsigned char* vox, void* stream) {
   if (!mv_sizes(B, G) || !vox || !bits) return SFMI_EINVAL;
   const int NV = B * G * G * G;
-  hipLaunchKernelGGL(mv_unpack_kernel, dim3(blocks(NV)), dim3(256), 0, (hipStream_t)stream, bits, G, mv_wz(G), NV, vox);
+  hipLaunchKernelGGL(mv_unpack_kernel, dim3(blocks256(NV)), dim3(256), 0, (hipStream_t)stream, bits, G, mv_wz(G), NV, vox);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

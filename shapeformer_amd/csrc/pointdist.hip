@@ -16,7 +16,7 @@
 // 2. Area-weighted surface sampling of a batch of indexed meshes: per-face areas in f64, a per-shape inclusive f64 CDF (one
 //    workgroup per shape, fixed summation order), then one thread per sample: the face by binary search on a counter-hash
 //    uniform of (seed, sample), barycentric weights 1-sqrt(u), sqrt(u)(1-v), sqrt(u) v as in geoutil.sampleMesh.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
 
 namespace {
 
@@ -28,9 +28,6 @@ constexpr int NN_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
 constexpr int NN_MAX_SPLITS = 64;
 constexpr int NN_MIN_CHUNK = 512;                // fewest Q points (on average) per chunk
 
-__host__ __device__ inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 // query-block upper bound: sum_b ceil(N_b / QB) <= ceil(N / QB) + B
 inline long long nn_qblocks(int B, long long N) { return cdiv(N, NN_QB) + B; }
 
@@ -40,16 +37,6 @@ inline int nn_splits(int B, long long N, long long M) {
   if (s > by_m) s = by_m;
   if (s > NN_MAX_SPLITS) s = NN_MAX_SPLITS;
   return s < 1 ? 1 : (int)s;
-}
-
-// largest b in [0, B) with off[b] <= x (off nondecreasing, off[0] <= x < off[B]): the owner of item x (empty sets skipped)
-__device__ __forceinline__ int owner(const long long* __restrict__ off, int B, long long x) {
-  int lo = 0, hi = B;                       // invariant: off[lo] <= x < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 // block_off[b] = sum_{b' < b} ceil(N_b' / QB): which query blocks belong to which set (one lane; B is small)
@@ -72,7 +59,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_kernel(const float* __restrict_
   __shared__ float4 tile[NN_TILE];
   const long long g = blockIdx.x;
   if (g >= block_off[B]) return;                               // block-uniform: the grid is an upper bound
-  const int b = owner(block_off, B, g);
+  const int b = sfmi_owner(block_off, B, g);
   const int tid = threadIdx.x;
   const long long pend = poff[b + 1];
   const long long qbase = poff[b] + (g - block_off[b]) * NN_QB;
@@ -144,20 +131,12 @@ __global__ void nn_merge_kernel(const float* __restrict__ pd, const int* __restr
 
 // ---- mesh sampling ---------------------------------------------------------------------------------------------------------
 
-// splitmix64 finalizer
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // per-face area (f64) of face t; a vertex index outside its shape gives NaN, which flags the shape
 __global__ void mesh_area_kernel(const float* __restrict__ verts, const int* __restrict__ faces, const long long* __restrict__ voff,
                                  const long long* __restrict__ toff, int B, long long T, double* __restrict__ area) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  const int b = owner(toff, B, t);
+  const int b = sfmi_owner(toff, B, t);
   const long long v0 = voff[b], nv = voff[b + 1] - v0;
   double p[3][3];
   bool ok = true;
@@ -222,9 +201,9 @@ __global__ void mesh_sample_kernel(const float* __restrict__ verts, const int* _
     return;
   }
   // the stream depends on (seed, k) only: shape b's samples do not depend on the batch around it
-  const unsigned long long s0 = mix64(seed);
-  const unsigned long long hf = mix64(s0 + 3 * (unsigned long long)k), hu = mix64(s0 + 3 * (unsigned long long)k + 1),
-                           hv = mix64(s0 + 3 * (unsigned long long)k + 2);
+  const unsigned long long s0 = sfmi_mix64(seed);
+  const unsigned long long hf = sfmi_mix64(s0 + 3 * (unsigned long long)k), hu = sfmi_mix64(s0 + 3 * (unsigned long long)k + 1),
+                           hv = sfmi_mix64(s0 + 3 * (unsigned long long)k + 2);
   const double target = (double)(hf >> 11) * 0x1.0p-53 * tot;
   long long lo = 0, hi = nt - 1;                               // first face with cdf > target (clamped to the last)
   while (lo < hi) {
@@ -251,8 +230,8 @@ extern "C" {
 size_t sfmi_nn_dist_workspace_bytes(int B, long long N, long long M) {
   if (B <= 0 || N < 0 || M < 0) return 0;
   const int S = nn_splits(B, N, M);
-  size_t w = al((size_t)(B + 1) * 8);
-  if (S > 1) w += 2 * al((size_t)S * N * 4);
+  size_t w = align256((size_t)(B + 1) * 8);
+  if (S > 1) w += 2 * align256((size_t)S * N * 4);
   return w;
 }
 
@@ -269,8 +248,8 @@ int sfmi_nn_dist_f32(const float* P, const float* Q, const long long* poff, cons
   if (S == 1) {
     hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)block_off, B, N, d2, idx);
   } else {
-    float* pd = (float*)((char*)workspace + al((size_t)(B + 1) * 8));
-    int* pi = (int*)((char*)pd + al((size_t)S * N * 4));
+    float* pd = (float*)((char*)workspace + align256((size_t)(B + 1) * 8));
+    int* pi = (int*)((char*)pd + align256((size_t)S * N * 4));
     hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)block_off, B, N, pd, pi);
     hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, (const float*)pd, (const int*)pi, S, N, d2, idx);
   }
@@ -281,7 +260,7 @@ int sfmi_nn_dist_f32(const float* P, const float* Q, const long long* poff, cons
 // workspace: per-face CDF (T f64)
 size_t sfmi_mesh_sample_workspace_bytes(int B, long long T) {
   if (B <= 0 || T < 0) return 0;
-  return al((size_t)(T > 0 ? T : 1) * 8);
+  return align256((size_t)(T > 0 ? T : 1) * 8);
 }
 
 int sfmi_mesh_sample_f32(const float* verts, const int* faces, const long long* voff, const long long* toff, int B, long long T,

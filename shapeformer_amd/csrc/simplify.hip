@@ -15,7 +15,7 @@
 //   emit    surviving faces, re-indexed to slots local to the shape
 // Integer atomicOr / atomicAdd only.  The solve walks each cell's records in a stably sorted order with lane l taking entries
 // l, l+64, ... and reduces with a fixed butterfly, so a cell's vertex depends on its shape alone and is the same bits every run.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
 
 // the f32 cell expression and the f64 plane terms are written once, here and in numpy: no contraction into fused multiply-adds
 #pragma clang fp contract(off)
@@ -24,20 +24,9 @@ namespace {
 
 constexpr int SIMP_GMAX = 512;
 constexpr int SIMP_NONE = 0x7fffffff;   // the slot of a flagged shape's vertices and corners: sorts behind every cell
-constexpr int SIMP_NO_VERTS = 1, SIMP_BAD_INDEX = 2, SIMP_NON_FINITE = 4;   // flag bits; the status is the lowest one set
 
 struct SimpBoxF { float lo[3], hi[3]; };
 struct SimpBoxD { double lo[3], hi[3]; };
-
-__device__ __forceinline__ int simp_shape_of(const int* __restrict__ off, int B, int j) {
-  int b = 0;
-  for (int i = 1; i < B; ++i) b += (j >= off[i]);
-  return b;
-}
-
-__device__ __forceinline__ int simp_status(int flags) {
-  return (flags & SIMP_NO_VERTS) ? 1 : ((flags & SIMP_BAD_INDEX) ? 2 : ((flags & SIMP_NON_FINITE) ? 3 : 0));
-}
 
 // threads [0,V): vertices; [V,V+T): faces; [V+T,V+T+B): shapes
 __global__ __launch_bounds__(256) void simp_cells_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -48,7 +37,7 @@ __global__ __launch_bounds__(256) void simp_cells_kernel(const float* __restrict
   const long long t = blockIdx.x * 256ll + threadIdx.x;
   unsigned w = 0xFFFFFFFFu, m = 0;      // the bit this lane has to set (m == 0: none)
   if (t < V) {
-    const int i = (int)t, b = simp_shape_of(voff, B, i);
+    const int i = (int)t, b = sfmi_shape_of(voff, B, i);
     const float p[3] = {verts[3ll * i], verts[3ll * i + 1], verts[3ll * i + 2]};
     if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
       const int G = grid[b];
@@ -66,10 +55,10 @@ __global__ __launch_bounds__(256) void simp_cells_kernel(const float* __restrict
       m = 1u << (key & 31);
     } else {
       vkey[i] = 0;
-      atomicOr(&flags[b], SIMP_NON_FINITE);
+      atomicOr(&flags[b], SFMI_MESH_NON_FINITE);
     }
   } else if (t < (long long)V + T) {
-    const int j = (int)(t - V), b = simp_shape_of(toff, B, j);
+    const int j = (int)(t - V), b = sfmi_shape_of(toff, B, j);
     const int nv = voff[b + 1] - voff[b];
     bool ok = true;
 #pragma unroll
@@ -77,10 +66,10 @@ __global__ __launch_bounds__(256) void simp_cells_kernel(const float* __restrict
       const int a = faces[3ll * j + k];
       ok = ok && a >= 0 && a < nv;
     }
-    if (!ok) atomicOr(&flags[b], SIMP_BAD_INDEX);
+    if (!ok) atomicOr(&flags[b], SFMI_MESH_BAD_INDEX);
   } else if (t < (long long)V + T + B) {
     const int b = (int)(t - V - T);
-    if (voff[b + 1] <= voff[b]) atomicOr(&flags[b], SIMP_NO_VERTS);
+    if (voff[b + 1] <= voff[b]) atomicOr(&flags[b], SFMI_MESH_NO_VERTS);
   }
   // Mesh vertices come in lattice order, so on a coarse grid whole runs of lanes name the same bit, and before the first atomicOr
   // lands every thread in flight would issue its own on a handful of words.  A lane whose left neighbour names the same bit leaves
@@ -93,9 +82,9 @@ __global__ __launch_bounds__(256) void simp_popc_kernel(const unsigned* __restri
                                                         const int* __restrict__ woff, int B, int nW, int* __restrict__ cnt,
                                                         int* __restrict__ status) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < B) status[i] = simp_status(flags[i]);
+  if (i < B) status[i] = sfmi_mesh_status(flags[i]);
   if (i >= nW) return;
-  cnt[i] = flags[simp_shape_of(woff, B, i)] ? 0 : __popc(bits[i]);
+  cnt[i] = flags[sfmi_shape_of(woff, B, i)] ? 0 : __popc(bits[i]);
 }
 
 // vslot[i] = the batch-wide slot of vertex i's cell (inclusive count up to the key's word minus the bits at or above it), SIMP_NONE for
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256) void simp_slots_kernel(const int* __restrict__
                                                          int* __restrict__ vslot) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= V) return;
-  const int b = simp_shape_of(voff, B, i);
+  const int b = sfmi_shape_of(voff, B, i);
   if (flags[b]) { vslot[i] = SIMP_NONE; return; }
   const int key = vkey[i];
   const unsigned w = (unsigned)woff[b] + ((unsigned)key >> 5);
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(256) void simp_faces_kernel(const int* __restrict__
   int b = -1;
   bool keep = false;
   if (j < T) {
-    b = simp_shape_of(toff, B, j);
+    b = sfmi_shape_of(toff, B, j);
     int s[3] = {SIMP_NONE, SIMP_NONE, SIMP_NONE};
     if (!flags[b]) {           // the indices of an unflagged shape are all inside it
       const int vb = voff[b];
@@ -142,12 +131,6 @@ __global__ __launch_bounds__(256) void simp_faces_kernel(const int* __restrict__
   if (keep && b != b0) atomicAdd(&count[b], 1);
 }
 
-__device__ __forceinline__ double simp_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one wave64 per cell.  vorder / corder: the vertices / the corner records (3 f + k) stably sorted by slot; vseg / cseg (nC+1): where
 // each cell's run starts.  Every cell holds at least one vertex, which names its shape and key.
 __global__ __launch_bounds__(256) void simp_solve_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -162,7 +145,7 @@ __global__ __launch_bounds__(256) void simp_solve_kernel(const float* __restrict
   const int v0 = vseg[c], v1 = vseg[c + 1];
   if (v1 <= v0) return;
   const int first = vorder[v0];
-  const int b = simp_shape_of(voff, B, first);
+  const int b = sfmi_shape_of(voff, B, first);
   const int G = min(max(grid[b], 1), SIMP_GMAX), key = vkey[first], vb = voff[b];
   const int cc[3] = {key / (G * G), (key / G) % G, key % G};
   double h[3], ctr[3];
@@ -190,10 +173,10 @@ __global__ __launch_bounds__(256) void simp_solve_kernel(const float* __restrict
     a00 += n0 * n0; a01 += n0 * n1; a02 += n0 * n2; a11 += n1 * n1; a12 += n1 * n2; a22 += n2 * n2;
     b0 += d * n0; b1 += d * n1; b2 += d * n2;
   }
-  m0 = simp_wave_sum(m0); m1 = simp_wave_sum(m1); m2 = simp_wave_sum(m2);
-  a00 = simp_wave_sum(a00); a01 = simp_wave_sum(a01); a02 = simp_wave_sum(a02);
-  a11 = simp_wave_sum(a11); a12 = simp_wave_sum(a12); a22 = simp_wave_sum(a22);
-  b0 = simp_wave_sum(b0); b1 = simp_wave_sum(b1); b2 = simp_wave_sum(b2);
+  m0 = wave_sum_f64(m0); m1 = wave_sum_f64(m1); m2 = wave_sum_f64(m2);
+  a00 = wave_sum_f64(a00); a01 = wave_sum_f64(a01); a02 = wave_sum_f64(a02);
+  a11 = wave_sum_f64(a11); a12 = wave_sum_f64(a12); a22 = wave_sum_f64(a22);
+  b0 = wave_sum_f64(b0); b1 = wave_sum_f64(b1); b2 = wave_sum_f64(b2);
   if (lane) return;
   const double nv = (double)(v1 - v0);
   const double m[3] = {m0 / nv, m1 / nv, m2 / nv};
@@ -230,12 +213,10 @@ __global__ __launch_bounds__(256) void simp_emit_kernel(const int* __restrict__ 
   if (j >= T || !surv[j]) return;
   const int dst = sincl[j] - 1;
   if (dst < 0 || dst >= nS) return;
-  const int b = simp_shape_of(toff, B, j), vb = voff[b], cb = coff[b];
+  const int b = sfmi_shape_of(toff, B, j), vb = voff[b], cb = coff[b];
 #pragma unroll
   for (int k = 0; k < 3; ++k) out[3ll * dst + k] = vslot[vb + faces[3ll * j + k]] - cb;
 }
-
-inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 // every G in [1, 512]; -> the bit sets' words, or -1
 inline long long simp_words(const int* grid_host, int B) {
@@ -277,7 +258,7 @@ int sfmi_simplify_cells_f32(const float* verts, const int* faces, const int* vof
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(bits, 0, (size_t)nW * 4, st);
   hipMemsetAsync(flags, 0, (size_t)B * 4, st);
-  hipLaunchKernelGGL(simp_cells_kernel, dim3(blocks((long long)V + T + B)), dim3(256), 0, st, verts, faces, voff, toff, grid, woff, B, V, T, box,
+  hipLaunchKernelGGL(simp_cells_kernel, dim3(blocks256((long long)V + T + B)), dim3(256), 0, st, verts, faces, voff, toff, grid, woff, B, V, T, box,
                      vkey, bits, flags);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -287,7 +268,7 @@ int sfmi_simplify_popc_i32(const unsigned* bits, const int* flags, const int* wo
                            void* stream) {
   const long long nW = simp_words(grid_host, B);
   if (nW < 0 || !bits || !flags || !woff || !cnt || !status) return SFMI_EINVAL;
-  hipLaunchKernelGGL(simp_popc_kernel, dim3(blocks(nW)), dim3(256), 0, (hipStream_t)stream, bits, flags, woff, B, (int)nW, cnt, status);
+  hipLaunchKernelGGL(simp_popc_kernel, dim3(blocks256(nW)), dim3(256), 0, (hipStream_t)stream, bits, flags, woff, B, (int)nW, cnt, status);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -297,7 +278,7 @@ int sfmi_simplify_slots_i32(const int* vkey, const int* voff, const int* woff, c
   if (simp_words(grid_host, B) < 0 || V < 0 || !voff || !woff || !bits || !rank || !flags || (V > 0 && (!vkey || !vslot)))
     return SFMI_EINVAL;
   if (V == 0) return SFMI_OK;
-  hipLaunchKernelGGL(simp_slots_kernel, dim3(blocks(V)), dim3(256), 0, (hipStream_t)stream, vkey, voff, woff, bits, rank, flags, B, V, vslot);
+  hipLaunchKernelGGL(simp_slots_kernel, dim3(blocks256(V)), dim3(256), 0, (hipStream_t)stream, vkey, voff, woff, bits, rank, flags, B, V, vslot);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -309,7 +290,7 @@ int sfmi_simplify_faces_i32(const int* faces, const int* voff, const int* toff, 
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(count, 0, (size_t)B * 4, st);
   if (T > 0)
-    hipLaunchKernelGGL(simp_faces_kernel, dim3(blocks(T)), dim3(256), 0, st, faces, voff, toff, vslot, flags, B, T, cslot, surv, count);
+    hipLaunchKernelGGL(simp_faces_kernel, dim3(blocks256(T)), dim3(256), 0, st, faces, voff, toff, vslot, flags, B, T, cslot, surv, count);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -332,7 +313,7 @@ int sfmi_simplify_emit_i32(const int* faces, const int* voff, const int* toff, c
   if (B <= 0 || T < 0 || nS < 0 || !voff || !toff || !coff || (T > 0 && (!faces || !vslot || !surv || !sincl)) || (nS > 0 && !out))
     return SFMI_EINVAL;
   if (T == 0 || nS == 0) return SFMI_OK;
-  hipLaunchKernelGGL(simp_emit_kernel, dim3(blocks(T)), dim3(256), 0, (hipStream_t)stream, faces, voff, toff, vslot, surv, sincl, coff, B, T, nS,
+  hipLaunchKernelGGL(simp_emit_kernel, dim3(blocks256(T)), dim3(256), 0, (hipStream_t)stream, faces, voff, toff, vslot, surv, sincl, coff, B, T, nS,
                      out);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

@@ -13,7 +13,7 @@ point; this module hands the kernel a Morton order of the viewing directions to 
 Exact duplicate points: the lowest index of a class of bitwise-equal points represents it (qhull reports one arbitrary member).
 status per shape: 0 ok, 1 fewer than 4 points, 2 a non-finite coordinate, 3 a point at the camera (mask all zero).
 The resample and jitter draws are counter hashes of (seed, shape index, row): they touch no global RNG, and a batch equals per-shape
-calls (`shape0` names the index of the first shape).
+calls (`shape0` names the index of the first shape).  Ragged batches and their argument checks are _ragged.py's.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .metrics import _host_offsets, _on_device, _points
+from ._ragged import on_device, point_sets
 
 
 def _cams(cams, B, what):
@@ -36,19 +36,12 @@ def _cams(cams, B, what):
 
 def _prepare(points, cams, off, what):
     """-> (flat (N,3) f32 / f64 contiguous device tensor, host offsets, host cameras (B,3) f64, batch shape or None)."""
-    x = _points(points, what)
-    if x.dim() == 3:
-        if off is not None:
-            raise L.SfmiError(f"{what}: a (B,N,3) batch takes no offsets")
-        shape = (x.shape[0], x.shape[1])
-        o = np.arange(shape[0] + 1, dtype=np.int64) * shape[1]
-    else:
-        shape, o = None, _host_offsets(off, x.shape[0], f"{what} off")
+    x, o, shape = point_sets(points, off, what)
     c = _cams(cams, len(o) - 1, what)
-    _on_device(what, x)
+    on_device(what, x)
     if x.dtype not in (torch.float32, torch.float64):
         x = x.float()
-    return x.reshape(-1, 3).contiguous(), o, c, shape
+    return x.contiguous(), o, c, shape
 
 
 def _spread16(v):

@@ -4,7 +4,8 @@ The reference meshes a dense lattice only (xgutils/geoutil.py:175-233 array2mesh
 vqdif.py:60-76).  Here the field is evaluated on a coarse lattice first and only around the cells the surface passes through at
 each finer level, so a mesh at 257^3 or 513^3 costs what its surface costs.  The contract (lattice, hierarchy, mesh order) is in
 include/sfmi.h; the result equals `marching_cubes_dev` on the dense Q^3 grid restricted to the cut cells that were reached, bit for
-bit, and the whole dense mesh where every cut cell was reached.  There is no CPU fallback.
+bit, and the whole dense mesh where every cut cell was reached.  There is no CPU fallback.  The ragged-batch idioms (prefix sums at
+offsets) are _ragged.py's.
 
   extract_sparse_dev(field, B, coarse_Q, levels, ...) -> verts, faces, voff, toff [, info]
   table_field(F)                                      -> a field that gathers from a dense (B,Q,Q,Q) device tensor
@@ -16,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._ragged import excl_at
 
 
 def lattice_levels(res, coarse):
@@ -75,11 +77,6 @@ class _BitSet:
         k = torch.empty(max(n, 1), device=self.bits.device, dtype=torch.int32)
         L.check(lib.sfmi_iso_compact_i32(L.ptr(self.bits), L.ptr(self.rank), *lat, L.ptr(k), n, L.stream_ptr()), "sfmi_iso_compact_i32")
         return k[:n]
-
-
-def _excl_at(incl, off):
-    """exclusive prefix at the (B+1) offsets `off` of an inclusive prefix sum (its total at off[B])"""
-    return torch.cat([incl.new_zeros(1), incl])[off.long()]
 
 
 def extract_sparse_dev(field, B, coarse_Q, levels, thresh=0.5, margin=1, bbox=((-1.0,) * 3, (1.0,) * 3), return_levels=False, device="cuda"):
@@ -147,7 +144,7 @@ def extract_sparse_dev(field, B, coarse_Q, levels, thresh=0.5, margin=1, bbox=((
         info["points"].append(np.diff(he))
         if return_levels:
             mincl = torch.cumsum(flag[:nC] != 0, 0, dtype=torch.int32)
-            moff = _excl_at(mincl, coff)
+            moff = excl_at(mincl, coff)
             info["S"].append((cells, hc.copy()))
         else:
             moff = coff.new_zeros(B + 1)
@@ -158,7 +155,7 @@ def extract_sparse_dev(field, B, coarse_Q, levels, thresh=0.5, margin=1, bbox=((
             dst = torch.full((max(nP, 1),), -1, device=dev, dtype=torch.int32)
             L.check(lib.sfmi_iso_carry_i32(L.ptr(pkeys), L.ptr(old_poff), nP, L.ptr(pts.bits), L.ptr(pts.rank), *lat, L.ptr(dst), st()),
                     "sfmi_iso_carry_i32")
-            hoff = _excl_at(torch.cumsum(dst[:nP] >= 0, 0, dtype=torch.int32), old_poff)
+            hoff = excl_at(torch.cumsum(dst[:nP] >= 0, 0, dtype=torch.int32), old_poff)
             h = torch.cat([poff, coff, moff, hoff]).cpu().numpy().astype(np.int64).reshape(4, B + 1)       # the level's one read-back: sizes
             hp, hc, hm, hh = h
             prev = (dst[:nP], vals)
@@ -170,7 +167,7 @@ def extract_sparse_dev(field, B, coarse_Q, levels, thresh=0.5, margin=1, bbox=((
             m = emask[:nP]
             vincl = torch.cumsum((m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1), 0, dtype=torch.int32)
             tincl = torch.cumsum(ntri[:nC], 0, dtype=torch.int32)
-            voff_d, toff_d = _excl_at(vincl, poff).contiguous(), _excl_at(tincl, coff)
+            voff_d, toff_d = excl_at(vincl, poff).contiguous(), excl_at(tincl, coff)
             voff, toff, hm = torch.cat([voff_d, toff_d, moff]).cpu().numpy().astype(np.int64).reshape(3, B + 1)   # the output sizes
             verts = torch.empty(max(int(voff[-1]), 1), 3, device=dev, dtype=torch.float32)
             faces = torch.empty(max(int(toff[-1]), 1), 3, device=dev, dtype=torch.int32)

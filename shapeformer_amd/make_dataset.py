@@ -54,15 +54,6 @@ def write_imnet_store(root, dataset, split, Xbd, occ, cates=None):
     return d
 
 
-def _batch(meshes, dev):
-    import torch
-    verts = torch.from_numpy(np.concatenate([v for v, _ in meshes]).astype(np.float32)).to(dev)
-    faces = torch.from_numpy(np.concatenate([f for _, f in meshes]).astype(np.int32)).to(dev)
-    voff = np.concatenate([[0], np.cumsum([len(v) for v, _ in meshes])]).astype(np.int64)
-    toff = np.concatenate([[0], np.cumsum([len(f) for _, f in meshes])]).astype(np.int64)
-    return verts, faces, voff, toff
-
-
 def _morph_occupancy(v, f, voff, toff, names, lattice, grid, morph_grid, selem, morph_samples, seed):
     """(B, grid, grid, grid) uint8: the watertight voxel of the cell that holds each lattice point; status (B,) on the device"""
     from . import morph
@@ -84,6 +75,7 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
     morph_samples surface samples); scale multiplies the normalised vertices on both routes."""
     import torch
     from . import meshio, meshsdf
+    from ._ragged import batch_meshes
     from .metrics import sample_mesh_dev
     if occupancy not in OCCUPANCY:
         raise ValueError(f"occupancy = {occupancy!r} must be one of {OCCUPANCY}")
@@ -103,7 +95,7 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
                 raise ValueError(f"{p}: no faces")
             v = meshsdf.normalize_point_set(v)
             meshes.append((v if scale == 1.0 else v * scale, f))
-        v, f, voff, toff = _batch(meshes, dev)
+        v, f, voff, toff = batch_meshes(meshes, dev)
         if occupancy == "morph":
             o, st = _morph_occupancy(v, f, voff, toff, paths[s:s + batch], lattice, grid, morph_grid, selem, morph_samples, seed + s)
         else:

@@ -13,8 +13,8 @@ Contracts (include/sfmi.h):
             libigl's winding-number sign type for closed, consistently oriented meshes; finite inputs never give NaN
   status    per shape: 0 ok, 1 no faces, 2 a vertex index outside the shape; its queries get S = NaN, I = -1, C = NaN, W = 0
             (its lattice occupancy is 0)
-Ragged batches follow metrics.py: verts (V,3) f32 and faces (T,3) int32 local to each shape, host offsets voff / toff / qoff
-(B+1,), validated before any launch.
+Ragged batches (_ragged.py): verts (V,3) f32 and faces (T,3) int32 local to each shape, host offsets voff / toff /
+qoff (B+1,), validated before any launch.
 """
 from __future__ import annotations
 
@@ -22,26 +22,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .metrics import _host_offsets, _on_device, sample_mesh_dev
+from ._ragged import batch_meshes, f32_dev, host_offsets, mesh_args, on_device
+from .metrics import sample_mesh_dev
 
 STATUS_OK, STATUS_NO_FACES, STATUS_BAD_INDEX = 0, 1, 2
-
-
-def _mesh(verts, faces, voff, toff, what):
-    """-> (verts f32 contiguous, faces int32 contiguous, host voff, host toff) after the host checks."""
-    if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
-        raise L.SfmiError(f"{what}: verts / faces must be torch tensors on the HIP device")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise L.SfmiError(f"{what}: expected verts (V,3) and faces (T,3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
-    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
-        raise L.SfmiError(f"{what}: faces must be an integer tensor")
-    vo = _host_offsets(voff, verts.shape[0], f"{what} voff")
-    to = _host_offsets(toff, faces.shape[0], f"{what} toff")
-    if len(vo) != len(to):
-        raise L.SfmiError(f"{what}: voff and toff describe different batch sizes ({len(vo) - 1} and {len(to) - 1})")
-    if (np.diff(to) >= 2 ** 31).any():
-        raise L.SfmiError(f"{what}: a shape has 2^31 faces or more")
-    return verts.float().contiguous(), faces.to(torch.int32).contiguous(), vo, to
 
 
 def _workspace(B, N, T, dev):
@@ -56,13 +40,13 @@ def signed_distance_dev(queries, verts, faces, qoff=None, voff=None, toff=None, 
     (, W (N,) f32 winding number), status (B,) int32.  A shape with queries but no faces raises SfmiError."""
     if not isinstance(queries, torch.Tensor) or queries.dim() != 2 or queries.shape[1] != 3:
         raise L.SfmiError("signed_distance_dev: queries must be an (N,3) torch tensor")
-    vf, ff, vo, to = _mesh(verts, faces, voff, toff, "signed_distance_dev")
-    qo = _host_offsets(qoff, queries.shape[0], "signed_distance_dev qoff")
+    vf, ff, vo, to = mesh_args(verts, faces, voff, toff, "signed_distance_dev")
+    qo = host_offsets(qoff, queries.shape[0], "signed_distance_dev qoff")
     if len(qo) != len(to):
         raise L.SfmiError(f"signed_distance_dev: {len(qo) - 1} query sets for {len(to) - 1} meshes")
     if ((np.diff(to) == 0) & (np.diff(qo) > 0)).any():
         raise L.SfmiError("signed_distance_dev: a shape has queries but no faces")
-    dev = _on_device("signed_distance_dev", queries, verts, faces)
+    dev = on_device("signed_distance_dev", queries, verts, faces)
     B, N, T = len(to) - 1, queries.shape[0], faces.shape[0]
     qf = queries.float().contiguous()
     S = torch.empty(N, device=dev, dtype=torch.float32)
@@ -80,14 +64,14 @@ def signed_distance_dev(queries, verts, faces, qoff=None, voff=None, toff=None, 
 def mesh_occupancy_dev(verts, faces, voff, toff, grid_dim=64, bbox=((-1.0,) * 3, (1.0,) * 3), return_status=False):
     """Inside test (|W| > 0.5) of every point of the makeGrid(bbox, [grid_dim]*3, mode="on", indexing="ij") lattice, generated in
     the kernel (no G^3 query array).  -> (B, G, G, G) uint8 in data.make_grid's order (first axis slowest) (, status (B,))."""
-    vf, ff, vo, to = _mesh(verts, faces, voff, toff, "mesh_occupancy_dev")
+    vf, ff, vo, to = mesh_args(verts, faces, voff, toff, "mesh_occupancy_dev")
     if (np.diff(to) == 0).any():
         raise L.SfmiError("mesh_occupancy_dev: a shape has no faces")
     G = int(grid_dim)
     if G < 1:
         raise L.SfmiError("mesh_occupancy_dev: grid_dim must be >= 1")
     lo, hi = (np.ascontiguousarray(np.asarray(x, np.float64).reshape(3)) for x in bbox)
-    dev = _on_device("mesh_occupancy_dev", verts, faces)
+    dev = on_device("mesh_occupancy_dev", verts, faces)
     B, T = len(to) - 1, faces.shape[0]
     occ = torch.empty(B, G, G, G, device=dev, dtype=torch.uint8)
     status = torch.empty(B, device=dev, dtype=torch.int32)
@@ -105,13 +89,13 @@ def sdf_sampling_dev(verts, faces, voff, toff, sample_N=64 ** 3, near_std=0.015,
     The normals and uniforms come from a counter hash of (seed, k), not from numpy's global RNG: the draws match the reference
     in distribution, not draw for draw, and sample k of a shape does not depend on the batch around it.
     -> Xbd (B, sample_N, 3), Xtg (B, sample_N, 3), Ytg (B, sample_N) float16 (as the reference returns)."""
-    vf, ff, vo, to = _mesh(verts, faces, voff, toff, "sdf_sampling_dev")
+    vf, ff, vo, to = mesh_args(verts, faces, voff, toff, "sdf_sampling_dev")
     if (np.diff(to) == 0).any():
         raise L.SfmiError("sdf_sampling_dev: a shape has no faces")
     n = int(sample_N)
     if n < 1:
         raise L.SfmiError("sdf_sampling_dev: sample_N must be >= 1")
-    dev = _on_device("sdf_sampling_dev", verts, faces)
+    dev = on_device("sdf_sampling_dev", verts, faces)
     B = len(to) - 1
     Xbd, st = sample_mesh_dev(vf, ff, vo, to, n, seed=seed)
     Xtg = torch.empty_like(Xbd)
@@ -127,17 +111,14 @@ def sdf_sampling_dev(verts, faces, voff, toff, sample_N=64 ** 3, near_std=0.015,
 
 # ---- reference signatures (numpy in, numpy out) ------------------------------------------------------------------------------
 
-def _dev_mesh(vert, face, dev=None):
-    dev = dev or torch.device("cuda")
-    v = torch.from_numpy(np.ascontiguousarray(np.asarray(vert, np.float32).reshape(-1, 3))).to(dev)
-    f = torch.from_numpy(np.ascontiguousarray(np.asarray(face, np.int32).reshape(-1, 3))).to(dev)
-    return v, f
+def _one_mesh(vert, face):
+    return batch_meshes([(np.asarray(vert).reshape(-1, 3), np.asarray(face).reshape(-1, 3))], torch.device("cuda"))
 
 
 def signed_distance(queries, vert, face):
     """geoutil.signed_distance: (S f64 with NaN -> 0 as np.nan_to_num, I int64 closest face, C (N,3) f64 closest point)."""
-    v, f = _dev_mesh(vert, face)
-    q = torch.from_numpy(np.ascontiguousarray(np.asarray(queries, np.float32).reshape(-1, 3))).to(v.device)
+    v, f, _, _ = _one_mesh(vert, face)
+    q = f32_dev(np.asarray(queries, np.float32).reshape(-1, 3), v.device)
     S, I, C, _ = signed_distance_dev(q, v, f)
     return (np.nan_to_num(S.cpu().numpy().astype(np.float64)), I.cpu().numpy().astype(np.int64),
             C.cpu().numpy().astype(np.float64))
@@ -156,9 +137,7 @@ def mesh2sdf(vert, face, gridDim=64, disturb=False):
 
 def SDF_sampling(vert, face, sample_N=64 ** 3, near_std=0.015, far_std=0.2, seed=0):
     """geoutil.SDF_sampling for one mesh -> (Xbd, Xtg, Ytg) float16 numpy; see sdf_sampling_dev (counter-hash draws)."""
-    v, f = _dev_mesh(vert, face)
-    o = np.array([0, v.shape[0]], np.int64), np.array([0, f.shape[0]], np.int64)
-    Xbd, Xtg, Ytg = sdf_sampling_dev(v, f, o[0], o[1], sample_N, near_std, far_std, seed=seed)
+    Xbd, Xtg, Ytg = sdf_sampling_dev(*_one_mesh(vert, face), sample_N, near_std, far_std, seed=seed)
     return Xbd[0].cpu().numpy(), Xtg[0].cpu().numpy(), Ytg[0].cpu().numpy()
 
 

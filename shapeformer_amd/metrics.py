@@ -13,7 +13,7 @@ Definitions (d2(a, S) = min_{s in S} |a - s|^2 in f32, direct form; means and su
   uhd(partial, C)    = per completion c: max_p min_c |p - c| (Euclidean); returned with its mean over the completions
   tmd(S_1..S_k)      = sum_i 1/(k-1) sum_{j != i} CD(S_i, S_j), k >= 2; all k(k-1) directions in one launch
 Ragged sets are (points (N,3), offsets (B+1,)) pairs or lists of (n_i,3) tensors; reductions over them are per-set torch sums on
-the device (fixed order: deterministic).
+the device (fixed order: deterministic).  The offset convention and the argument checks are _ragged.py's.
 """
 from __future__ import annotations
 
@@ -21,40 +21,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._ragged import f32_dev, host_offsets, on_device, points_arg
 
 
-# ---- argument handling (host only: everything here runs before any launch) -------------------------------------------------
-
-def _host_offsets(off, n, what):
-    """-> (B+1,) int64 numpy exclusive offsets, validated against the n rows they cut."""
-    if off is None:
-        return np.array([0, n], np.int64)
-    o = off.detach().cpu().numpy() if isinstance(off, torch.Tensor) else np.asarray(off)
-    if o.ndim != 1 or o.shape[0] < 2 or not (np.issubdtype(o.dtype, np.integer)):
-        raise L.SfmiError(f"{what}: offsets must be a 1-D integer array of length B+1")
-    o = o.astype(np.int64)
-    if o[0] != 0 or o[-1] != n or (np.diff(o) < 0).any():
-        raise L.SfmiError(f"{what}: offsets must start at 0, be nondecreasing and end at {n}")
-    return o
-
-
-def _points(x, what):
-    if not isinstance(x, torch.Tensor):
-        raise L.SfmiError(f"{what}: expected a torch tensor on the HIP device")
-    if x.shape[-1] != 3 or x.dim() not in (2, 3):
-        raise L.SfmiError(f"{what}: expected (N,3) or (B,N,3) points, got {tuple(x.shape)}")
-    return x
-
-
-def _on_device(what, *ts):
-    dev = ts[0].device
-    for t in ts:
-        if t.device.type != "cuda":
-            raise L.SfmiError(f"{what} needs HIP device tensors (no CPU fallback)")
-        if t.device != dev:
-            raise L.SfmiError(f"{what}: all tensors must be on one device")
-    return dev
-
+# ---- nearest neighbours over ragged sets (the argument checks are _ragged.py's: DESIGN.md §5.5a) ----------------------------
 
 def _launch_nn(pf, qf, po, qo, want_index):
     """pf (N,3), qf (M,3) f32 contiguous on one device, po / qo validated host offsets -> d2 (N,), idx (N,) int32 or None."""
@@ -79,7 +49,7 @@ def nn_dist(p, q, p_off=None, q_off=None, return_index=False):
     batches (set b of p against set b of q; offsets must then be None).  -> d2 (N,) f32 (or (B,N)) and, with return_index, the
     int32 index of that nearest point local to its set of q: the lowest index among equal f32 distances.  Bit-identical from
     run to run.  A set of q with no points while its set of p has some raises SfmiError."""
-    p, q = _points(p, "nn_dist p"), _points(q, "nn_dist q")
+    p, q = points_arg(p, "nn_dist p"), points_arg(q, "nn_dist q")
     batched = p.dim() == 3
     if batched:
         if q.dim() != 3 or q.shape[0] != p.shape[0] or p_off is not None or q_off is not None:
@@ -89,12 +59,12 @@ def nn_dist(p, q, p_off=None, q_off=None, return_index=False):
     else:
         if q.dim() != 2:
             raise L.SfmiError("nn_dist: (N,3) p needs an (M,3) q")
-        po, qo = _host_offsets(p_off, p.shape[0], "nn_dist p_off"), _host_offsets(q_off, q.shape[0], "nn_dist q_off")
+        po, qo = host_offsets(p_off, p.shape[0], "nn_dist p_off"), host_offsets(q_off, q.shape[0], "nn_dist q_off")
         if len(po) != len(qo):
             raise L.SfmiError(f"nn_dist: p has {len(po) - 1} sets, q has {len(qo) - 1}")
     if ((np.diff(qo) == 0) & (np.diff(po) > 0)).any():
         raise L.SfmiError("nn_dist: a reference set is empty while its query set is not")
-    _on_device("nn_dist", p, q)
+    on_device("nn_dist", p, q)
     pf, qf = p.reshape(-1, 3).float().contiguous(), q.reshape(-1, 3).float().contiguous()
     d2, idx = _launch_nn(pf, qf, po, qo, return_index)
     if batched:
@@ -106,16 +76,16 @@ def nn_dist(p, q, p_off=None, q_off=None, return_index=False):
 def _pack(sets, what):
     """list of (n_i,3) tensors or a (k,n,3) tensor -> (points (sum n_i,3) f32 contiguous, host offsets)."""
     if isinstance(sets, torch.Tensor):
-        _points(sets, what)
-        _on_device(what, sets)
+        points_arg(sets, what)
+        on_device(what, sets)
         if sets.dim() == 2:
             sets = sets[None]
         k, n = sets.shape[0], sets.shape[1]
         return sets.reshape(-1, 3).float().contiguous(), np.arange(k + 1, dtype=np.int64) * n
-    sets = [_points(s, what) for s in sets]
+    sets = [points_arg(s, what) for s in sets]
     if not sets or any(s.dim() != 2 for s in sets):
         raise L.SfmiError(f"{what}: expected a non-empty list of (n_i,3) tensors")
-    _on_device(what, *sets)
+    on_device(what, *sets)
     off = np.concatenate([[0], np.cumsum([s.shape[0] for s in sets])]).astype(np.int64)
     return torch.cat([s.float() for s in sets]).contiguous(), off
 
@@ -125,7 +95,7 @@ def _directions(pairs, want_index=False):
     for a, b in pairs:
         if b.shape[0] == 0 and a.shape[0] > 0:
             raise L.SfmiError("nn_dist: a reference set is empty while its query set is not")
-    _on_device("metrics", *[t for pq in pairs for t in pq])
+    on_device("metrics", *[t for pq in pairs for t in pq])
     po = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
     qo = np.concatenate([[0], np.cumsum([b.shape[0] for _, b in pairs])]).astype(np.int64)
     pf = torch.cat([a for a, _ in pairs]).float().contiguous()
@@ -152,17 +122,11 @@ def _seg_mean(d, off):
     return _seg(d, off, "sum") / torch.from_numpy(np.diff(off).astype(np.float64)).to(d.device)
 
 
-def _as_dev(x, dev):
-    if isinstance(x, torch.Tensor):
-        return x
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32))).to(dev)
-
-
 # ---- metrics ------------------------------------------------------------------------------------------------------------------
 
 def chamfer(a, b):
     """CD(A, B) = mean_a d2(a, B) + mean_b d2(b, A) (squared distances, f64 means) -> float."""
-    a, b = _points(a, "chamfer a"), _points(b, "chamfer b")
+    a, b = points_arg(a, "chamfer a"), points_arg(b, "chamfer b")
     d, off = _directions([(a.reshape(-1, 3), b.reshape(-1, 3)), (b.reshape(-1, 3), a.reshape(-1, 3))])
     return float(_seg_mean(d, off).sum())
 
@@ -170,7 +134,7 @@ def chamfer(a, b):
 def fscore(pred, gt, tau=0.01, return_pr=False):
     """F-score at threshold tau: precision P = share of pred points within tau (Euclidean: sqrt(d2) <= tau, in f64) of gt,
     recall R = share of gt points within tau of pred, F = 2PR/(P+R), 0 when P+R = 0.  -> F (, P, R)."""
-    pred, gt = _points(pred, "fscore pred").reshape(-1, 3), _points(gt, "fscore gt").reshape(-1, 3)
+    pred, gt = points_arg(pred, "fscore pred").reshape(-1, 3), points_arg(gt, "fscore gt").reshape(-1, 3)
     d, off = _directions([(pred, gt), (gt, pred)])
     within = (d.double().sqrt() <= tau).double()
     pr = (_seg(within, off, "sum") / torch.from_numpy(np.diff(off).astype(np.float64)).to(d.device)).cpu().numpy()
@@ -182,7 +146,7 @@ def fscore(pred, gt, tau=0.01, return_pr=False):
 def uhd(partial, completions):
     """Unidirectional Hausdorff distance from the partial cloud to each completion: max_p min_c |p - c| (Euclidean).
     completions: list of (n_i,3) tensors or a (k,n,3) tensor.  -> (per-completion f64 numpy (k,), their mean)."""
-    partial = _points(partial, "uhd partial").reshape(-1, 3)
+    partial = points_arg(partial, "uhd partial").reshape(-1, 3)
     cf, co = _pack(completions, "uhd completions")
     k = len(co) - 1
     d, off = _directions([(partial, cf[int(co[i]):int(co[i + 1])]) for i in range(k)])
@@ -224,8 +188,8 @@ def evaluate(Xct, completions, Xbd=None, tau=0.01):
         dev = completions.device
     else:
         dev = completions[0].device if len(completions) and isinstance(completions[0], torch.Tensor) else torch.device("cuda")
-        completions = [_as_dev(c, dev) for c in completions]
-    Xct = _as_dev(Xct, dev).reshape(-1, 3)
+        completions = [f32_dev(c, dev) for c in completions]
+    Xct = f32_dev(Xct, dev).reshape(-1, 3)
     cf, co = _pack(completions, "evaluate completions")
     k = len(co) - 1
     S = [cf[int(co[i]):int(co[i + 1])] for i in range(k)]
@@ -234,7 +198,7 @@ def evaluate(Xct, completions, Xbd=None, tau=0.01):
     if k >= 2:
         out["tmd"] = tmd(S)
     if Xbd is not None:
-        X = _as_dev(Xbd, dev).reshape(-1, 3)
+        X = f32_dev(Xbd, dev).reshape(-1, 3)
         d, off = _directions([(s, X) for s in S] + [(X, s) for s in S])
         m = _seg_mean(d, off).cpu().numpy()
         cd = m[:k] + m[k:]
@@ -257,14 +221,14 @@ def sample_mesh_dev(verts, faces, voff, toff, n, seed=0, return_face=False):
         raise L.SfmiError("sample_mesh_dev: verts / faces must be torch tensors on the HIP device")
     if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
         raise L.SfmiError("sample_mesh_dev: expected verts (V,3) and faces (T,3)")
-    vo, to = _host_offsets(voff, verts.shape[0], "sample_mesh_dev voff"), _host_offsets(toff, faces.shape[0], "sample_mesh_dev toff")
+    vo, to = host_offsets(voff, verts.shape[0], "sample_mesh_dev voff"), host_offsets(toff, faces.shape[0], "sample_mesh_dev toff")
     if len(vo) != len(to):
         raise L.SfmiError("sample_mesh_dev: voff and toff describe different batch sizes")
     if (np.diff(to) == 0).any():
         raise L.SfmiError("sample_mesh_dev: a shape has no faces")
     if int(n) < 0:
         raise L.SfmiError("sample_mesh_dev: n must be >= 0")
-    dev = _on_device("sample_mesh_dev", verts, faces)
+    dev = on_device("sample_mesh_dev", verts, faces)
     lib = L.lib()
     B, T, n = len(vo) - 1, faces.shape[0], int(n)
     vf, ff = verts.float().contiguous(), faces.to(torch.int32).contiguous()
@@ -280,25 +244,19 @@ def sample_mesh_dev(verts, faces, voff, toff, n, seed=0, return_face=False):
 
 # ---- reference signatures (numpy in, numpy out) ------------------------------------------------------------------------------
 
-def _np_dev(x, dev=None):
-    if isinstance(x, torch.Tensor):
-        return x
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32))).to(dev or torch.device("cuda"))
-
-
 def points_dist(p1, p2, k=1, return_ind=False):
     """geoutil.points_dist for k = 1: Euclidean distance from each point of p1 to its nearest point of p2 (f64 numpy)
     (, the int64 index of that point)."""
     if k != 1:
         raise L.SfmiError("points_dist: only k = 1 is implemented")
-    d2, idx = nn_dist(_np_dev(p1).reshape(-1, 3), _np_dev(p2).reshape(-1, 3), return_index=True)
+    d2, idx = nn_dist(f32_dev(p1).reshape(-1, 3), f32_dev(p2).reshape(-1, 3), return_index=True)
     dist = np.sqrt(d2.cpu().numpy().astype(np.float64))
     return (dist, idx.cpu().numpy().astype(np.int64)) if return_ind else dist
 
 
 def chamfer_dist(p1, p2):
     """geoutil.chamfer_dist: (squared distances p1 -> p2, squared distances p2 -> p1), f64 numpy, in one launch."""
-    a, b = _np_dev(p1).reshape(-1, 3), _np_dev(p2).reshape(-1, 3)
+    a, b = f32_dev(p1).reshape(-1, 3), f32_dev(p2).reshape(-1, 3)
     d, off = _directions([(a, b), (b, a)])
     d = d.cpu().numpy().astype(np.float64)
     return d[:off[1]], d[off[1]:]
@@ -310,8 +268,8 @@ def chamfer_distance(points1, points2, use_kdtree=True, give_id=False):
     with give_id.  torch in -> torch out on the input's device (f32 means, int64 indices); numpy in -> numpy out.
     use_kdtree is accepted and ignored (the search is exact either way)."""
     as_np = not isinstance(points1, torch.Tensor)
-    a = _np_dev(points1)
-    b = _np_dev(points2, a.device)
+    a = f32_dev(points1)
+    b = f32_dev(points2, a.device)
     B, n, m = a.shape[0], a.shape[1], b.shape[1]
     d, off, idx = _directions([(a[i], b[i]) for i in range(B)] + [(b[i], a[i]) for i in range(B)], want_index=True)
     mean = _seg_mean(d, off)

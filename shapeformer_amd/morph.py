@@ -15,8 +15,9 @@ statement in tests/morph_ref.py.  There is no CPU fallback.
 
 Grids are (B,G,G,G) uint8 device tensors ([i][j][k] = x, y, z; a (G,G,G) grid is taken as a batch of one and comes back as (G,G,G)).
 Everything after the surface samples is exact: bit-identical to the reference's integer steps, from run to run, and between a batch and
-per-shape calls.  Arguments are checked on the host before anything is launched.  status (B,) int32 on the device: 0 ok; 3 the seed voxel
-(0,0,0) was set, so the flood ran over the set voxels as the reference's would (morph_voxelization_dev: 1 a mesh without surface area).
+per-shape calls.  Arguments are checked on the host before anything is launched (ragged batches: _ragged.py).
+status (B,) int32 on the device: 0 ok; 3 the seed voxel (0,0,0) was set, so the flood ran over the set voxels as the reference's would
+(morph_voxelization_dev: 1 a mesh without surface area).
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .metrics import _host_offsets
+from ._ragged import i32_dev, mesh_args, on_device, point_sets
 
 MAX_RADIUS = 16         # sfmi_morph_max_radius()
 STATUS_OK, STATUS_NO_AREA, STATUS_SEED_SET = 0, 1, 3
@@ -51,16 +52,6 @@ def _sizes(B, G, what):
         raise L.SfmiError(f"{what}: B * G^3 = {B} * {G}^3 needs 32-bit voxel indices (must be < 2^31)")
 
 
-def _device(what, *ts):
-    dev = ts[0].device
-    for t in ts:
-        if t.device.type != "cuda":
-            raise L.SfmiError(f"{what} needs HIP device tensors (no CPU fallback)")
-        if t.device != dev:
-            raise L.SfmiError(f"{what}: all tensors must be on one device")
-    return dev
-
-
 def _grid(vox, what):
     """-> (vox as (B,G,G,G), B, G, squeeze) after the shape checks (the device is checked by the caller, last)"""
     if not isinstance(vox, torch.Tensor):
@@ -73,19 +64,9 @@ def _grid(vox, what):
     return v4, v4.shape[0], v4.shape[-1], squeeze
 
 
-def _point_sets(points, off, what):
-    """-> (points as (N,3), host offsets (B+1,))"""
-    if not isinstance(points, torch.Tensor):
-        raise L.SfmiError(f"{what}: points must be a torch tensor on the HIP device (no CPU fallback)")
-    if points.shape[-1:] != (3,) or points.dim() not in (2, 3):
-        raise L.SfmiError(f"{what}: expected (N,3) or (B,N,3) points, got {tuple(points.shape)}")
-    if points.dim() == 3:
-        if off is not None:
-            raise L.SfmiError(f"{what}: offsets go with (N,3) points, not with (B,N,3)")
-        B, n = points.shape[:2]
-        o, points = np.arange(B + 1, dtype=np.int64) * n, points.reshape(B * n, 3)
-    else:
-        o = _host_offsets(off, points.shape[0], f"{what} offsets")
+def _points32(points, off, what):
+    """-> (points as (N,3), host offsets (B+1,)); the kernels index the coordinates in 32 bits"""
+    points, o, _ = point_sets(points, off, what)
     if 3 * points.shape[0] >= 2 ** 31:
         raise L.SfmiError(f"{what}: 2^31 / 3 points or more")
     return points, o
@@ -130,7 +111,7 @@ def _flood(bits, B, G, ws):
 
 def _voxelize(pts, o, B, G, dev):
     pf = pts.float().contiguous()
-    od = torch.from_numpy(o.astype(np.int32)).to(dev)
+    od = i32_dev(o, dev)
     bits = _words(B, G, dev)
     L.check(L.lib().sfmi_voxelize_points_f32(L.ptr(pf), L.ptr(od), B, pf.shape[0], G, L.ptr(bits), L.stream_ptr()), "sfmi_voxelize_points_f32")
     return bits
@@ -152,10 +133,10 @@ def point2voxel_dev(points, off=None, grid_dim=32):
     evaluates the reference's expression); a point with a non-finite coordinate sets none.  points (N,3) with off (B+1,) exclusive offsets
     (None: one set) or (B,N,3).  -> (B,G,G,G) uint8."""
     G = _grid_dim(grid_dim, "point2voxel_dev")
-    pts, o = _point_sets(points, off, "point2voxel_dev")
+    pts, o = _points32(points, off, "point2voxel_dev")
     B = len(o) - 1
     _sizes(B, G, "point2voxel_dev")
-    dev = _device("point2voxel_dev", points)
+    dev = on_device("point2voxel_dev", points)
     return _unpack(_voxelize(pts, o, B, G, dev), B, G)
 
 
@@ -163,11 +144,11 @@ def voxel_lookup_dev(vox, points, off=None):
     """The voxel of the cell that holds each point (point2voxel_dev's index; 0 for a non-finite point): vox (B,G,G,G), points (N,3) with
     off (B+1,) or (B,N,3) -> (N,) / (B,N) uint8."""
     v4, B, G, _ = _grid(vox, "voxel_lookup_dev")
-    pts, o = _point_sets(points, off, "voxel_lookup_dev")
+    pts, o = _points32(points, off, "voxel_lookup_dev")
     if len(o) - 1 != B:
         raise L.SfmiError(f"voxel_lookup_dev: {len(o) - 1} point sets for {B} grids")
-    dev = _device("voxel_lookup_dev", vox, points)
-    pf, od = pts.float().contiguous(), torch.from_numpy(o.astype(np.int32)).to(dev)
+    dev = on_device("voxel_lookup_dev", vox, points)
+    pf, od = pts.float().contiguous(), i32_dev(o, dev)
     bits = _pack(v4, B, G)
     out = torch.empty(pf.shape[0], device=dev, dtype=torch.uint8)
     L.check(L.lib().sfmi_voxelize_lookup_f32(L.ptr(pf), L.ptr(od), B, pf.shape[0], G, L.ptr(bits), L.ptr(out), L.stream_ptr()),
@@ -178,7 +159,7 @@ def voxel_lookup_dev(vox, points, off=None):
 def _morph(vox, r, erode, what):
     r = _radius(r, what)
     v4, B, G, squeeze = _grid(vox, what)
-    dev = _device(what, vox)
+    dev = on_device(what, vox)
     out = _dilate(_pack(v4, B, G), B, G, r, erode, erode, _workspace(B, G, r, dev))
     return _unpack(out, B, G, squeeze)
 
@@ -198,7 +179,7 @@ def flood_dev(vox):
     """skimage flood(vox, (0,0,0)): the voxels that carry voxel (0,0,0)'s value and are joined to it under 26-connectivity.
     -> region (uint8, vox's shape), status (B,) int32 (3: the seed voxel was set)."""
     v4, B, G, squeeze = _grid(vox, "flood_dev")
-    dev = _device("flood_dev", vox)
+    dev = on_device("flood_dev", vox)
     region, status = _flood(_pack(v4, B, G), B, G, _workspace(B, G, 0, dev))
     return _unpack(region, B, G, squeeze), status
 
@@ -208,7 +189,7 @@ def watertight_fill_dev(vox, selem_size=6, return_status=False):
     -> uint8 grid(s) (, status)."""
     r = _radius(selem_size, "watertight_fill_dev", "selem_size")
     v4, B, G, squeeze = _grid(vox, "watertight_fill_dev")
-    _device("watertight_fill_dev", vox)
+    on_device("watertight_fill_dev", vox)
     out, status = _fill(_pack(v4, B, G), B, G, r)
     out = _unpack(out, B, G, squeeze)
     return (out, status) if return_status else out
@@ -226,11 +207,10 @@ def morph_voxelization_dev(verts, faces, voff=None, toff=None, sampleN=1_000_000
     (B+1,), None: one mesh): sampleN area-weighted surface samples per shape (sample_mesh_dev: the reference's distribution, not its
     draws), their voxels, then watertight_fill_dev.  -> (B,G,G,G) uint8 (, coords (G^3,3) f32 cell centres) (, status (B,) int32: 1 a
     mesh without surface area, 3 the seed voxel was set) (, the samples (B,sampleN,3))."""
-    from .meshsdf import _mesh
     from .metrics import sample_mesh_dev
     what = "morph_voxelization_dev"
     G, r = _grid_dim(grid_dim, what), _radius(selem_size, what, "selem_size")
-    vf, ff, vo, to = _mesh(verts, faces, voff, toff, what)
+    vf, ff, vo, to = mesh_args(verts, faces, voff, toff, what)
     if (np.diff(to) == 0).any():
         raise L.SfmiError(f"{what}: a shape has no faces")
     if isinstance(sampleN, bool) or not isinstance(sampleN, (int, np.integer)) or sampleN < 1:
@@ -239,7 +219,7 @@ def morph_voxelization_dev(verts, faces, voff=None, toff=None, sampleN=1_000_000
     _sizes(B, G, what)
     if 3 * B * n >= 2 ** 31:
         raise L.SfmiError(f"{what}: B * sampleN = {B} * {n} points is 2^31 / 3 or more")
-    dev = _device(what, verts, faces)
+    dev = on_device(what, verts, faces)
     pts, st = sample_mesh_dev(vf, ff, vo, to, n, seed=seed)
     out, st3 = _fill(_voxelize(pts, np.arange(B + 1, dtype=np.int64) * n, B, G, dev), B, G, r)
     res = [_unpack(out, B, G)]

@@ -12,7 +12,7 @@ not reproducible).  The contract is in include/sfmi.h, its numpy statement in te
   decimate_dev(verts, faces, voff, toff, decimate_face, bbox, reg)   -> verts, faces, voff, toff, status, G
 
 verts (V,3) f32 and faces (T,3) int32 (indices local per shape) are device tensors, voff / toff (B+1) host offsets, as
-`marching_cubes_dev` returns them.  status (B) int32 on the device: 0 ok, 1 no vertices, 2 a face index outside the shape, 3 a
+`marching_cubes_dev` returns them (the argument checks are _ragged.py's).  status (B) int32 on the device: 0 ok, 1 no vertices, 2 a face index outside the shape, 3 a
 non-finite vertex (such a shape comes back empty).  Results are bit-identical from run to run and a batch equals per-shape calls.
 """
 from __future__ import annotations
@@ -21,13 +21,20 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._ragged import i32_dev, mesh_args, on_device, runs
 
 GRID_MAX = 512
 UNIT_BOX = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
 read_backs = 0          # device -> host size read-backs so far (tools/kbench_simplify.py reports the number per call)
 
 
+# how this module calls mesh_args: 32-bit batch-wide indices, offsets of any array shape
+_MESH = dict(index32=True, flatten_offsets=True)
+
+
 def _nshapes(off):
+    if off is None:
+        return 1
     return (off.numel() if isinstance(off, torch.Tensor) else np.asarray(off).size) - 1
 
 
@@ -42,46 +49,11 @@ def _grid(grid, B):
     return np.ascontiguousarray(g.astype(np.int32))
 
 
-def _offsets(off, n, what):
-    o = off.detach().cpu().numpy() if isinstance(off, torch.Tensor) else np.asarray(off)
-    o = o.astype(np.int64).reshape(-1)
-    if len(o) < 2 or o[0] != 0 or o[-1] != n or (np.diff(o) < 0).any():
-        raise L.SfmiError(f"simplify: {what} must be (B+1) exclusive offsets from 0 to {n}")
-    return o
-
-
 def _box(bbox):
     lo, hi = (np.ascontiguousarray(np.asarray(x, np.float64).reshape(3)) for x in bbox)
     if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
         raise L.SfmiError(f"simplify: bbox needs finite lo < hi, got {lo.tolist()}, {hi.tolist()}")
     return lo, hi
-
-
-def _mesh(verts, faces, voff, toff, what):
-    for t in (verts, faces):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise L.SfmiError(f"{what} needs HIP device tensors (no CPU fallback)")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise L.SfmiError(f"{what}: expected verts (V,3) and faces (T,3), got {tuple(verts.shape)}, {tuple(faces.shape)}")
-    verts = verts.contiguous() if verts.dtype == torch.float32 else verts.float().contiguous()
-    faces = faces.contiguous() if faces.dtype == torch.int32 else faces.to(torch.int32).contiguous()
-    vo, to = _offsets(voff, verts.shape[0], "voff"), _offsets(toff, faces.shape[0], "toff")
-    if len(vo) != len(to):
-        raise L.SfmiError(f"{what}: voff and toff name {len(vo) - 1} and {len(to) - 1} shapes")
-    if verts.shape[0] + faces.shape[0] + len(vo) >= 2 ** 31 or 3 * faces.shape[0] >= 2 ** 31:
-        raise L.SfmiError(f"{what}: the batch is too large for 32-bit indices")
-    return verts, faces, vo, to
-
-
-def _i32(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.int32))).to(dev)
-
-
-def _runs(slots, n_cells):
-    """stable sort of the records by slot -> (order int32, (n_cells+1) int32 run starts)"""
-    s = torch.sort(slots, stable=True)
-    seg = torch.searchsorted(s.values, torch.arange(n_cells + 1, device=slots.device, dtype=torch.int32))
-    return s.indices.to(torch.int32), seg.to(torch.int32)
 
 
 def _cluster(verts, faces, vo, to, g, lo, hi, reg=None):
@@ -93,7 +65,7 @@ def _cluster(verts, faces, vo, to, g, lo, hi, reg=None):
     if nW < 0:
         raise L.SfmiError("sfmi_simplify_words: invalid grid")
     gq = g.astype(np.int64) ** 3
-    woff, gd, voff, toff = _i32(np.concatenate([[0], np.cumsum((gq + 31) // 32)]), dev), _i32(g, dev), _i32(vo, dev), _i32(to, dev)
+    woff, gd, voff, toff = (i32_dev(a, dev) for a in (np.concatenate([[0], np.cumsum((gq + 31) // 32)]), g, vo, to))
     bits, rank = torch.empty(nW, device=dev, dtype=torch.int32), torch.empty(nW, device=dev, dtype=torch.int32)
     vkey, vslot = torch.empty(max(V, 1), device=dev, dtype=torch.int32), torch.empty(max(V, 1), device=dev, dtype=torch.int32)
     flags, status, count = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
@@ -118,8 +90,8 @@ def _cluster(verts, faces, vo, to, g, lo, hi, reg=None):
     out_v = torch.empty(max(nC, 1), 3, device=dev, dtype=torch.float32)
     out_f = torch.empty(max(nS, 1), 3, device=dev, dtype=torch.int32)
     if nC:
-        vorder, vseg = _runs(vslot[:V], nC)
-        corder, cseg = _runs(cslot[:3 * T], nC)
+        vorder, vseg = runs(vslot[:V], nC)
+        corder, cseg = runs(cslot[:3 * T], nC)
         L.check(lib.sfmi_simplify_solve_f32(L.ptr(verts), L.ptr(faces), L.ptr(voff), L.ptr(vkey), L.ptr(g), L.ptr(gd), L.ptr(vorder),
                                             L.ptr(vseg), L.ptr(corder), L.ptr(cseg), B, nC, L.ptr(lo), L.ptr(hi), float(reg), L.ptr(out_v),
                                             st()), "sfmi_simplify_solve_f32")
@@ -134,7 +106,8 @@ def cluster_faces_dev(verts, faces, voff, toff, grid, bbox=UNIT_BOX):
     """The counting pass: per shape the faces that survive clustering on a grid^3 lattice over bbox and the occupied cells, as two
     (B,) host int arrays ((0, 0) for a shape whose status is not 0).  grid: an int or one per shape, in [1, 512]."""
     g = _grid(grid, _nshapes(voff))
-    verts, faces, vo, to = _mesh(verts, faces, voff, toff, "cluster_faces_dev")
+    verts, faces, vo, to = mesh_args(verts, faces, voff, toff, "cluster_faces_dev", **_MESH)
+    on_device("cluster_faces_dev", verts, faces)
     return _cluster(verts, faces, vo, to, g, *_box(bbox))
 
 
@@ -145,7 +118,8 @@ def cluster_simplify_dev(verts, faces, voff, toff, grid, bbox=UNIT_BOX, reg=1e-3
     g = _grid(grid, _nshapes(voff))
     if not (np.isfinite(reg) and reg > 0):
         raise L.SfmiError(f"simplify: reg = {reg} must be > 0")
-    verts, faces, vo, to = _mesh(verts, faces, voff, toff, "cluster_simplify_dev")
+    verts, faces, vo, to = mesh_args(verts, faces, voff, toff, "cluster_simplify_dev", **_MESH)
+    on_device("cluster_simplify_dev", verts, faces)
     return _cluster(verts, faces, vo, to, g, *_box(bbox), reg=float(reg))
 
 
@@ -169,7 +143,8 @@ def decimate_dev(verts, faces, voff, toff, decimate_face=4096, bbox=UNIT_BOX, re
     if not (np.isfinite(reg) and reg > 0):
         raise L.SfmiError(f"simplify: reg = {reg} must be > 0")
     lo, hi = _box(bbox)
-    verts, faces, vo, to = _mesh(verts, faces, voff, toff, "decimate_dev")
+    verts, faces, vo, to = mesh_args(verts, faces, voff, toff, "decimate_dev", **_MESH)
+    on_device("decimate_dev", verts, faces)
     B = len(vo) - 1
     status = torch.from_numpy((np.diff(vo) == 0).astype(np.int32)).to(verts.device)
     G = np.zeros(B, np.int64)
