@@ -777,6 +777,30 @@ int sfmi_morph_flood_u32(const unsigned* in, int B, int G, unsigned* region, int
 int sfmi_morph_pack_u8(const unsigned char* vox, int B, int G, unsigned* bits, void* stream);
 int sfmi_morph_unpack_u8(const unsigned* bits, int B, int G, unsigned char* vox, void* stream);
 
+/* ---- Exact k-nearest neighbours, outlier statistics and normals of raw scans (csrc/knn.hip).
+ *      xgutils/geoutil.py:362-366 (points_dist: scipy cKDTree(p2).query(p1, k) for any k); the real-scan datasets that need a cleaning
+ *      front end: shapeformer/data/imnet_datasets/redwood.py:17-104 (Redwood, Redwood2), realtest.py:17-111 (RealTest_dataset,
+ *      RealTest2_dataset).  Outlier rule: PCL StatisticalOutlierRemoval; normals: local PCA as in PCL / Open3D. ------------------------ */
+/* 0 for arguments sfmi_knn_f32 refuses.  Grows with k when Q is cut into chunks (few query blocks): partial lists per chunk. */
+size_t sfmi_knn_workspace_bytes(int B, long long N, long long M, int k);
+/* Ragged sets as in sfmi_nn_dist_f32: P (N,3), Q (M,3) f32; poff / qoff (B+1) int64 exclusive offsets (M_b < 2^31); 1 <= k <= 64.
+ * d2 (N,k) f32, idx (N,k) int32: row i = the k nearest points of Q_b to query i of P_b, ascending in (d2, index) with
+ * d2 = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) (column 0 is sfmi_nn_dist_f32's result bit for bit), idx local to Q_b, the lower index first among
+ * equal f32 distances; a set offering fewer than k candidates ends its rows in (+inf, -1).
+ * exclude_self != 0 (valid only when P and Q are the same sets, N == M): the candidate with the query's own local index is skipped - by
+ * index, not by distance, so duplicates of a point remain its neighbours.  Deterministic, no atomics, independent of the chunking. */
+int sfmi_knn_f32(const float* P, const float* Q, const long long* poff, const long long* qoff, int B, long long N, long long M, int k,
+                 int exclude_self, float* d2, int* idx, void* workspace, void* stream);
+/* out (N) f64: mean over the k columns of sqrt(d2) in f64, in column order (the statistic of statistical outlier removal) */
+int sfmi_knn_mean_dist_f64(const float* d2, long long N, int k, double* out, void* stream);
+/* P (N,3) f32 with off (B+1) int64; idx (N,k) int32 neighbour table local to each set (entries < 0 or outside the set are skipped).
+ * Centroid and 3x3 covariance of the neighbours in f64 in column order, eigenvector of the smallest eigenvalue in f64 (fixed-sweep
+ * cyclic Jacobi).  normal (N,3) f32 unit; variation (N) f32 = l0 / (l0 + l1 + l2).  viewpoint (B,3) f64 [device]: the sign with
+ * n . (v - p) >= 0; NULL: the component of largest magnitude is positive (the first such on a tie).  Fewer than 3 valid neighbours:
+ * normal (0,0,0), variation NaN. */
+int sfmi_knn_normals_f32(const float* P, const long long* off, const int* idx, int B, long long N, int k, const double* viewpoint,
+                         float* normal, float* variation, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

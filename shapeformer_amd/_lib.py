@@ -223,6 +223,11 @@ PROTOTYPES = {
     "sfmi_morph_flood_u32": (i32, [c_ptr, i32, i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "sfmi_morph_pack_u8": (i32, [c_ptr, i32, i32, c_ptr, c_ptr]),
     "sfmi_morph_unpack_u8": (i32, [c_ptr, i32, i32, c_ptr, c_ptr]),
+    # exact k-nearest neighbours, outlier statistics, normals (csrc/knn.hip)
+    "sfmi_knn_workspace_bytes": (sz, [i32, i64, i64, i32]),
+    "sfmi_knn_f32": (i32, [c_ptr] * 4 + [i32, i64, i64, i32, i32] + [c_ptr] * 4),
+    "sfmi_knn_mean_dist_f64": (i32, [c_ptr, i64, i32, c_ptr, c_ptr]),
+    "sfmi_knn_normals_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 4),
 }
 
 

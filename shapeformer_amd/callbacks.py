@@ -200,8 +200,14 @@ class VisShapeFormer(VisCallback):
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
                  thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
                  eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, refine_steps=0,
-                 vertex_normals=False, keep_components=None, **kw):
+                 vertex_normals=False, keep_components=None, clean_context=None, **kw):
         super().__init__(**kw)
+        # clean_context: a dict of scan.clean_cloud_dev keyword arguments (k, std_ratio, seed): compute_batch removes the
+        # statistical outliers of Xct on the device before encode_cloud, resampled back to Xct's point count, and records the kept
+        # count as `context_kept` in the computed dict.  For raw scans (data.ScanDataset).  None: off, the path as it always was
+        if clean_context is not None and (not isinstance(clean_context, dict) or "out_N" in clean_context):
+            raise ValueError("clean_context must be a dict of clean_cloud_dev keyword arguments without out_N (the point count is kept)")
+        self.clean_context = clean_context
         # keep_components: as VisSparseRecon3D's, on the dense and the sparse_decode route alike: extract -> refine -> components ->
         # decimate -> normals; eval_pc, recon_<i>, eval_metrics, the fewer-than-10-vertices rule, the decimation and the PLY see the
         # filtered meshes, and the returned dict (with eval_metrics also eval/<name>_metrics.json) has `components` per mesh key.  None: off
@@ -236,6 +242,10 @@ class VisShapeFormer(VisCallback):
         pipe, g = m.pipe, m.transformer
         Xct = batch["Xct"].to(g.dev, torch.float32)
         assert Xct.shape[0] == 1                 # shapeformer.py:227
+        context_kept = None
+        if self.clean_context is not None:
+            from .scan import clean_cloud_dev
+            Xct, context_kept = clean_cloud_dev(Xct, **self.clean_context)
         enc = pipe.encode_cloud(Xct)             # representer.get_indices(stage="test"): c tokens + empty index
         Lc = int(enc["Lc"][0])
         c_ind = enc["c_tokens"][:, :Lc].long()   # origin_c_indices (1, L_c, 2), end-token pair last
@@ -257,6 +267,8 @@ class VisShapeFormer(VisCallback):
                         logits_history=res.get("logits_history"), c_ind=c_ind,
                         z_ind=z_ind if z_ind is not None else c_ind[:, :0], empty_index=enc["empty_index"].long()[0])
         computed = _np(computed)
+        if context_kept is not None:
+            computed["context_kept"] = int(context_kept[0])
         if self.sort_prob:
             # compute_log_probs(samples, logits_history): the sampler already accumulated exactly these terms on the device
             computed["log_prob"] = res["log_prob"].numpy().astype(np.float64) if isinstance(res["log_prob"], torch.Tensor) else np.asarray(res["log_prob"], np.float64)

@@ -9,6 +9,8 @@ same points):
   ListDataset                             shapeformer/data/paper_datasets/list_dataset.py:14-41
   Imnet2LowResDataset                     shapeformer/data/imnet_datasets/imnet_datasets.py:144-224 (HDF5: `Xbd` clouds,
                                           bit-packed `Ytg` occupancy, `cate_<k>` index lists)
+  ScanDataset (Redwood, Redwood2, RealTest_dataset, RealTest2_dataset)   shapeformer/data/imnet_datasets/redwood.py:17-104,
+                                          realtest.py:17-111 (raw .pts scans, normalised four ways)
   DataModule                              shapeformer/datamodule.py:13-63 (plain loaders, no Lightning)
   collate_to_device                       GPU-side batching: stack on the host once, one H2D copy per key
 
@@ -304,6 +306,57 @@ class Imnet2LowResDataset:
         return dict(Xct=Xct.astype(np.float32), Xbd=Xbd.astype(np.float32), Xtg=Xtg.astype(np.float32), Ytg=Ytg.astype(np.float32))
 
 
+
+class ScanDataset:
+    """Raw scans as the reference's real-scan datasets serve them (shapeformer/data/imnet_datasets/redwood.py:17-104 Redwood /
+    Redwood2, realtest.py:17-111 RealTest_dataset / RealTest2_dataset): every file `pattern` under `scan_path` is read
+    (meshio.read_points: the first three columns, in f32), normalised (scan.normalize_scan: `normalize` and `scale` are the one
+    thing the four classes differ in) and served as {"Xbd": points, "Xct": partial_selector(points)}; the default selector is
+    VirtualScanSelector(radius=camR, context_N=context_N).  The reference hard-codes its directory; here it is `scan_path`.
+    Files are taken in sorted order (the reference lists them with glob, whose order is unspecified).  Further reference kwargs
+    (split, samples_per_cate, evalseed, the HDF5 arguments of its base class) are accepted and unused, as the reference leaves them.
+    Host-only: it may run in loader workers and never touches the device; cleaning a scan on the device is
+    VisShapeFormer(clean_context=...) / scan.clean_cloud_dev."""
+    NORMALIZE, SCALE = "mean_max", 0.7
+
+    def __init__(self, scan_path, pattern="*.pts", normalize=None, scale=None, partial_opt=None, context_N=8192, camR=10, **_):
+        import glob
+        from .scan import NORMALIZE_MODES
+        self.normalize = self.NORMALIZE if normalize is None else normalize
+        self.scale = self.SCALE if scale is None else scale
+        if self.normalize not in NORMALIZE_MODES:
+            raise ValueError(f"ScanDataset: normalize must be one of {NORMALIZE_MODES}, got {self.normalize!r}")
+        self.scan_path = scan_path
+        self.files = sorted(glob.glob(os.path.join(scan_path, pattern)))
+        self.partial_selector = instantiate(partial_opt or {"class": "shapeformer.data.partial.VirtualScanSelector",
+                                                            "kwargs": dict(radius=camR, context_N=context_N)})
+
+    def __len__(self):
+        return len(self.files)
+
+    def __getitem__(self, ind):
+        from .meshio import read_points
+        from .scan import normalize_scan
+        points = normalize_scan(read_points(self.files[ind]), self.normalize, self.scale)
+        return {"Xbd": points, "Xct": self.partial_selector(points)}
+
+
+class Redwood(ScanDataset):
+    NORMALIZE, SCALE = "mean_max", 0.7
+
+
+class Redwood2(ScanDataset):
+    NORMALIZE, SCALE = "bbox", 0.9
+
+
+class RealTestDataset(ScanDataset):
+    NORMALIZE, SCALE = "mean_max", 0.8
+
+
+class RealTest2Dataset(ScanDataset):
+    NORMALIZE, SCALE = "bbox", 0.85
+
+
 # ----------------------------------------------------------------------------- plugin glue + loaders
 DATA_REGISTRY = {
     "shapeformer.data.partial.AllSelector": AllSelector,
@@ -313,6 +366,10 @@ DATA_REGISTRY = {
     "shapeformer.data.paper_datasets.transform_dataset.TransformDataset": TransformDataset,
     "shapeformer.data.paper_datasets.list_dataset.ListDataset": ListDataset,
     "shapeformer.data.imnet_datasets.imnet_datasets.Imnet2LowResDataset": Imnet2LowResDataset,
+    "shapeformer.data.imnet_datasets.redwood.Redwood": Redwood,
+    "shapeformer.data.imnet_datasets.redwood.Redwood2": Redwood2,
+    "shapeformer.data.imnet_datasets.realtest.RealTest_dataset": RealTestDataset,
+    "shapeformer.data.imnet_datasets.realtest.RealTest2_dataset": RealTest2Dataset,
 }
 
 

@@ -245,10 +245,14 @@ def sample_mesh_dev(verts, faces, voff, toff, n, seed=0, return_face=False):
 # ---- reference signatures (numpy in, numpy out) ------------------------------------------------------------------------------
 
 def points_dist(p1, p2, k=1, return_ind=False):
-    """geoutil.points_dist for k = 1: Euclidean distance from each point of p1 to its nearest point of p2 (f64 numpy)
-    (, the int64 index of that point)."""
+    """geoutil.points_dist: Euclidean distance from each point of p1 to its nearest point of p2 (f64 numpy) (, the int64 index of
+    that point).  2 <= k <= 64: (N,k) distances (, indices) to the k nearest, ascending, as cKDTree.query(p1, k) returns them
+    (scan.knn_dev; fewer than k points in p2: inf, and -1 where scipy writes len(p2))."""
     if k != 1:
-        raise L.SfmiError("points_dist: only k = 1 is implemented")
+        from .scan import knn_dev
+        d2, idx = knn_dev(f32_dev(p1).reshape(-1, 3), f32_dev(p2).reshape(-1, 3), k)
+        dist = np.sqrt(d2.cpu().numpy().astype(np.float64))
+        return (dist, idx.cpu().numpy().astype(np.int64)) if return_ind else dist
     d2, idx = nn_dist(f32_dev(p1).reshape(-1, 3), f32_dev(p2).reshape(-1, 3), return_index=True)
     dist = np.sqrt(d2.cpu().numpy().astype(np.float64))
     return (dist, idx.cpu().numpy().astype(np.int64)) if return_ind else dist
