@@ -801,6 +801,36 @@ int sfmi_knn_mean_dist_f64(const float* d2, long long N, int k, double* out, voi
 int sfmi_knn_normals_f32(const float* P, const long long* off, const int* idx, int B, long long N, int k, const double* viewpoint,
                          float* normal, float* variation, void* stream);
 
+/* ---- Downsampling of raw scans: farthest point sampling and a voxel grid (csrc/downsample.hip).  What PCL / Open3D
+ *      pipelines run in front of the outlier rule above (VoxelGrid, voxel_down_sample), and the sampler that brings a cloud to the
+ *      2 048 / 16 384 points of the completion benchmarks. ---------------------------------------------------------------------------- */
+/* the largest set that is sampled from registers (16 384); larger sets are swept from global memory each pick */
+int sfmi_fps_resident_max(void);
+/* 0 for arguments the sampler refuses.  Holds the running distances of sets beyond the resident maximum. */
+size_t sfmi_fps_workspace_bytes(int B, long long N, int n);
+/* P (N,3) f32 with off (B+1) int64 exclusive offsets (every set below 2^31 points); valid (N) uint8 or NULL; start (B) int32 local
+ * indices or NULL (ignored when valid is given).  idx (B,n) int32 local to the set, d2 (B,n) f32, count (B), status (B) int32.
+ * Candidates of set b: its points, or those with valid != 0; count[b] = min(n, candidates).  Every candidate starts at dist = +inf; the
+ * first pick is start[b], else the arg max (the candidate of lowest index); after each pick s every remaining candidate takes
+ * dist = min(dist, fmaf(dz,dz,fmaf(dy,dy,dx*dx))) with f32 differences to s (sfmi_nn_dist_f32's bits) and s leaves the candidates; the
+ * next pick is arg max dist, the LOWER index among equal f32 values; d2[b,t] is the winner's dist when picked (d2[b,0] = +inf, the row
+ * non-increasing, sqrt(d2[b,t]) the covering radius of the first t picks).  Columns t >= count[b] hold (-1, 0.0f).
+ * status: 0 ok; 1 no candidate; 2 a non-finite coordinate among the candidates; 3 a set of 2^31 points or more (1 - 3: all tail).
+ * One workgroup per set, no atomics: bit-identical from run to run, a set's row depends on that set alone, and a run with smaller n
+ * is a prefix of a run with larger n.  With N beyond the resident maximum P and the workspace must be 16-byte aligned. */
+int sfmi_fps_f32(const float* P, const long long* off, const unsigned char* valid, const int* start, int B, long long N, int n, int* idx,
+                 float* d2, int* count, int* status, void* workspace, void* stream);
+/* Voxel keys: per set lo = the componentwise f32 minimum of its points [lo: (B,3) uint32 scratch]; cell = floor((double(x) -
+ * double(lo)) / voxel) per axis in IEEE f64; keys (N) int64 = ((set * 65536 + cz) * 65536 + cy) * 65536 + cx.  B < 32768, voxel
+ * finite and > 0.  status (1) int32 bits: 1 a non-finite coordinate, 2 an axis with 65 536 cells or more (such keys mean nothing). */
+int sfmi_voxel_keys_f32(const float* P, const long long* off, int B, long long N, double voxel, unsigned* lo, long long* keys,
+                        int* status, void* stream);
+/* order (N) int64: the points sorted by key, stable; starts (M+1) int64: where each run of equal keys begins, starts[M] = N.
+ * Per run m: count[m] points, first[m] = the lowest local index among them, out[m] = that point bit for bit (centroid == 0) or the
+ * mean of the run's points, summed in f64 in a fixed order that depends on the run alone, rounded to f32 (centroid != 0). */
+int sfmi_voxel_reduce_f32(const float* P, const long long* off, const long long* order, const long long* starts, int B, long long N,
+                          long long M, int centroid, float* out, int* first, int* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

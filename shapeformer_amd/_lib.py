@@ -228,6 +228,12 @@ PROTOTYPES = {
     "sfmi_knn_f32": (i32, [c_ptr] * 4 + [i32, i64, i64, i32, i32] + [c_ptr] * 4),
     "sfmi_knn_mean_dist_f64": (i32, [c_ptr, i64, i32, c_ptr, c_ptr]),
     "sfmi_knn_normals_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 4),
+    # farthest point sampling and voxel-grid downsampling (csrc/downsample.hip)
+    "sfmi_fps_resident_max": (i32, []),
+    "sfmi_fps_workspace_bytes": (sz, [i32, i64, i32]),
+    "sfmi_fps_f32": (i32, [c_ptr] * 4 + [i32, i64, i32] + [c_ptr] * 6),
+    "sfmi_voxel_keys_f32": (i32, [c_ptr, c_ptr, i32, i64, C.c_double] + [c_ptr] * 4),
+    "sfmi_voxel_reduce_f32": (i32, [c_ptr] * 4 + [i32, i64, i64, i32] + [c_ptr] * 4),
 }
 
 

@@ -126,3 +126,21 @@ def runs(keys, n):
     s = torch.sort(keys, stable=True)
     seg = torch.searchsorted(s.values, torch.arange(n + 1, device=keys.device, dtype=torch.int32))
     return s.indices.to(torch.int32), seg.to(torch.int32)
+
+
+def sorted_runs(keys):
+    """`runs` for sparse keys (any int64 values): stable sort of the n >= 1 records by key -> (order int64, is_start bool: sorted record
+    i begins a run of equal keys, rank int64: the runs begun up to and including i).  Nothing is read back."""
+    s = torch.sort(keys, stable=True)
+    is_start = torch.ones_like(s.values, dtype=torch.bool)
+    is_start[1:] = s.values[1:] != s.values[:-1]
+    return s.indices, is_start, torch.cumsum(is_start, 0)
+
+
+def run_starts(is_start, rank, m):
+    """-> (m+1,) int64: where each of the m runs of `sorted_runs` begins, the record count at [m] (m read back by the caller)"""
+    n = is_start.shape[0]
+    starts = torch.empty(m + 2, device=rank.device, dtype=torch.int64)
+    starts.scatter_(0, torch.where(is_start, rank - 1, m + 1), torch.arange(n, device=rank.device))   # the rest land in the spare slot
+    starts[m] = n
+    return starts[:m + 1]

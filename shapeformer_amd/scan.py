@@ -11,7 +11,9 @@ cKDTree.query); here it is exact brute force on the device, the sibling of metri
   radius_outlier_mask_dev(points, off, radius, min_neighbors) -> keep, count
   estimate_normals_dev(points, off, k, viewpoint)         -> normal (N,3) f32, variation (N,) f32               (local PCA)
   normalize_scan(points, mode, scale)                     -> the four normalisations of the reference's real-scan datasets (host or device)
-  clean_cloud_dev(X, k, std_ratio, out_N, seed)           -> (B, out_N, 3) cleaned clouds of a fixed size, count (B,)
+  farthest_point_sample_dev(points, off, n, start, valid) -> idx (B,n) int32, d2 (B,n) f32, count (B,), status (B,)   (csrc/downsample.hip,
+  voxel_downsample_dev(points, off, voxel, pick)          -> out (M,3) f32, out_off (B+1,) host, first (M,), count (M,)       DESIGN.md §5.15)
+  clean_cloud_dev(X, k, std_ratio, out_N, seed, voxel, resample) -> (B, out_N, 3) cleaned clouds of a fixed size, count (B,)
 
 Ragged batches and their argument checks are _ragged.py's: every refusal is an SfmiError raised on the host before
 the library is loaded, and where the tensors live is checked last.  There is no CPU fallback.
@@ -26,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import excl_at, host_offsets, on_device, point_sets, points_arg
+from ._ragged import excl_at, host_offsets, on_device, point_sets, points_arg, run_starts, sorted_runs
 
 MAX_K = 64
 
@@ -220,13 +222,145 @@ def normalize_scan(points, mode="mean_max", scale=0.7):
     return p * np.float32(scale)
 
 
+# ---- downsampling: farthest point sampling and a voxel grid (csrc/downsample.hip) ----------------------------------
+
+FPS_RESIDENT_MAX = 16384          # sfmi_fps_resident_max(): the largest set sampled from registers; larger sets stream from memory
+VOXEL_MAX_CELLS, VOXEL_MAX_SETS = 65536, 32768
+VOXEL_PICKS = ("centroid", "first")
+RESAMPLE_MODES = ("random", "fps")
+
+
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def farthest_point_sample_dev(points, off=None, n=None, start=None, valid=None):
+    """Farthest point sampling, set by set, exact.
+
+    points (N,3) f32 HIP tensor with (B+1,) exclusive offsets (None: one set), or a (B,M,3) batch.  -> idx (B,n) int32 local to the set,
+    d2 (B,n) f32, count (B,) int32, status (B,) int32, all on the device; the call does not synchronise.
+    Candidates of set b are its points, or those with valid != 0 (valid: (N,) uint8 HIP tensor, (B,M) for a batch);
+    count[b] = min(n, candidates).  The first pick is start (an int or (B,) ints, local indices; not together with valid), by default
+    the candidate of lowest index.  Every candidate starts at dist = +inf; after each pick s the remaining candidates take
+    dist = min(dist, |p - s|^2) in the f32 direct form of nn_dist (the same bits) and s leaves the candidates, so indices in a row are
+    distinct; the next pick is arg max dist, the lower index among equal f32 values.  d2[b,t] is the winner's dist when it was picked:
+    d2[b,0] = +inf, the row is non-increasing, sqrt(d2[b,t]) is the covering radius of the first t picks.  Columns t >= count[b] hold
+    (-1, 0.0).  status: 0 ok, 1 no candidate, 2 a non-finite coordinate among the candidates (1, 2: the row is all tail).
+    Bit-identical from run to run; a set's row depends on that set only; a run with smaller n is a prefix of a run with larger n."""
+    what = "farthest_point_sample_dev"
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 0 or int(n) >= 2 ** 31:
+        raise L.SfmiError(f"{what}: n must be an integer in [0, 2^31), got {n!r}")
+    n = int(n)
+    x, o, shape = point_sets(points, off, what)
+    B, sizes = len(o) - 1, np.diff(o)
+    if (sizes >= 2 ** 31).any():
+        raise L.SfmiError(f"{what}: a set has 2^31 points or more")
+    if start is not None and valid is not None:
+        raise L.SfmiError(f"{what}: start together with valid is refused (the first pick of a masked set is its lowest candidate)")
+    st = None
+    if start is not None:
+        s = start.detach().cpu().numpy() if isinstance(start, torch.Tensor) else np.asarray(start)
+        if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
+            raise L.SfmiError(f"{what}: start must be an integer or a ({B},) integer array")
+        if s.ndim == 0:
+            s = np.full(B, s)
+        if s.shape != (B,):
+            raise L.SfmiError(f"{what}: start must be an integer or a ({B},) integer array, got shape {tuple(s.shape)}")
+        if ((s < 0) | (s >= sizes)).any():
+            raise L.SfmiError(f"{what}: start out of range for its set")
+        st = s.astype(np.int32)
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8:
+            raise L.SfmiError(f"{what}: valid must be a uint8 torch tensor on the HIP device")
+        if tuple(valid.shape) != (shape if shape else (x.shape[0],)):
+            raise L.SfmiError(f"{what}: valid must have one entry per point, got shape {tuple(valid.shape)}")
+    dev = on_device(what, x, *([valid] if valid is not None else []))
+    N = x.shape[0]
+    idx = torch.empty(B, n, device=dev, dtype=torch.int32)
+    d2 = torch.empty(B, n, device=dev, dtype=torch.float32)
+    count = torch.empty(B, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return idx, d2, count, status
+    lib = L.lib()
+    xf = _aligned16(x.float().contiguous())
+    vd = valid.reshape(-1).contiguous() if valid is not None else None
+    od = torch.from_numpy(o).to(dev)
+    sd = torch.from_numpy(st).to(dev) if st is not None else None
+    ws = torch.empty(max(int(lib.sfmi_fps_workspace_bytes(B, N, n)), 16), device=dev, dtype=torch.uint8)
+    L.check(lib.sfmi_fps_f32(L.ptr(xf), L.ptr(od), L.ptr(vd), L.ptr(sd), B, N, n, L.ptr(idx), L.ptr(d2), L.ptr(count), L.ptr(status),
+                             L.ptr(ws), L.stream_ptr()), "sfmi_fps_f32")
+    return idx, d2, count, status
+
+
+def _check_voxel(voxel, what):
+    if isinstance(voxel, bool) or not isinstance(voxel, (int, float, np.integer, np.floating)) or not 0 < float(voxel) < float("inf"):
+        raise L.SfmiError(f"{what}: voxel must be a finite number > 0, got {voxel!r}")
+    return float(voxel)
+
+
+def voxel_downsample_dev(points, off=None, voxel=None, pick="centroid"):
+    """Voxel-grid downsampling, set by set: one output point per occupied cell of edge `voxel`.
+
+    points (N,3) f32 HIP tensor with (B+1,) offsets (None: one set), or a (B,M,3) batch.  -> out (M,3) f32, out_off (B+1,) host int64
+    (the result is ragged: the voxel counts are read back, one synchronisation), first (M,) int32, count (M,) int32.
+    Per set lo is the componentwise f32 minimum of its points and the cell of a point is floor((double(x) - double(lo)) / voxel) per
+    axis (a point on a cell face belongs to the upper cell).  The voxels of a set ascend in (cz, cy, cx).  count: the points in the
+    voxel; first: the lowest local index among them.  pick="first": that input point, bit for bit.  pick="centroid" (PCL VoxelGrid,
+    Open3D voxel_down_sample): their mean, summed in f64 in a fixed order and rounded to f32: bit-identical from run to run and
+    independent of the batch around the set.  An empty set yields no voxels.
+    Raises SfmiError after the read-back for a non-finite coordinate or a grid of 65 536 cells or more along an axis; a batch holds
+    fewer than 32 768 sets."""
+    what = "voxel_downsample_dev"
+    voxel = _check_voxel(voxel, what)
+    if pick not in VOXEL_PICKS:
+        raise L.SfmiError(f"{what}: pick must be one of {VOXEL_PICKS}, got {pick!r}")
+    x, o, _ = point_sets(points, off, what)
+    B, N = len(o) - 1, x.shape[0]
+    if B >= VOXEL_MAX_SETS:
+        raise L.SfmiError(f"{what}: a batch holds fewer than {VOXEL_MAX_SETS} sets, got {B}")
+    if N >= 2 ** 31:
+        raise L.SfmiError(f"{what}: the batch has 2^31 points or more")
+    dev = on_device(what, x)
+    if N == 0:
+        return (torch.empty(0, 3, device=dev, dtype=torch.float32), np.zeros(B + 1, np.int64),
+                torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.int32))
+    lib = L.lib()
+    xf = x.float().contiguous()
+    od = torch.from_numpy(o).to(dev)
+    lo = torch.empty(B, 3, device=dev, dtype=torch.int32)
+    keys = torch.empty(N, device=dev, dtype=torch.int64)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    L.check(lib.sfmi_voxel_keys_f32(L.ptr(xf), L.ptr(od), B, N, voxel, L.ptr(lo), L.ptr(keys), L.ptr(status), L.stream_ptr()),
+            "sfmi_voxel_keys_f32")
+    order, is_start, rank = sorted_runs(keys)
+    head = torch.cat([excl_at(rank, od), status.to(rank.dtype)]).cpu().numpy()          # the one read-back: voxels per set, status
+    if head[-1]:
+        raise L.SfmiError(f"{what}: " + ("a coordinate is not finite" if head[-1] & 1 else
+                                         f"the grid has {VOXEL_MAX_CELLS} cells or more along an axis (voxel = {voxel!r})"))
+    out_off = head[:-1].astype(np.int64)
+    M = int(out_off[-1])
+    starts = run_starts(is_start, rank, M)
+    out = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    first = torch.empty(M, device=dev, dtype=torch.int32)
+    count = torch.empty(M, device=dev, dtype=torch.int32)
+    L.check(lib.sfmi_voxel_reduce_f32(L.ptr(xf), L.ptr(od), L.ptr(order), L.ptr(starts), B, N, M, int(pick == "centroid"), L.ptr(out),
+                                      L.ptr(first), L.ptr(count), L.stream_ptr()), "sfmi_voxel_reduce_f32")
+    return out, out_off, first, count
+
+
 # ---- the cleaning front end --------------------------------------------------------------------------------------------------------
 
-def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0):
+def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0, voxel=None, resample="random"):
     """Statistical outlier removal of a batch of clouds, back at a fixed size: X (B,N,3) HIP tensor -> (B, out_N or N, 3) f32, each row
     a uniformly drawn kept point of its cloud (hpr.resample_visible_dev with the mask as `visible`: a counter hash of (seed, cloud
     index, row), no global RNG), and count (B,) int32 kept points per cloud.  That function's fallback applies: a cloud with two or
-    fewer kept points is resampled from all its points."""
+    fewer kept points is resampled from all its points.
+    voxel: each cloud is first reduced to one centroid per occupied voxel of that edge (voxel_downsample_dev), the outlier rule runs on
+    the ragged result (a density test wants one density) and count is the number of kept voxels.
+    resample="fps": the rows are the kept points in farthest-point order (farthest_point_sample_dev with the mask as `valid`); a cloud
+    that keeps fewer than out_N points continues cyclically through that order (row r = order[r mod count]); two or fewer kept points:
+    all the cloud's points, as above.  The defaults take exactly the path this function always took."""
     from .hpr import resample_visible_dev
     x = points_arg(X, "clean_cloud_dev")
     if x.dim() != 3:
@@ -234,7 +368,27 @@ def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0):
     n_out = x.shape[1] if out_N is None else int(out_N)
     if n_out < 0:
         raise L.SfmiError("clean_cloud_dev: out_N must be >= 0")
-    keep, count, _ = statistical_outlier_mask_dev(x, None, k, std_ratio)
+    if resample not in RESAMPLE_MODES:
+        raise L.SfmiError(f"clean_cloud_dev: resample must be one of {RESAMPLE_MODES}, got {resample!r}")
+    if voxel is not None:
+        voxel = _check_voxel(voxel, "clean_cloud_dev")
     B, n = x.shape[:2]
-    xf, o = x.reshape(B * n, 3).float().contiguous(), np.arange(B + 1, dtype=np.int64) * n
-    return resample_visible_dev(xf, o, keep.reshape(-1), count, n_out, 0., seed), count
+    if voxel is None:
+        keep, count, _ = statistical_outlier_mask_dev(x, None, k, std_ratio)
+        xf, o = x.reshape(B * n, 3).float().contiguous(), np.arange(B + 1, dtype=np.int64) * n
+    else:
+        _check_k(k, "clean_cloud_dev")
+        xf, o, _, _ = voxel_downsample_dev(x, None, voxel, "centroid")
+        keep, count, _ = statistical_outlier_mask_dev(xf, o, k, std_ratio)
+    keep = keep.reshape(-1)
+    if resample == "random":
+        return resample_visible_dev(xf, o, keep, count, n_out, 0., seed), count
+    dev = xf.device
+    if B == 0 or xf.shape[0] == 0:
+        return torch.zeros(B, n_out, 3, device=dev, dtype=torch.float32), count
+    od = torch.from_numpy(o).to(dev)
+    few = torch.repeat_interleave(count <= 2, od[1:] - od[:-1], output_size=xf.shape[0])        # the fallback: all the cloud's points
+    idx, _, got, _ = farthest_point_sample_dev(xf, o, n_out, valid=keep | few.to(torch.uint8))
+    r = torch.arange(n_out, device=dev)[None, :] % got.clamp(min=1).long()[:, None]
+    rows = (idx.long().gather(1, r) + od[:-1, None]).clamp(min=0, max=xf.shape[0] - 1)          # an empty cloud has no order: any row
+    return xf[rows.reshape(-1)].reshape(B, n_out, 3), count
