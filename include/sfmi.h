@@ -831,6 +831,50 @@ int sfmi_voxel_keys_f32(const float* P, const long long* off, int B, long long N
 int sfmi_voxel_reduce_f32(const float* P, const long long* off, const long long* order, const long long* starts, int B, long long N,
                           long long M, int centroid, float* out, int* first, int* count, void* stream);
 
+/* ---- Poisson surface reconstruction of oriented point clouds on a uniform lattice (csrc/poisson.hip).
+ *      xgutils/geoutil.py:297-342 (Open3D_Toolbox.poisson_recon, Meshlab_Toolbox.poisson_recon): the interface of that call on a uniform
+ *      lattice, not Open3D's octree output.  Lattices are (B,R,R,R) f32, axes 0,1,2 = x,y,z, 5 <= R <= 513, B R^3 < 2^31.  box: 6 doubles
+ *      ON THE HOST, lo xyz then hi xyz; h = (hi - lo) / (R - 1) per axis; the lattice coordinate of a point is t = (double(x) - lo) / h
+ *      clamped to [0, R - 1]; a point is inside when lo <= x <= hi on every axis.  hat(d) = max(0, 1 - |d|). --------------------------- */
+/* geoutil.py:322-329 (the cloud and its normals enter the reconstruction).  P, Nrm (N,3) f32 with off (B+1) int64.  keys (N) int64 =
+ * ((set * C + cx) * C + cy) * C + cz, C = R - 1, c = min(floor(t), C - 1); a point outside the box gets B C^3 and is counted in
+ * outside (B) int32; a non-finite coordinate or normal gets B C^3 and sets bit 1 of status (1) int32. */
+int sfmi_poisson_keys_f32(const float* P, const float* Nrm, const long long* off, int B, long long N, int R, const double* box,
+                          long long* keys, int* outside, int* status, void* stream);
+/* sorted_keys (N) int64: the keys above in ascending order.  cell_start (B C^3 + 1) int32: the number of keys below each cell, i.e.
+ * where the cell's run begins in the sorted order; the last entry is the number of points inside the box. */
+int sfmi_poisson_cells_i32(const long long* sorted_keys, int B, long long N, int R, int* cell_start, void* stream);
+/* geoutil.py:330-331 (create_from_point_cloud_poisson: the vector field and the densities).  order (N) int64: the points sorted by
+ * key, stable; cell_start (B C^3 + 1) int32: where each cell's run begins in order.  A gather, one lane per node, f64 sums over the
+ * 27 cells around the node in ascending cell order and ascending input index within a cell, rounded to f32 once:
+ * W (B,R,R,R) += hat(tx-i) hat(ty-j) hat(tz-k); Vx (B,R-1,R,R) at ((i+1/2),j,k) += nx hat(tx-i-1/2) hat(ty-j) hat(tz-k); Vy (B,R,R-1,R)
+ * and Vz (B,R,R,R-1) likewise.  No float atomics: bit-identical from run to run, a set's result depends on that set alone. */
+int sfmi_poisson_splat_f32(const float* P, const float* Nrm, const long long* order, const int* cell_start, int B, long long N, int R,
+                           const double* box, float* Vx, float* Vy, float* Vz, float* W, void* stream);
+/* rhs (B,R,R,R) = -G^T V, G the forward difference from nodes to edges with zeros around the lattice:
+ * ((Vx[i] - Vx[i-1]) + (Vy[j] - Vy[j-1])) + (Vz[k] - Vz[k-1]) in f64, sites outside the arrays zero, rounded to f32 */
+int sfmi_poisson_rhs_f32(const float* Vx, const float* Vy, const float* Vz, int B, int R, float* rhs, void* stream);
+/* geoutil.py:330 (the solve inside create_from_point_cloud_poisson).  0 for sizes the solver refuses.  Three lattices (r, p, q), the
+ * partials of the dot products and the per-shape state. */
+size_t sfmi_poisson_cg_workspace_bytes(int B, int R);
+/* Conjugate gradients on A = G^T G (the 7-point operator, 6 on every diagonal entry) from x0 = 0: x = 0, r = p = rhs, the state of
+ * iteration 0.  A shape is frozen at the first iteration whose recursive residual satisfies |r| <= tol |rhs| (a zero rhs: from the
+ * start): its x stops changing and its counter stops. */
+int sfmi_poisson_cg_init_f32(const float* rhs, int B, int R, double tol, float* x, void* workspace, void* stream);
+/* n iterations, three launches each, nothing read back; it0: the iterations run on this workspace so far (the state is
+ * double-buffered by its parity).  f32 vectors, f64 dot products over a fixed tree: bit-identical from run to run and in any batch. */
+int sfmi_poisson_cg_steps_f32(int B, int R, int n, long long it0, float* x, void* workspace, void* stream);
+/* the state after `it` iterations: iterations (B) int32, residual (B) f64 = |r| / |rhs| (recursive; 0 for a zero rhs), done (B) int32 */
+int sfmi_poisson_cg_read_i32(int B, int R, long long it, const void* workspace, int* iterations, double* residual, int* done, void* stream);
+/* geoutil.py:330-334 (the iso-surface is taken at the points' own level).  iso (B) f64 = the mean of the trilinear chi over each
+ * set's in-box points (0 without one), a fixed f64 tree over chunks in input order; field = float(double(chi) - iso).  field may be chi. */
+int sfmi_poisson_iso_f32(const float* chi, const float* P, const long long* off, int B, long long N, int R, const double* box, double* iso,
+                         float* field, void* stream);
+/* geoutil.py:332-334 (densities, the quantile trim).  out (N) f32 = the trilinear sample of set b's lattice at its points (f64
+ * weights, rounded once; a point outside the box is sampled where it is clamped to) */
+int sfmi_poisson_sample_f32(const float* lattice, const float* P, const long long* off, int B, long long N, int R, const double* box,
+                            float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,17 @@ PROTOTYPES = {
     "sfmi_fps_f32": (i32, [c_ptr] * 4 + [i32, i64, i32] + [c_ptr] * 6),
     "sfmi_voxel_keys_f32": (i32, [c_ptr, c_ptr, i32, i64, C.c_double] + [c_ptr] * 4),
     "sfmi_voxel_reduce_f32": (i32, [c_ptr] * 4 + [i32, i64, i64, i32] + [c_ptr] * 4),
+    # Poisson surface reconstruction (csrc/poisson.hip)
+    "sfmi_poisson_keys_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 5),
+    "sfmi_poisson_cells_i32": (i32, [c_ptr, i32, i64, i32, c_ptr, c_ptr]),
+    "sfmi_poisson_splat_f32": (i32, [c_ptr] * 4 + [i32, i64, i32] + [c_ptr] * 6),
+    "sfmi_poisson_rhs_f32": (i32, [c_ptr] * 3 + [i32, i32] + [c_ptr] * 2),
+    "sfmi_poisson_cg_workspace_bytes": (sz, [i32, i32]),
+    "sfmi_poisson_cg_init_f32": (i32, [c_ptr, i32, i32, C.c_double] + [c_ptr] * 3),
+    "sfmi_poisson_cg_steps_f32": (i32, [i32, i32, i32, i64] + [c_ptr] * 3),
+    "sfmi_poisson_cg_read_i32": (i32, [i32, i32, i64] + [c_ptr] * 5),
+    "sfmi_poisson_iso_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 4),
+    "sfmi_poisson_sample_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 3),
 }
 
 

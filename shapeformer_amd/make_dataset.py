@@ -3,7 +3,8 @@ shapeformer/data/imnet_datasets/utils.py:33-70, with the occupancy the IMNet2 st
 
     python -m shapeformer_amd.make_dataset MESH... --out ROOT --dataset NAME --split train [--grid 64] [--boundary-n 32768]
                                            [--cate NAME=GLOB ...] [--seed 0] [--batch K] [--scale 1.0]
-                                           [--occupancy winding|morph] [--morph-grid 128] [--selem 6] [--morph-samples 1000000]
+                                           [--occupancy winding|morph|poisson] [--morph-grid 128] [--selem 6] [--morph-samples 1000000]
+                                           [--poisson-grid m*(grid-1)+1]
 
 Each mesh (.obj / .off / .ply) is normalised with normalize_point_set (bounding box centred, longest side 2) and multiplied by
 --scale, then batches of K meshes go through the device: lattice occupancy on the grid^3 makeGrid lattice of [-1, 1]^3 and
@@ -11,7 +12,12 @@ area-weighted surface samples (sample_mesh_dev).  --occupancy winding (the defau
 closed, consistently oriented meshes.  --occupancy morph is for triangle soups (open shells, interior partitions, doubled and flipped
 faces): morph_voxelization_dev's watertight voxels on a --morph-grid^3 grid (closing with a ball of --selem cells over --morph-samples
 surface samples), read at each lattice point from the cell that holds it; the outside is flooded from voxel (0,0,0), so a shape that
-fills the box needs --scale 0.9 or so to keep that corner empty.  The store is what data.Imnet2LowResDataset reads:
+fills the box needs --scale 0.9 or so to keep that corner empty.  --occupancy poisson is for scans: the inputs are .ply point clouds
+with nx/ny/nz normals (pointing outward) and no faces; a cloud is NOT normalised (a scan's bounding box is noise; normalise it upstream,
+scan.normalize_scan), only multiplied by --scale; Xbd is the cloud resampled to --boundary-n points and the occupancy is
+poisson_field_dev's field > 0 on a --poisson-grid^3 lattice of [-1, 1]^3, which must be m (grid - 1) + 1 nodes per axis so that the
+store's lattice is every m-th Poisson node (default: the smallest such lattice of at least 129 nodes).  The store is what
+data.Imnet2LowResDataset reads:
 
     ROOT/NAME/SPLIT/Xbd.npy          (n, boundary_n, 3) float32 surface samples
     ROOT/NAME/SPLIT/Ytg.npy          (n, grid^3 / 8) uint8 = np.packbits(occupancy.reshape(n, -1), axis=-1)
@@ -27,7 +33,7 @@ import sys
 import numpy as np
 
 
-OCCUPANCY = ("winding", "morph")
+OCCUPANCY = ("winding", "morph", "poisson")
 
 
 def write_imnet_store(root, dataset, split, Xbd, occ, cates=None):
@@ -68,11 +74,48 @@ def _morph_occupancy(v, f, voff, toff, names, lattice, grid, morph_grid, selem, 
     return o.reshape(B, grid, grid, grid), st
 
 
+def check_poisson_grid(grid, poisson_grid=None):
+    """-> m with poisson_grid = m (grid - 1) + 1: the store's nodes are every m-th node of the Poisson lattice.  None: the smallest
+    such lattice with at least 129 nodes per axis (129 itself for a store of 3, 5, 9, 17, 33, 65 or 129 nodes per axis)"""
+    if poisson_grid is None:
+        if grid < 2:
+            raise ValueError(f"--grid {grid}: --occupancy poisson needs a lattice of at least 2 nodes per axis")
+        return max(1, -(-128 // (grid - 1)))
+    if grid < 2 or poisson_grid < grid or (poisson_grid - 1) % (grid - 1):
+        raise ValueError(f"--poisson-grid {poisson_grid} must be m * (grid - 1) + 1 = m * {grid - 1} + 1 for an integer m >= 1")
+    return (poisson_grid - 1) // (grid - 1)
+
+
+def _poisson_batch(paths, grid, poisson_grid, boundary_n, scale, seed, dev):
+    """.ply clouds with normals -> Xbd (B, boundary_n, 3), occupancy (B, grid, grid, grid) uint8, both on the device"""
+    import torch
+    from . import meshio, poisson
+    from .hpr import resample_visible_dev
+    m = check_poisson_grid(grid, poisson_grid)
+    pts, nrm = [], []
+    for p in paths:
+        v, _, n = meshio.read_ply(p, with_normals=True)
+        if n is None:
+            raise ValueError(f"{p}: the cloud has no normals (nx/ny/nz): --occupancy poisson needs oriented points")
+        if len(v) == 0:
+            raise ValueError(f"{p}: no points")
+        pts.append(np.asarray(v * scale, np.float32))
+        nrm.append(np.asarray(n, np.float32))
+    off = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
+    x, n = torch.from_numpy(np.concatenate(pts)).to(dev), torch.from_numpy(np.concatenate(nrm)).to(dev)
+    field = poisson.poisson_field_dev(x, n, off, grid_dim=m * (grid - 1) + 1)[0]
+    occ = (field[:, ::m, ::m, ::m] > 0).to(torch.uint8)
+    ones = torch.ones(x.shape[0], device=dev, dtype=torch.uint8)
+    count = torch.from_numpy(np.diff(off).astype(np.int32)).to(dev)
+    return resample_visible_dev(x, off, ones, count, boundary_n, 0., seed), occ
+
+
 def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, cates=None, seed=0, batch=8, device="cuda:0",
-                 log=None, occupancy="winding", morph_grid=128, selem=6, morph_samples=1_000_000, scale=1.0):
+                 log=None, occupancy="winding", morph_grid=128, selem=6, morph_samples=1_000_000, scale=1.0, poisson_grid=None):
     """Read, normalise and sample every mesh of `paths`; write the store.  cates: {name: glob} matched against each path.
-    occupancy: "winding" (mesh_occupancy_dev) or "morph" (morph_voxelization_dev on a morph_grid^3 grid, ball of selem cells,
-    morph_samples surface samples); scale multiplies the normalised vertices on both routes."""
+    occupancy: "winding" (mesh_occupancy_dev), "morph" (morph_voxelization_dev on a morph_grid^3 grid, ball of selem cells,
+    morph_samples surface samples) or "poisson" (paths are .ply clouds with normals: poisson_field_dev on a poisson_grid^3 lattice);
+    scale multiplies the normalised vertices (poisson: the cloud as it is) on every route."""
     import torch
     from . import meshio, meshsdf
     from ._ragged import batch_meshes
@@ -81,6 +124,8 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
         raise ValueError(f"occupancy = {occupancy!r} must be one of {OCCUPANCY}")
     if not (np.isfinite(scale) and scale > 0):
         raise ValueError(f"scale = {scale!r} must be a positive number")
+    if occupancy == "poisson":
+        check_poisson_grid(grid, poisson_grid)
     dev = torch.device(device)
     Xbd, occ = [], []
     lattice = None
@@ -88,6 +133,13 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
         from .data import make_grid
         lattice = torch.from_numpy(make_grid([-1, -1, -1.], [1., 1, 1], [grid] * 3).astype(np.float32)).to(dev)
     for s in range(0, len(paths), batch):
+        if occupancy == "poisson":
+            x, o = _poisson_batch(paths[s:s + batch], grid, poisson_grid, boundary_n, scale, seed + s, dev)
+            occ.append(o.cpu().numpy())
+            Xbd.append(x.cpu().numpy())
+            if log:
+                log(f"[make_dataset] {min(s + batch, len(paths))}/{len(paths)} clouds")
+            continue
         meshes = []
         for p in paths[s:s + batch]:
             v, f = meshio.read_mesh(p)
@@ -124,7 +176,10 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--occupancy", choices=OCCUPANCY, default="winding",
-                    help="winding: |W| > 0.5, for closed oriented meshes; morph: watertight voxelization, for triangle soups")
+                    help="winding: |W| > 0.5, for closed oriented meshes; morph: watertight voxelization, for triangle soups; "
+                         "poisson: Poisson reconstruction of .ply point clouds with normals")
+    ap.add_argument("--poisson-grid", type=int, default=None,
+                    help="poisson: nodes per axis of the Poisson lattice, m * (grid - 1) + 1 (default: the smallest such >= 129)")
     ap.add_argument("--morph-grid", type=int, default=128, help="morph: voxels per axis of the watertight grid")
     ap.add_argument("--selem", type=int, default=6, help="morph: radius in voxels of the closing's ball (0 .. 16)")
     ap.add_argument("--morph-samples", type=int, default=1_000_000, help="morph: surface samples per mesh")
@@ -136,6 +191,11 @@ def parse_args(argv=None):
         ap.error("--selem must lie in [0, 16]")
     if not (np.isfinite(a.scale) and a.scale > 0):
         ap.error("--scale must be a positive number")
+    if a.occupancy == "poisson":
+        try:
+            check_poisson_grid(a.grid, a.poisson_grid)
+        except ValueError as e:
+            ap.error(str(e))
     cates = {}
     for c in a.cate:
         name, sep, g = c.partition("=")
@@ -150,7 +210,7 @@ def main(argv=None):
     a = parse_args(argv)
     d = make_dataset(a.meshes, a.out, a.dataset, a.split, a.grid, a.boundary_n, a.cates, a.seed, max(1, a.batch),
                      log=lambda m: print(m, file=sys.stderr), occupancy=a.occupancy, morph_grid=a.morph_grid, selem=a.selem,
-                     morph_samples=a.morph_samples, scale=a.scale)
+                     morph_samples=a.morph_samples, scale=a.scale, poisson_grid=a.poisson_grid)
     print(d)
 
 
