@@ -875,6 +875,34 @@ int sfmi_poisson_iso_f32(const float* chi, const float* P, const long long* off,
 int sfmi_poisson_sample_f32(const float* lattice, const float* P, const long long* off, int B, long long N, int R, const double* box,
                             float* out, void* stream);
 
+/* ---- Plane removal and Euclidean clustering of raw scans (csrc/segment.hip).  PCL SACSegmentation / Open3D
+ *      segment_plane and PCL EuclideanClusterExtraction / Open3D cluster_dbscan.  The reference has no such step: its real-scan datasets
+ *      (shapeformer/data/imnet_datasets/redwood.py:53-58,99-102, realtest.py:55-62,105-109) normalise and serve the cloud as it is read,
+ *      floor included; scan.isolate_object_dev runs these entries in front of those normalisations.
+ * Ragged sets as in sfmi_knn_f32: P (N,3) f32, off (B+1) int64 [device], every set below 2^31 points, B <= 65535.  max_n: the largest
+ * set's size (it sizes the grid only: any value gives the same result). */
+/* RANSAC scoring.  triples (B,H,3) int32 local indices; thr2 = threshold^2 as the host rounds it in f64.  In f64, every product and sum
+ * rounded on its own: u = p1 - p0, v = p2 - p0, n = u x v, nn = (nx nx + ny ny) + nz nz, d = (nx p0x + ny p0y) + nz p0z; a point x is an
+ * inlier iff s s <= thr2 nn with s = ((nx x + ny y) + nz z) - d.  count (B,H) int32: the inliers over the whole set, -1 for an invalid
+ * hypothesis (an index repeats or lies outside the set, or nn > 0 is false); best (B) int32: the valid hypothesis of largest count, the
+ * lowest h among equal counts, -1 without one; status (B) int32: 0 ok, 1 no valid hypothesis (fewer than 3 points among them), 2 a
+ * non-finite coordinate in the set (the row of count is then all -1).  Integer atomics only: a function of the input. */
+int sfmi_plane_score_f32(const float* P, const long long* off, const int* triples, int B, long long N, int H, long long max_n,
+                         double thr2, int* count, int* best, int* status, void* stream);
+/* The least-squares plane of a seed plane's inliers (Open3D segment_plane's last step).  Seed: the triple best[b] of triples (B,H,3)
+ * (status (B) or NULL: a set with status != 0 fails), or seed_plane (B,4) f64 (n, dd) when it is not NULL.  Its inliers by the rule above
+ * -> centroid c and covariance in f64, two passes summed in a fixed order -> the unit eigenvector n of the smallest eigenvalue (cyclic
+ * Jacobi, f64) -> dd = -n.c; sign: n.up >= 0 with up (B,3) f64, else the component of largest magnitude positive.  plane (B,4) f64
+ * (nx, ny, nz, dd); inlier (N) uint8 = fabs(n.x + dd) <= thr in f64; n_in (B) int32.  Fewer than 3 seed inliers or a failed set: plane
+ * NaN, mask 0, n_in 0.  refit == 0: inlier / n_in are the seed's own inliers by the rule above and plane is not written. */
+int sfmi_plane_refit_f32(const float* P, const long long* off, const int* triples, const int* best, const int* status,
+                         const double* seed_plane, const double* up, int B, long long N, int H, double thr, int refit, double* plane,
+                         unsigned char* inlier, int* n_in, void* stream);
+/* Euclidean clusters: two points of a set are joined iff fmaf(dz, dz, fmaf(dy, dy, dx dx)) <= r2 in f32 (the d2 bits of sfmi_knn_f32);
+ * root (N) int32 = the lowest local index of the point's connected component.  A NaN coordinate joins nothing.  Lock-free union-find
+ * (compare-and-swap on roots): the result does not depend on the schedule. */
+int sfmi_cluster_f32(const float* P, const long long* off, int B, long long N, long long max_n, float r2, int* root, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

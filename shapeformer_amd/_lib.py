@@ -245,6 +245,10 @@ PROTOTYPES = {
     "sfmi_poisson_cg_read_i32": (i32, [i32, i32, i64] + [c_ptr] * 5),
     "sfmi_poisson_iso_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 4),
     "sfmi_poisson_sample_f32": (i32, [c_ptr] * 3 + [i32, i64, i32] + [c_ptr] * 3),
+    # plane removal and Euclidean clustering (csrc/segment.hip)
+    "sfmi_plane_score_f32": (i32, [c_ptr] * 3 + [i32, i64, i32, i64, C.c_double] + [c_ptr] * 4),
+    "sfmi_plane_refit_f32": (i32, [c_ptr] * 7 + [i32, i64, i32, C.c_double, i32] + [c_ptr] * 4),
+    "sfmi_cluster_f32": (i32, [c_ptr, c_ptr, i32, i64, i64, C.c_float, c_ptr, c_ptr]),
 }
 
 

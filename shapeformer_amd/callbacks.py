@@ -202,7 +202,7 @@ class VisShapeFormer(VisCallback):
                  eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, refine_steps=0,
                  vertex_normals=False, keep_components=None, clean_context=None, **kw):
         super().__init__(**kw)
-        # clean_context: a dict of scan.clean_cloud_dev keyword arguments (k, std_ratio, seed): compute_batch removes the
+        # clean_context: a dict of scan.clean_cloud_dev keyword arguments (k, std_ratio, seed, voxel, resample, remove_planes, keep_cluster): compute_batch removes the
         # statistical outliers of Xct on the device before encode_cloud, resampled back to Xct's point count, and records the kept
         # count as `context_kept` in the computed dict.  For raw scans (data.ScanDataset).  None: off, the path as it always was
         if clean_context is not None and (not isinstance(clean_context, dict) or "out_N" in clean_context):

@@ -272,27 +272,7 @@ __global__ void knn_mean_dist_kernel(const float* __restrict__ d2, long long N, 
 
 // ---- normals by local PCA -------------------------------------------------------------------------------------------------------
 
-// one Jacobi rotation of the symmetric 3x3 matrix in the plane (p, q), r the third axis: zeroes a_pq.  v*p / v*q: columns p and q of
-// the accumulated eigenvector matrix.  Branch-free: a_pq == 0 is the identity rotation.
-__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
-                                           double& v1p, double& v1q, double& v2p, double& v2q) {
-  const double theta = (aqq - app) / (2.0 * apq);
-  double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));      // |theta| huge: t -> 0
-  t = apq == 0.0 ? 0.0 : t;
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  app -= t * apq;
-  aqq += t * apq;
-  apq = 0.0;
-  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-  arp = rp; arq = rq;
-  const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
-  const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
-  const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
-  v0p = a0; v0q = b0; v1p = a1; v1q = b1; v2p = a2; v2q = b2;
-}
-
-constexpr int KNN_JACOBI_SWEEPS = 8;             // a 3x3 in f64 is converged to the last bit after 5 or 6
-
+// jacobi_rot and KNN_JACOBI_SWEEPS: sfmi_ragged.h (csrc/segment.hip's plane refit runs the same solver)
 __global__ void knn_normals_kernel(const float* __restrict__ P, const long long* __restrict__ off, const int* __restrict__ idx, int B,
                                    long long N, int k, const double* __restrict__ view, float* __restrict__ normal,
                                    float* __restrict__ variation) {

@@ -1,8 +1,8 @@
 // Shared pieces of the mesh tools: what csrc/pointdist.hip, meshsdf.hip, hpr.hip, iso_sparse.hip, simplify.hip,
 // components.hip and morph.hip all need for ragged batches.  A ragged batch is B sets stored back to back with (B+1) nondecreasing
 // offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b with off[b] <= x < off[b+1].  Everything here is
-// inlined into its caller; none of it holds a multiply-add, so a caller's `#pragma clang fp contract(off)` after this include
-// changes nothing in here.
+// inlined into its caller; apart from jacobi_rot below none of it holds a multiply-add, and a caller's `#pragma clang fp contract(off)`
+// comes after this include, so it changes nothing in here.
 #pragma once
 #include "sfmi_common.h"
 
@@ -92,6 +92,30 @@ __device__ __forceinline__ unsigned long long sfmi_mix64(unsigned long long x) {
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
+
+// ---- symmetric 3x3 eigen-solver in f64: the cyclic Jacobi step of knn.hip's normals and segment.hip's plane refit -------------------
+// (the one piece of this header with products feeding sums: it is compiled under the build's contraction setting in every includer,
+// because each includer's `#pragma clang fp contract(off)` comes after this include)
+// one Jacobi rotation of the symmetric 3x3 matrix in the plane (p, q), r the third axis: zeroes a_pq.  v*p / v*q: columns p and q of
+// the accumulated eigenvector matrix.  Branch-free: a_pq == 0 is the identity rotation.
+__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
+                                           double& v1p, double& v1q, double& v2p, double& v2q) {
+  const double theta = (aqq - app) / (2.0 * apq);
+  double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));      // |theta| huge: t -> 0
+  t = apq == 0.0 ? 0.0 : t;
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq;
+  aqq += t * apq;
+  apq = 0.0;
+  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+  arp = rp; arq = rq;
+  const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
+  const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
+  const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
+  v0p = a0; v0q = b0; v1p = a1; v1q = b1; v2p = a2; v2q = b2;
+}
+
+constexpr int KNN_JACOBI_SWEEPS = 8;             // a 3x3 in f64 is converged to the last bit after 5 or 6
 
 // ---- per-shape mesh validation: flag bits that kernels OR into flags[b], and the status code they stand for ------------------------
 constexpr int SFMI_MESH_NO_VERTS = 1, SFMI_MESH_BAD_INDEX = 2, SFMI_MESH_NON_FINITE = 4;   // the status is the lowest one set

@@ -13,7 +13,15 @@ cKDTree.query); here it is exact brute force on the device, the sibling of metri
   normalize_scan(points, mode, scale)                     -> the four normalisations of the reference's real-scan datasets (host or device)
   farthest_point_sample_dev(points, off, n, start, valid) -> idx (B,n) int32, d2 (B,n) f32, count (B,), status (B,)   (csrc/downsample.hip,
   voxel_downsample_dev(points, off, voxel, pick)          -> out (M,3) f32, out_off (B+1,) host, first (M,), count (M,)       DESIGN.md §5.15)
-  clean_cloud_dev(X, k, std_ratio, out_N, seed, voxel, resample) -> (B, out_N, 3) cleaned clouds of a fixed size, count (B,)
+  plane_hypotheses(sizes, H, seed)                        -> (B,H,3) int32 RANSAC draws on the host                   (csrc/segment.hip,
+  segment_plane_dev(points, off, threshold, hypotheses, ...) -> plane (B,4) f64, inlier (N,), n_in, count (B,H), best, status  DESIGN.md §5.17)
+  refit_plane_dev(points, off, plane, threshold, up)      -> plane (B,4) f64, inlier (N,), n_in: the refit seeded by any plane
+  remove_planes_dev(points, off, threshold, max_planes, min_ratio, ...) -> keep (N,) uint8, planes (B,max_planes,4), taken (B,)
+  euclidean_clusters_dev(points, off, radius, min_points) -> label (N,) int32, sizes, c_off (B+1,) host
+  largest_cluster_mask_dev(points, off, radius, min_points) -> keep (N,) uint8, count (B,)
+  upright_rotation(normal, up)                            -> (B,3,3) f64 (host or device)
+  isolate_object_dev(points, off, plane_threshold, cluster_radius, ...) -> kept points, offsets, mask, planes, rotation
+  clean_cloud_dev(X, k, std_ratio, out_N, seed, voxel, resample, remove_planes, keep_cluster) -> (B, out_N, 3) cleaned clouds, count (B,)
 
 Ragged batches and their argument checks are _ragged.py's: every refusal is an SfmiError raised on the host before
 the library is loaded, and where the tensors live is checked last.  There is no CPU fallback.
@@ -349,9 +357,360 @@ def voxel_downsample_dev(points, off=None, voxel=None, pick="centroid"):
     return out, out_off, first, count
 
 
+# ---- plane removal and Euclidean clustering (csrc/segment.hip) -----------------------------------------------------
+
+def _mix64(x):
+    """sfmi_mix64 of csrc/sfmi_ragged.h on a numpy uint64 array (wrapping arithmetic)"""
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def _check_count(v, what, name, lo=1):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < 2 ** 31:
+        raise L.SfmiError(f"{what}: {name} must be an integer in [{lo}, 2^31), got {v!r}")
+    return int(v)
+
+
+def _check_nonneg(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
+        raise L.SfmiError(f"{what}: {name} must be a finite number >= 0, got {v!r}")
+    return float(v)
+
+
+def plane_hypotheses(sizes, H, seed=0):
+    """The RANSAC draws of segment_plane_dev: (B,H,3) int32 on the host, index = sfmi_mix64((seed << 40) + 4 h + slot) mod n_b (uint64
+    arithmetic): a function of (seed, h, slot, n) and not of b, so a batch draws what per-set calls draw.  Repeated indices are not
+    redrawn: the kernel marks such a hypothesis invalid.  A set of no points gets index 0, which lies outside it."""
+    H = _check_count(H, "plane_hypotheses", "H")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 23:
+        raise L.SfmiError(f"plane_hypotheses: seed must be an integer in [0, 2^23), got {seed!r}")
+    n = np.asarray(sizes, np.int64).reshape(-1)
+    if (n < 0).any():
+        raise L.SfmiError("plane_hypotheses: sizes must be >= 0")
+    ctr = np.uint64(int(seed) << 40) + np.uint64(4) * np.arange(H, dtype=np.uint64)[:, None] + np.arange(3, dtype=np.uint64)[None, :]
+    r = _mix64(ctr)
+    return (r[None] % np.maximum(n, 1).astype(np.uint64)[:, None, None]).astype(np.int32)
+
+
+def _max_n(o):
+    return int(np.diff(o).max()) if len(o) > 1 else 0
+
+
+def _set_ids(o, dev):
+    """(N,) int64: the set of every point"""
+    return torch.repeat_interleave(torch.arange(len(o) - 1, device=dev), torch.from_numpy(np.diff(o)).to(dev), output_size=int(o[-1]))
+
+
+def _up_arg(up, B, what):
+    if up is None:
+        return None
+    u = up.detach().cpu().numpy() if isinstance(up, torch.Tensor) else np.asarray(up)
+    u = np.asarray(u, np.float64)
+    if u.shape == (3,):
+        u = np.broadcast_to(u, (B, 3))
+    if u.shape != (B, 3) or not np.isfinite(u).all():
+        raise L.SfmiError(f"{what}: up must be finite, (3,) or ({B},3), got shape {tuple(u.shape)}")
+    return np.array(u, np.float64, order="C")          # a copy: broadcast_to gives a read-only view
+
+
+def _triple_plane(xf, od, tr, best, upd):
+    """refit=False: the plane of the winning triple, unit normal, in f64 by elementwise torch arithmetic (one rounding per operation)"""
+    B = best.shape[0]
+    nan = torch.full((B, 4), float("nan"), device=xf.device, dtype=torch.float64)
+    if xf.shape[0] == 0:
+        return nan
+    t = tr[torch.arange(B, device=xf.device), best.clamp(min=0).long()].long() + od[:-1, None]
+    p = xf[t.clamp(0, xf.shape[0] - 1)].double()                                          # (B,3,3): a set without a winner reads any row
+    u, v, p0 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0], p[:, 0]
+    n = torch.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]], 1)
+    n = n / torch.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])[:, None]
+    if upd is not None:
+        flip = ((n[:, 0] * upd[:, 0] + n[:, 1] * upd[:, 1]) + n[:, 2] * upd[:, 2]) < 0
+    else:
+        flip = n.gather(1, n.abs().argmax(1, keepdim=True))[:, 0] < 0
+    n = torch.where(flip[:, None], -n, n)
+    dd = -((n[:, 0] * p0[:, 0] + n[:, 1] * p0[:, 1]) + n[:, 2] * p0[:, 2])
+    return torch.where((best >= 0)[:, None], torch.cat([n, dd[:, None]], 1), nan)
+
+
+def segment_plane_dev(points, off=None, threshold=0.01, hypotheses=1024, seed=0, triples=None, up=None, refit=True):
+    """The dominant plane of every set by RANSAC (PCL SACSegmentation, Open3D segment_plane), exact and deterministic.
+
+    points (N,3) f32 HIP tensor with (B+1,) offsets (None: one set), or a (B,M,3) batch.  -> plane (B,4) f64 (nx, ny, nz, dd) with
+    n.x + dd = 0 and |n| = 1, inlier (N,) uint8 ((B,M) for a batch), n_in (B,) int32, count (B,H) int32, best (B,) int32, status (B,)
+    int32, all on the device; the call does not synchronise.
+    Hypotheses are point triples: plane_hypotheses(sizes, hypotheses, seed), or `triples` (B,H,3) integers local to each set.  Scoring,
+    in f64 with every product and sum rounded on its own: n = (p1 - p0) x (p2 - p0), nn = (nx nx + ny ny) + nz nz, d = (nx p0x + ny p0y)
+    + nz p0z; x is an inlier iff s s <= threshold^2 nn with s = ((nx x + ny y) + nz z) - d.  count[b,h] = the inliers of hypothesis h over
+    the set, -1 for an invalid one (an index repeats or lies outside the set, or nn > 0 is false: collinear points); best[b] = the valid
+    hypothesis of largest count, the lowest h among equal counts, -1 without one; status: 0 ok, 1 no valid hypothesis (a set of fewer
+    than 3 points has none), 2 a non-finite coordinate in the set (its row of count is all -1).
+    refit=True (Open3D's last step): the least-squares plane of the winner's inliers - centroid and covariance in f64 summed in a fixed
+    order, the eigenvector of the smallest eigenvalue, dd = -n.c - and inlier = fabs(n.x + dd) <= threshold in f64.  refit=False: the
+    winner's own plane, normalised in f64, and its inliers by the scoring rule.  Sign: n.up >= 0 with up ((3,) or (B,3)), else the
+    component of largest magnitude is positive.  A set without a winner, or whose winner has fewer than 3 inliers: plane NaN, mask 0,
+    n_in 0.  Bit-identical from run to run; a set's results depend on that set alone."""
+    what = "segment_plane_dev"
+    thr = _check_nonneg(threshold, what, "threshold")
+    x, o, shape = point_sets(points, off, what)
+    B, N = len(o) - 1, x.shape[0]
+    if B > 65535 or (np.diff(o) >= 2 ** 31).any():
+        raise L.SfmiError(f"{what}: at most 65535 sets, each below 2^31 points")
+    if triples is None:
+        tr = plane_hypotheses(np.diff(o), _check_count(hypotheses, what, "hypotheses"), seed)
+    else:
+        tr = triples
+        if not isinstance(tr, torch.Tensor):
+            tr = np.asarray(tr)
+            if tr.dtype == np.bool_ or not np.issubdtype(tr.dtype, np.integer):
+                raise L.SfmiError(f"{what}: triples must be integers")
+        elif tr.dtype.is_floating_point or tr.dtype == torch.bool:
+            raise L.SfmiError(f"{what}: triples must be integers")
+        if tr.ndim != 3 or tr.shape[0] != B or tr.shape[1] < 1 or tr.shape[2] != 3:
+            raise L.SfmiError(f"{what}: triples must be ({B},H,3) with H >= 1, got {tuple(tr.shape)}")
+    H = int(tr.shape[1])
+    upa = _up_arg(up, B, what)
+    dev = on_device(what, x, *([tr] if isinstance(tr, torch.Tensor) else []))
+    xf = x.float().contiguous()
+    trd = (tr if isinstance(tr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tr)).to(dev)).to(torch.int32).contiguous()
+    od = torch.from_numpy(o).to(dev)
+    upd = torch.from_numpy(upa).to(dev) if upa is not None else None
+    count = torch.empty(B, H, device=dev, dtype=torch.int32)
+    best = torch.empty(B, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    plane = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    inlier = torch.empty(N, device=dev, dtype=torch.uint8)
+    n_in = torch.empty(B, device=dev, dtype=torch.int32)
+    lib = L.lib()
+    L.check(lib.sfmi_plane_score_f32(L.ptr(xf), L.ptr(od), L.ptr(trd), B, N, H, _max_n(o), thr * thr, L.ptr(count), L.ptr(best),
+                                     L.ptr(status), L.stream_ptr()), "sfmi_plane_score_f32")
+    L.check(lib.sfmi_plane_refit_f32(L.ptr(xf), L.ptr(od), L.ptr(trd), L.ptr(best), L.ptr(status), None, L.ptr(upd), B, N, H, thr,
+                                     int(bool(refit)), L.ptr(plane), L.ptr(inlier), L.ptr(n_in), L.stream_ptr()), "sfmi_plane_refit_f32")
+    if not refit:
+        plane = _triple_plane(xf, od, trd, best, upd)
+    return plane, (inlier.reshape(shape) if shape else inlier), n_in, count, best, status
+
+
+def refit_plane_dev(points, off=None, plane=None, threshold=0.01, up=None):
+    """The least-squares plane of a given plane's inliers, segment_plane_dev's refit seeded by any plane: plane (B,4) (or (4,) for one
+    set) f64 (n, dd), n of any length > 0.  Its inliers are the points with s s <= threshold^2 nn, s = ((nx x + ny y) + nz z) + dd,
+    nn = (nx nx + ny ny) + nz nz, in f64; centroid, covariance, eigenvector, sign and final mask as in segment_plane_dev.
+    -> plane (B,4) f64, inlier (N,) uint8 ((B,M) for a batch), n_in (B,) int32.  A seed that is not finite or has n = 0, or fewer than
+    3 seed inliers: plane NaN, mask 0, n_in 0.  Calling it on its own output iterates the fit."""
+    what = "refit_plane_dev"
+    thr = _check_nonneg(threshold, what, "threshold")
+    x, o, shape = point_sets(points, off, what)
+    B, N = len(o) - 1, x.shape[0]
+    if isinstance(plane, torch.Tensor):
+        seed = plane.detach().to(torch.float64)
+    else:
+        seed = torch.from_numpy(np.array(plane, np.float64)) if plane is not None else None
+    if seed is not None and tuple(seed.shape) == (4,) and B == 1:
+        seed = seed[None]
+    if seed is None or tuple(seed.shape) != (B, 4):
+        raise L.SfmiError(f"{what}: plane must be ({B},4), got {None if seed is None else tuple(seed.shape)}")
+    upa = _up_arg(up, B, what)
+    dev = on_device(what, x)
+    xf, seed = x.float().contiguous(), seed.to(dev).contiguous()
+    od = torch.from_numpy(o).to(dev)
+    upd = torch.from_numpy(upa).to(dev) if upa is not None else None
+    out = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    inlier = torch.empty(N, device=dev, dtype=torch.uint8)
+    n_in = torch.empty(B, device=dev, dtype=torch.int32)
+    L.check(L.lib().sfmi_plane_refit_f32(L.ptr(xf), L.ptr(od), None, None, None, L.ptr(seed), L.ptr(upd), B, N, 0, thr, 1, L.ptr(out),
+                                         L.ptr(inlier), L.ptr(n_in), L.stream_ptr()), "sfmi_plane_refit_f32")
+    return out, (inlier.reshape(shape) if shape else inlier), n_in
+
+
+def remove_planes_dev(points, off=None, threshold=0.01, max_planes=1, min_ratio=0.2, hypotheses=1024, seed=0, up=None, refit=True):
+    """Up to max_planes dominant planes per set, one after the other: -> keep (N,) uint8 (0 on a removed plane; (B,M) for a batch), planes
+    (B,max_planes,4) f64 (NaN rows where none was taken), taken (B,) int32, on the device.
+    Round r runs segment_plane_dev with seed + r on what the earlier rounds left of each set, compacted.  A set takes the round's plane
+    when its inliers (n_in) are at least 3 and at least min_ratio x the set's ORIGINAL point count; otherwise it stops for good.
+    Between two rounds the per-set counts are read back (one synchronisation per round after the first) to cut the compacted batch;
+    max_planes = 1 reads nothing back."""
+    what = "remove_planes_dev"
+    _check_nonneg(threshold, what, "threshold")
+    max_planes = _check_count(max_planes, what, "max_planes")
+    min_ratio = _check_nonneg(min_ratio, what, "min_ratio")
+    _check_count(hypotheses, what, "hypotheses")
+    x, o, shape = point_sets(points, off, what)
+    B, N = len(o) - 1, x.shape[0]
+    _up_arg(up, B, what)
+    dev = on_device(what, x)
+    cur, co = x.float().contiguous(), o
+    idx = torch.arange(N, device=dev)
+    keep = torch.ones(N, device=dev, dtype=torch.uint8)
+    planes = torch.full((B, max_planes, 4), float("nan"), device=dev, dtype=torch.float64)
+    taken = torch.zeros(B, device=dev, dtype=torch.int32)
+    active = torch.ones(B, device=dev, dtype=torch.bool)
+    need = min_ratio * torch.from_numpy(np.diff(o)).to(dev).double()
+    for r in range(max_planes):
+        plane, inl, n_in, _, _, _ = segment_plane_dev(cur, co, threshold, hypotheses, seed + r, None, up, refit)
+        active = active & (n_in >= 3) & (n_in.double() >= need)
+        planes[:, r] = torch.where(active[:, None], plane, planes[:, r])
+        taken += active.to(torch.int32)
+        sid = _set_ids(co, dev)
+        drop = inl.bool() & active[sid]
+        keep[idx[drop]] = 0
+        if r + 1 == max_planes:
+            break
+        rem = ~drop & active[sid]                                   # a set that has stopped brings no points to the next round
+        head = _counts(rem.to(torch.uint8), co).cpu().numpy()      # the read-back of the round
+        if not head.any():
+            break
+        cur, idx = cur[rem], idx[rem]
+        co = np.concatenate([[0], np.cumsum(head)]).astype(np.int64)
+    return (keep.reshape(shape) if shape else keep), planes, taken
+
+
+def _cluster_roots(xf, o, r2):
+    dev = xf.device
+    root = torch.empty(xf.shape[0], device=dev, dtype=torch.int32)
+    if xf.shape[0]:
+        od = torch.from_numpy(o).to(dev)
+        L.check(L.lib().sfmi_cluster_f32(L.ptr(xf), L.ptr(od), len(o) - 1, xf.shape[0], _max_n(o), r2, L.ptr(root), L.stream_ptr()),
+                "sfmi_cluster_f32")
+    return root
+
+
+def euclidean_clusters_dev(points, off=None, radius=None, min_points=1, return_root=False):
+    """Euclidean cluster extraction (PCL EuclideanClusterExtraction; Open3D cluster_dbscan with min_points = 1), exact.
+
+    points (N,3) f32 HIP tensor with (B+1,) offsets (None: one set), or a (B,M,3) batch.  Two points of a set are joined iff
+    fmaf(dz, dz, fmaf(dy, dy, dx dx)) <= radius^2 with the square rounded to f32 and the compare in f32 (knn_dev's d2 bits, the rule of
+    radius_outlier_mask_dev); a cluster is a connected component of that graph; a point with a NaN coordinate is a cluster of its own.
+    -> label (N,) int32 ((B,M) for a batch): the rank of the point's cluster in its set under (size descending, lowest member index
+    ascending), -1 for clusters of fewer than min_points points; sizes: int32 on the device, the kept clusters' sizes set after set in
+    rank order; c_off (B+1,) host int64 offsets into sizes (the cluster counts are read back: one synchronisation).
+    return_root: also root (N,) int32, the lowest local index of each point's cluster, as the library returns it.
+    Bit-identical from run to run (lock-free union-find whose result does not depend on the schedule); a set's labels depend on that
+    set alone.  Brute force over N^2 / 2 pairs per set: meant to run after voxel_downsample_dev, not on 10^6 raw points."""
+    what = "euclidean_clusters_dev"
+    if radius is None or isinstance(radius, bool) or not float(radius) >= 0:
+        raise L.SfmiError(f"{what}: radius must be >= 0, got {radius!r}")
+    min_points = _check_count(min_points, what, "min_points")
+    x, o, shape = point_sets(points, off, what)
+    B, N = len(o) - 1, x.shape[0]
+    if B > 65535 or (np.diff(o) >= 2 ** 31).any():
+        raise L.SfmiError(f"{what}: at most 65535 sets, each below 2^31 points")
+    dev = on_device(what, x)
+    xf = x.float().contiguous()
+    root = _cluster_roots(xf, o, float(np.float32(float(radius) ** 2)))
+    if N == 0:
+        out = (root.clone(), torch.empty(0, device=dev, dtype=torch.int32), np.zeros(B + 1, np.int64))
+        return out + (root,) if return_root else out
+    od = torch.from_numpy(o).to(dev)
+    sid = _set_ids(o, dev)
+    g = root.long() + od[sid]                                                   # the root as a batch index
+    size_at = torch.bincount(g, minlength=N)                                    # at a root: its cluster's size; elsewhere 0
+    roots = torch.nonzero(size_at >= min_points)[:, 0]                          # ascending: (set, root)
+    by_size = torch.sort(-size_at[roots], stable=True).indices
+    by_set = torch.sort(sid[roots][by_size], stable=True).indices
+    ranked = roots[by_size[by_set]]                                             # (set, size descending, root ascending)
+    c_off_d = torch.searchsorted(sid[ranked].contiguous(), torch.arange(B + 1, device=dev))
+    rank_at = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    rank_at[ranked] = (torch.arange(ranked.shape[0], device=dev) - c_off_d[sid[ranked]]).to(torch.int32)
+    label = rank_at[g]
+    out = ((label.reshape(shape) if shape else label), size_at[ranked].to(torch.int32), c_off_d.cpu().numpy().astype(np.int64))
+    return out + (root,) if return_root else out
+
+
+def largest_cluster_mask_dev(points, off=None, radius=None, min_points=1):
+    """-> keep (N,) uint8 ((B,M) for a batch): the points of each set's largest Euclidean cluster (euclidean_clusters_dev's rank 0: the
+    one with the lowest member index among equally large ones), count (B,) int32 its size, 0 where no cluster reaches min_points."""
+    label, _, _ = euclidean_clusters_dev(points, off, radius, min_points)
+    keep = (label == 0).to(torch.uint8)
+    _, o, _ = point_sets(points, off, "largest_cluster_mask_dev")
+    return keep, _counts(keep.reshape(-1), o)
+
+
+def upright_rotation(normal, up=(0, 1, 0)):
+    """(B,3,3) f64 rotations that take each `normal` (B,3) or (3,) onto `up`: the reference's geoutil.rotation_v1tov2 (xgutils/
+    geoutil.py:14-19), a turn of 180 degrees about the bisector a of the two unit vectors, R = 2 a a^T - I, in plain arithmetic.  For
+    normal = -up the bisector vanishes: the turn is about the first coordinate axis not parallel to up.  numpy in -> numpy out, torch
+    in -> torch out (on the tensor's device)."""
+    is_t = isinstance(normal, torch.Tensor)
+    xp = torch if is_t else np
+    n = normal.to(torch.float64) if is_t else np.asarray(normal, np.float64)
+    if n.shape[-1:] != (3,) or n.ndim not in (1, 2):
+        raise L.SfmiError(f"upright_rotation: expected (3,) or (B,3) normals, got {tuple(n.shape)}")
+    n = n.reshape(-1, 3)
+    u = np.asarray(up.detach().cpu().numpy() if isinstance(up, torch.Tensor) else up, np.float64)
+    if u.shape != (3,) or not np.isfinite(u).all() or not np.linalg.norm(u) > 0:
+        raise L.SfmiError("upright_rotation: up must be a finite non-zero (3,) vector")
+    u = u / np.linalg.norm(u)
+    e = np.zeros(3)
+    e[int(np.argmax(np.abs(np.cross(np.eye(3), u)).sum(1) > 1e-12))] = 1.0      # the first axis not parallel to up
+    fb = e - (e @ u) * u
+    fb = fb / np.linalg.norm(fb)                                                # its part orthogonal to up: the antiparallel case's axis
+    if is_t:
+        u, fb = torch.from_numpy(u).to(n.device), torch.from_numpy(fb).to(n.device)
+    v = n / xp.sqrt((n * n).sum(-1))[:, None]
+    a = v + u
+    la = xp.sqrt((a * a).sum(-1))[:, None]
+    a = xp.where(la > 1e-8, a / xp.where(la > 1e-8, la, xp.ones_like(la)), fb[None] + 0 * a)
+    eye = torch.eye(3, dtype=torch.float64, device=n.device) if is_t else np.eye(3)
+    return 2.0 * a[:, :, None] * a[:, None, :] - eye[None]
+
+
+def _compact(xf, o, keep):
+    """the kept points of a ragged batch, their host offsets (one read-back) and their indices into xf"""
+    count = _counts(keep, o).cpu().numpy()
+    idx = torch.nonzero(keep)[:, 0]
+    return xf[idx], np.concatenate([[0], np.cumsum(count)]).astype(np.int64), idx
+
+
+def isolate_object_dev(points, off=None, plane_threshold=0.01, cluster_radius=0.05, max_planes=1, min_ratio=0.2, min_points=1,
+                       up=(0, 1, 0), normalize=None, scale=None, hypotheses=1024, seed=0):
+    """The object of a raw scan without its floor and its surroundings: remove_planes_dev -> turn the first plane's normal onto `up`
+    (upright_rotation) -> largest_cluster_mask_dev on what is left -> optionally normalize_scan(mode=normalize, scale) set by set.
+    -> kept (M,3) f32 points, ragged; k_off (B+1,) host int64; mask (N,) uint8 over the input ((B,M) for a batch); planes
+    (B,max_planes,4) f64; rotation (B,3,3) f64 (identity for a set that gave no plane).
+    The first plane's normal is pointed at the side that holds the rest of the set (the mean signed distance of the points off the
+    planes is >= 0) before it is turned onto up: an object stands ON its floor.  Points are rotated in f64 and rounded to f32 once;
+    clustering runs on the points as they came.  Two read-backs (the compactions), plus remove_planes_dev's between rounds."""
+    what = "isolate_object_dev"
+    if normalize is not None and normalize not in NORMALIZE_MODES:
+        raise L.SfmiError(f"{what}: normalize must be None or one of {NORMALIZE_MODES}, got {normalize!r}")
+    if cluster_radius is None or isinstance(cluster_radius, bool) or not float(cluster_radius) >= 0:
+        raise L.SfmiError(f"{what}: cluster_radius must be >= 0, got {cluster_radius!r}")
+    _check_count(min_points, what, "min_points")
+    x, o, shape = point_sets(points, off, what)
+    B = len(o) - 1
+    keep, planes, taken = remove_planes_dev(x, o, plane_threshold, max_planes, min_ratio, hypotheses, seed)
+    dev = x.device
+    xf = x.float().contiguous()
+    rest, ro, ridx = _compact(xf, o, keep)
+    plane0 = planes[:, 0].clone()
+    if rest.shape[0]:
+        sid = _set_ids(ro, dev)
+        sd = (rest.double() * plane0[sid, :3]).sum(1) + plane0[sid, 3]
+        side = torch.zeros(B, device=dev, dtype=torch.float64).index_add_(0, sid, torch.nan_to_num(sd))
+        plane0 = torch.where((side < 0)[:, None], -plane0, plane0)
+        planes = planes.clone()
+        planes[:, 0] = plane0
+    has = taken > 0
+    rot = upright_rotation(torch.where(has[:, None], plane0[:, :3], torch.from_numpy(np.asarray(up, np.float64)).to(dev)[None]), up)
+    big, _ = largest_cluster_mask_dev(rest, ro, cluster_radius, min_points)
+    kept, k_off, kidx = _compact(rest, ro, big)
+    mask = torch.zeros(xf.shape[0], device=dev, dtype=torch.uint8)
+    mask[ridx[kidx]] = 1
+    if kept.shape[0]:
+        kept = torch.einsum("nij,nj->ni", rot[_set_ids(k_off, dev)], kept.double()).float()
+    if normalize is not None:
+        kw = {} if scale is None else {"scale": scale}
+        kept = torch.cat([normalize_scan(kept[int(k_off[b]):int(k_off[b + 1])], normalize, **kw) if k_off[b + 1] > k_off[b]
+                          else kept[:0] for b in range(B)]) if B else kept
+    return kept, k_off, (mask.reshape(shape) if shape else mask), planes, rot
+
+
 # ---- the cleaning front end --------------------------------------------------------------------------------------------------------
 
-def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0, voxel=None, resample="random"):
+def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0, voxel=None, resample="random", remove_planes=None, keep_cluster=None):
     """Statistical outlier removal of a batch of clouds, back at a fixed size: X (B,N,3) HIP tensor -> (B, out_N or N, 3) f32, each row
     a uniformly drawn kept point of its cloud (hpr.resample_visible_dev with the mask as `visible`: a counter hash of (seed, cloud
     index, row), no global RNG), and count (B,) int32 kept points per cloud.  That function's fallback applies: a cloud with two or
@@ -360,7 +719,11 @@ def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0, voxel=None, resa
     the ragged result (a density test wants one density) and count is the number of kept voxels.
     resample="fps": the rows are the kept points in farthest-point order (farthest_point_sample_dev with the mask as `valid`); a cloud
     that keeps fewer than out_N points continues cyclically through that order (row r = order[r mod count]); two or fewer kept points:
-    all the cloud's points, as above.  The defaults take exactly the path this function always took."""
+    all the cloud's points, as above.
+    remove_planes / keep_cluster: dicts of remove_planes_dev / largest_cluster_mask_dev keyword arguments (threshold, max_planes,
+    min_ratio, ...; radius, min_points).  The order is voxel -> planes -> outlier rule -> largest cluster -> resample: each step runs on
+    what the step before kept, compacted (one read-back each), and count is what is kept at the end.
+    The defaults take exactly the path this function always took."""
     from .hpr import resample_visible_dev
     x = points_arg(X, "clean_cloud_dev")
     if x.dim() != 3:
@@ -372,8 +735,28 @@ def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0, voxel=None, resa
         raise L.SfmiError(f"clean_cloud_dev: resample must be one of {RESAMPLE_MODES}, got {resample!r}")
     if voxel is not None:
         voxel = _check_voxel(voxel, "clean_cloud_dev")
+    for name, d in (("remove_planes", remove_planes), ("keep_cluster", keep_cluster)):
+        if d is not None and not isinstance(d, dict):
+            raise L.SfmiError(f"clean_cloud_dev: {name} must be None or a dict of keyword arguments, got {d!r}")
     B, n = x.shape[:2]
-    if voxel is None:
+    if remove_planes is not None or keep_cluster is not None:
+        _check_k(k, "clean_cloud_dev")
+        if voxel is None:
+            xf, o = x.reshape(B * n, 3).float().contiguous(), np.arange(B + 1, dtype=np.int64) * n
+        else:
+            xf, o, _, _ = voxel_downsample_dev(x, None, voxel, "centroid")
+        cur, co, idx = xf, o, torch.arange(xf.shape[0], device=xf.device)
+        if remove_planes is not None:
+            cur, co, sub = _compact(cur, co, remove_planes_dev(cur, co, **remove_planes)[0])
+            idx = idx[sub]
+        cur, co, sub = _compact(cur, co, statistical_outlier_mask_dev(cur, co, k, std_ratio)[0])
+        idx = idx[sub]
+        if keep_cluster is not None:
+            idx = idx[torch.nonzero(largest_cluster_mask_dev(cur, co, **keep_cluster)[0])[:, 0]]
+        keep = torch.zeros(xf.shape[0], device=xf.device, dtype=torch.uint8)
+        keep[idx] = 1
+        count = _counts(keep, o)
+    elif voxel is None:
         keep, count, _ = statistical_outlier_mask_dev(x, None, k, std_ratio)
         xf, o = x.reshape(B * n, 3).float().contiguous(), np.arange(B + 1, dtype=np.int64) * n
     else:
