@@ -903,6 +903,56 @@ int sfmi_plane_refit_f32(const float* P, const long long* off, const int* triple
  * (compare-and-swap on roots): the result does not depend on the schedule. */
 int sfmi_cluster_f32(const float* P, const long long* off, int B, long long N, long long max_n, float r2, int* root, void* stream);
 
+/* ---- Rigid registration of partial scans: iterative closest point (csrc/register.hip).  Open3D registration_icp,
+ *      point-to-point and point-to-plane.  The reference has no such step: its real-scan datasets (shapeformer/data/imnet_datasets/
+ *      redwood.py, realtest.py) serve one cloud in one frame.
+ * Ragged pairs: src (N,3) f32 with soff (B+1) int64, tgt (M,3) f32 with toff (B+1) int64 [device]; pair b registers set b of src onto
+ * set b of tgt; every set below 2^31 points, B <= 65535.  nrm (M,3) f32: the target normals of the plane metric, used as given: they
+ * must be unit vectors.  max_n / max_m: the largest source / target set (they size grids and the partial buffer only).
+ * Pose: pose (B,12) f64, row-major [R | t] (3x4).  Transform, in f64 with every product and sum rounded on its own, the f32 point
+ * widened first: x' = f32(((r00 x + r01 y) + r02 z) + t0), likewise y', z'.  The pose is always applied to the original source.
+ * Correspondences under a pose: for every transformed source point the nearest target point of its pair by the rule of
+ * sfmi_nn_dist_f32 - d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)) in f32, the lowest index among equal distances, (+inf, -1) for an empty
+ * target: idx (N) int32 and d2 (N) f32 are bit-identical to sfmi_nn_dist_f32 on the transformed cloud.  Inlier iff d2 <= maxd2 (f32).
+ * Residuals in f64, a = the f32 transformed point widened, q = its target point, n = the target normal:
+ *   metric 1 (plane): r = (a - q).n = ((dx nx + dy ny) + dz nz), one row J = [a x n, n];
+ *   metric 0 (point): r = a - q (three rows), J = [-[a]x | I].
+ * sums (B,29) f64 over the inliers: A = sum J^T J (its 21 upper entries, row-major) | sum J^T r (6; g = -sum J^T r) | sum d2 (the
+ * f32 values widened) | count.  Order of every sum: a lane's 4 points ascending, wave_sum_f64, the 4 waves of the workgroup in
+ * order, then the partials of the set's chunks of sfmi_icp_chunk() points in ascending order; chunks start at the set's first point,
+ * so a pair's sums do not depend on the batch around it and two runs give the same bits.  No float atomics.
+ * Step: A xi = g by Cholesky in f64, xi = (w, v); dR = I + a K + c K^2 with K = [w]x, t = |w|, a = sin t / t, c = (1 - cos t) / t^2
+ * (below t = 1e-4: a = 1 - t^2/6 + t^4/120, c = 1/2 - t^2/24 + t^4/720); R <- dR R, t <- dR t + v.
+ * Loop (Open3D's criteria: absolute differences): iteration k = 0 .. max_iter-1 evaluates under pose_k (fitness_k = count / n_source,
+ * rmse_k = sqrt(sum d2 / count), 0 for count 0); if k > 0 and |fitness_k - fitness_{k-1}| < rel_fitness and |rmse_k - rmse_{k-1}| <
+ * rel_rmse the pair ends with status 0 and iterations = k; otherwise it steps.  After the last step one more evaluation (last = 1)
+ * ends the pair with status 1, so fitness and rmse always describe the returned pose.  status (B) int32: 0 converged, 1 max_iter
+ * reached, 2 fewer than 3 (point) / 6 (plane) inliers, 3 the system is not positive definite (a pivot that is not positive and finite,
+ * or <= 1e-12 x the largest diagonal entry), 4 a non-finite coordinate, normal or initial pose in the pair (fitness 0, rmse 0).  With
+ * status 2, 3 or 4 the pose stays where it was.  A pair that has ended (state != 0) is frozen: its workgroups leave at once and none
+ * of its outputs changes again. */
+/* source points per workgroup of the search / per partial of the sums; how many chunks the search cuts the targets into */
+int sfmi_icp_query_block(void);
+int sfmi_icp_chunk(void);
+int sfmi_icp_splits(int B, long long N, long long M);
+/* out (N,3) f32 = the transform above of set b's points by pose b */
+int sfmi_icp_transform_f32(const float* P, const long long* off, const double* pose, int B, long long N, float* out, void* stream);
+/* The state of iteration 0: state (B) int32 0 = running, 1 = ended; status 1 (4 and ended for a non-finite pair); iterations 0;
+ * fitness, rmse (B) f64 0.  bad (B) int32 scratch; block_off (B+1) int64: which query blocks belong to which pair. */
+int sfmi_icp_begin_f32(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
+                       const double* pose, const int* metric, int B, long long N, long long M, long long max_n, long long max_m,
+                       int* bad, long long* block_off, int* state, int* status, int* iterations, double* fitness, double* rmse,
+                       void* stream);
+/* Iteration k of every running pair: correspond, accumulate, and test / step as stated above; nothing is read back.  metric (B) int32
+ * and maxd2 (B) f32 [device]: every pair's metric (0 point, 1 plane) and bound; nrm may be NULL only when no pair is a plane pair.
+ * part_d2 (S N) f32 and part_idx (S N) int32 with S = sfmi_icp_splits(B, N, M) (unused for S = 1); part (B ceil(max_n /
+ * sfmi_icp_chunk()) 29) f64; xi (B,6) f64: the last step taken. */
+int sfmi_icp_iterate_f32(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
+                         const long long* block_off, int B, long long N, long long M, long long max_n, const int* metric,
+                         const float* maxd2, int k, int last, double rel_fitness, double rel_rmse, double* pose, int* state, int* status,
+                         int* iterations, double* fitness, double* rmse, int* idx, float* d2, float* part_d2, int* part_idx, double* part,
+                         double* sums, double* xi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

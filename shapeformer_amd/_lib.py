@@ -249,6 +249,13 @@ PROTOTYPES = {
     "sfmi_plane_score_f32": (i32, [c_ptr] * 3 + [i32, i64, i32, i64, C.c_double] + [c_ptr] * 4),
     "sfmi_plane_refit_f32": (i32, [c_ptr] * 7 + [i32, i64, i32, C.c_double, i32] + [c_ptr] * 4),
     "sfmi_cluster_f32": (i32, [c_ptr, c_ptr, i32, i64, i64, C.c_float, c_ptr, c_ptr]),
+    # iterative closest point (csrc/register.hip)
+    "sfmi_icp_query_block": (i32, []),
+    "sfmi_icp_chunk": (i32, []),
+    "sfmi_icp_splits": (i32, [i32, i64, i64]),
+    "sfmi_icp_transform_f32": (i32, [c_ptr] * 3 + [i32, i64, c_ptr, c_ptr]),
+    "sfmi_icp_begin_f32": (i32, [c_ptr] * 7 + [i32, i64, i64, i64, i64] + [c_ptr] * 8),
+    "sfmi_icp_iterate_f32": (i32, [c_ptr] * 6 + [i32, i64, i64, i64, c_ptr, c_ptr, i32, i32, C.c_double, C.c_double] + [c_ptr] * 14),
 }
 
 

@@ -1,0 +1,468 @@
+// Rigid registration of partial scans: iterative closest point for ragged batches of (source, target) pairs, what Open3D calls
+// registration_icp (point-to-point and point-to-plane).  The reference has no such step: its real-scan datasets
+// (shapeformer/data/imnet_datasets/redwood.py, realtest.py) serve one cloud in one frame.  DESIGN.md §5.18.
+//
+// The pose of a pair is 12 doubles on the device, row-major [R | t]; it is always applied to the ORIGINAL f32 source, so nothing
+// accumulates in f32.  One iteration is three launches (four when the target is split), and nothing is read back:
+// 1. icp_correspond_kernel: the tiled search of pointdist.hip's nn_kernel - 256 lanes x 8 queries in registers, the target through a
+//    256-point float4 LDS tile read as a broadcast, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), a strict `<` over ascending indices - with
+//    the pose applied as the query is loaded.  (idx, d2) are the bits nn_dist gives on the transformed cloud.  When there are too
+//    few query blocks the target is cut into S chunks (grid.y) and icp_merge_kernel merges them in ascending chunk order.
+// 2. icp_accumulate_kernel: grid (source chunks of 1024 points, pairs).  A lane gathers q (and n) of its 4 points, ascending, into
+//    29 f64 accumulators (the 21 upper entries of A = sum J^T J, the 6 of sum J^T r, sum d2, count); wave_sum_f64; the 4 waves in
+//    order; one partial per chunk.  Chunks start at the set's first point: a pair's sums do not depend on the batch around it.
+// 3. icp_update_kernel: one wave per pair.  Lane e adds entry e of the chunk partials in ascending chunk order; lane 0 takes the
+//    statistics, tests convergence, solves A xi = g by Cholesky, and writes the pose and the state.
+// A pair that has ended (state != 0) is frozen: its workgroups leave at once (block-uniform exits, before any barrier) and none of
+// its outputs changes again, so the result does not depend on how often the host looks at the states.
+//
+// Loop discipline: no kernel waits on another workgroup, there are no spins, every loop around a barrier has workgroup-uniform
+// bounds.  No float atomics: every sum has one fixed order.  An index is range-checked before the point it names is read.
+#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+
+// the transform and the residuals are written once, here and in numpy (tests/icp_ref.py): every product and sum rounded on its own
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int IC_THREADS = 256;
+constexpr int IC_R = 8;                          // queries per lane
+constexpr int IC_QB = IC_THREADS * IC_R;         // queries per workgroup
+constexpr int IC_TILE = 256;                     // target points per LDS tile (float4: 4 KiB)
+constexpr int IC_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
+constexpr int IC_MAX_SPLITS = 64;
+constexpr int IC_MIN_CHUNK = 512;                // fewest target points (on average) per split
+constexpr int IA_THREADS = 256;
+constexpr int IA_WAVES = IA_THREADS / 64;
+constexpr int IA_R = 4;                          // points per lane
+constexpr int IA_CHUNK = IA_THREADS * IA_R;      // source points per partial
+constexpr int IC_NS = 29;                        // A (21, upper, row-major) | J^T r (6) | sum d2 | count
+constexpr int IC_SD2 = 27, IC_CNT = 28;
+constexpr int ICP_POINT = 0, ICP_PLANE = 1;
+
+inline long long ic_qblocks(int B, long long N) { return cdiv(N, IC_QB) + B; }
+
+inline int ic_splits(int B, long long N, long long M) {
+  long long s = cdiv(IC_TARGET_BLOCKS, ic_qblocks(B, N));
+  const long long by_m = M / ((long long)B * IC_MIN_CHUNK);
+  if (s > by_m) s = by_m;
+  if (s > IC_MAX_SPLITS) s = IC_MAX_SPLITS;
+  return s < 1 ? 1 : (int)s;
+}
+
+// x' = f32(((r0 x + r1 y) + r2 z) + t) in f64, the f32 point widened first; T: one row of the pose (4 doubles)
+__device__ __forceinline__ float ic_row(const double* __restrict__ T, double x, double y, double z) {
+  return (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+}
+
+__device__ __forceinline__ bool ic_finite3(const float* __restrict__ p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
+
+// ---- start of a call ----------------------------------------------------------------------------------------------------------------
+
+// grid (chunks of 256 x 4 items, pairs): bad[b] |= 1 when a source, target or normal coordinate of the pair is not finite
+__global__ __launch_bounds__(256) void icp_check_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                        const float* __restrict__ nrm, const long long* __restrict__ soff,
+                                                        const long long* __restrict__ toff, const int* __restrict__ metric,
+                                                        int* __restrict__ bad) {
+  const int b = blockIdx.y;
+  const bool plane = metric[b] == ICP_PLANE;
+  const long long s0 = soff[b], n = soff[b + 1] - s0, t0 = toff[b], m = toff[b + 1] - t0;
+  bool x = false;
+  for (int r = 0; r < 4; ++r) {
+    const long long i = ((long long)blockIdx.x * 4 + r) * 256 + threadIdx.x;
+    if (i < n) x |= !ic_finite3(src + 3 * (s0 + i));
+    if (i < m) {
+      x |= !ic_finite3(tgt + 3 * (t0 + i));
+      if (plane) x |= !ic_finite3(nrm + 3 * (t0 + i));
+    }
+  }
+  if (__any(x) && (threadIdx.x & 63) == 0) atomicOr(bad + b, 1);
+}
+
+// one lane per pair: the state of iteration 0, and (lane 0) which query blocks belong to which pair
+__global__ void icp_begin_kernel(const long long* __restrict__ soff, const double* __restrict__ pose, const int* __restrict__ bad,
+                                 int B, long long* __restrict__ block_off, int* __restrict__ state, int* __restrict__ status,
+                                 int* __restrict__ iterations, double* __restrict__ fitness, double* __restrict__ rmse) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b == 0) {
+    long long acc = 0;
+    for (int c = 0; c < B; ++c) {
+      block_off[c] = acc;
+      acc += cdiv(soff[c + 1] - soff[c], IC_QB);
+    }
+    block_off[B] = acc;
+  }
+  if (b >= B) return;
+  bool ok = bad[b] == 0;
+  for (int e = 0; e < 12; ++e) ok = ok && isfinite(pose[12 * b + e]);
+  state[b] = ok ? 0 : 1;
+  status[b] = ok ? 1 : 4;
+  iterations[b] = 0;
+  fitness[b] = 0.0;
+  rmse[b] = 0.0;
+}
+
+// ---- correspondences ----------------------------------------------------------------------------------------------------------------
+
+// grid (query blocks upper bound, S).  S == 1: d_out / i_out are the results; S > 1: partial buffers, chunk s at d_out + s * N.
+__global__ __launch_bounds__(IC_THREADS) void icp_correspond_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                                    const long long* __restrict__ poff,
+                                                                    const long long* __restrict__ qoff,
+                                                                    const long long* __restrict__ block_off,
+                                                                    const double* __restrict__ pose, const int* __restrict__ state, int B,
+                                                                    long long N, float* __restrict__ d_out, int* __restrict__ i_out) {
+  __shared__ float4 tile[IC_TILE];
+  const long long g = blockIdx.x;
+  if (g >= block_off[B]) return;                               // block-uniform: the grid is an upper bound
+  const int b = sfmi_owner(block_off, B, g);
+  if (state[b] != 0) return;                                   // a frozen pair: block-uniform, before any barrier
+  const int tid = threadIdx.x;
+  const long long pend = poff[b + 1];
+  const long long qbase = poff[b] + (g - block_off[b]) * IC_QB;
+  const double* T = pose + 12 * b;
+  float px[IC_R], py[IC_R], pz[IC_R], best[IC_R];
+  int bi[IC_R];
+#pragma unroll
+  for (int r = 0; r < IC_R; ++r) {
+    const long long i = qbase + r * IC_THREADS + tid;
+    const bool ok = i < pend;
+    const double x = ok ? (double)P[3 * i] : 0.0, y = ok ? (double)P[3 * i + 1] : 0.0, z = ok ? (double)P[3 * i + 2] : 0.0;
+    px[r] = ic_row(T, x, y, z);
+    py[r] = ic_row(T + 4, x, y, z);
+    pz[r] = ic_row(T + 8, x, y, z);
+    best[r] = INFINITY;
+    bi[r] = -1;
+  }
+  const long long q0 = qoff[b], q1 = qoff[b + 1];
+  const long long chunk = cdiv(q1 - q0, (long long)gridDim.y);
+  long long j0 = q0 + (long long)blockIdx.y * chunk, j1 = j0 + chunk;
+  if (j1 > q1) j1 = q1;
+  for (long long t0 = j0; t0 < j1; t0 += IC_TILE) {            // workgroup-uniform bounds
+    __syncthreads();                                           // the previous tile is consumed
+    {
+      const long long j = t0 + tid;
+      // padding past the chunk: +inf coordinates give d2 = inf (or NaN), never < best (strict), so they are never selected
+      tile[tid] = j < j1 ? make_float4(Q[3 * j], Q[3 * j + 1], Q[3 * j + 2], 0.f) : make_float4(INFINITY, INFINITY, INFINITY, 0.f);
+    }
+    __syncthreads();
+    const int jb = (int)(t0 - q0);                             // local index of the tile's first point (M_b < 2^31)
+#pragma unroll 4
+    for (int jj = 0; jj < IC_TILE; ++jj) {
+      const float4 q = tile[jj];                               // broadcast ds_read_b128
+#pragma unroll
+      for (int r = 0; r < IC_R; ++r) {
+        const float dx = px[r] - q.x, dy = py[r] - q.y, dz = pz[r] - q.z;
+        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+        const bool lt = d2 < best[r];
+        best[r] = lt ? d2 : best[r];
+        bi[r] = lt ? jb + jj : bi[r];
+      }
+    }
+  }
+  float* dd = d_out + (long long)blockIdx.y * N;
+  int* ii = i_out + (long long)blockIdx.y * N;
+#pragma unroll
+  for (int r = 0; r < IC_R; ++r) {
+    const long long i = qbase + r * IC_THREADS + tid;
+    if (i < pend) {
+      dd[i] = best[r];
+      ii[i] = bi[r];
+    }
+  }
+}
+
+// merge the S partials of every query of a running pair in ascending chunk order (strict `<`: the lower index wins a tie)
+__global__ void icp_merge_kernel(const float* __restrict__ pd, const int* __restrict__ pi, const long long* __restrict__ poff,
+                                 const int* __restrict__ state, int B, int S, long long N, float* __restrict__ d2,
+                                 int* __restrict__ idx) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  if (state[sfmi_owner(poff, B, i)] != 0) return;
+  float best = pd[i];
+  int bi = pi[i];
+  for (int s = 1; s < S; ++s) {
+    const float d = pd[(long long)s * N + i];
+    const int k = pi[(long long)s * N + i];
+    if (d < best) { best = d; bi = k; }
+  }
+  d2[i] = best;
+  idx[i] = bi;
+}
+
+// ---- the normal equations -----------------------------------------------------------------------------------------------------------
+
+// one inlier's terms.  a: the transformed point (f32, widened); q: its target point; n: the target normal (plane metric)
+template <int METRIC>
+__device__ __forceinline__ void ia_add(double (&acc)[IC_NS], double ax, double ay, double az, double qx, double qy, double qz, double nx,
+                                       double ny, double nz) {
+  const double dx = ax - qx, dy = ay - qy, dz = az - qz;
+  if (METRIC == ICP_PLANE) {
+    // r = (a - q).n, J = [a x n, n]
+    const double r = (dx * nx + dy * ny) + dz * nz;
+    const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) acc[e++] += J[i] * J[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += J[i] * r;
+  } else {
+    // r = a - q (three rows), J = [-[a]x | I]: J^T J = [[|a|^2 I - a a^T, [a]x], [., I]], J^T r = [a x r, r]
+    acc[0] += ay * ay + az * az;  acc[1] += -(ax * ay);         acc[2] += -(ax * az);
+    acc[6] += ax * ax + az * az;  acc[7] += -(ay * az);         acc[11] += ax * ax + ay * ay;
+    acc[4] += -az;  acc[5] += ay;                               // row 0, columns 4 and 5 of [a]x
+    acc[8] += az;   acc[10] += -ax;                             // row 1, columns 3 and 5
+    acc[12] += -ay; acc[13] += ax;                              // row 2, columns 3 and 4
+    acc[15] += 1.0; acc[18] += 1.0; acc[20] += 1.0;             // the identity block's diagonal
+    acc[21] += ay * dz - az * dy;
+    acc[22] += az * dx - ax * dz;
+    acc[23] += ax * dy - ay * dx;
+    acc[24] += dx; acc[25] += dy; acc[26] += dz;
+  }
+}
+
+// grid (source chunks, pairs): part[(b * gridDim.x + chunk) * 29 + e].  metric[b] and maxd2[b] are the pair's: workgroup-uniform
+__global__ __launch_bounds__(IA_THREADS) void icp_accumulate_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                                    const float* __restrict__ Nrm, const long long* __restrict__ poff,
+                                                                    const long long* __restrict__ qoff, const double* __restrict__ pose,
+                                                                    const int* __restrict__ state, const int* __restrict__ idx,
+                                                                    const float* __restrict__ d2, const int* __restrict__ metric,
+                                                                    const float* __restrict__ maxd2v, double* __restrict__ part) {
+  __shared__ double red[IA_WAVES][IC_NS];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  if (state[b] != 0) return;                                   // a frozen pair: block-uniform, before any barrier
+  const long long p0 = poff[b], n = poff[b + 1] - p0;
+  if ((long long)blockIdx.x * IA_CHUNK >= n) return;           // block-uniform
+  const long long q0 = qoff[b], m = qoff[b + 1] - q0;
+  const double* T = pose + 12 * b;
+  const bool plane = metric[b] == ICP_PLANE;
+  const float maxd2 = maxd2v[b];
+  double acc[IC_NS];
+#pragma unroll
+  for (int e = 0; e < IC_NS; ++e) acc[e] = 0.0;
+#pragma unroll
+  for (int r = 0; r < IA_R; ++r) {                             // a lane's points in ascending order
+    const long long i = (long long)blockIdx.x * IA_CHUNK + r * IA_THREADS + tid;
+    if (i < n) {
+      const int j = idx[p0 + i];
+      const float d = d2[p0 + i];
+      if (j >= 0 && j < m && d <= maxd2) {                     // the index is checked before the point is read
+        const double x = (double)P[3 * (p0 + i)], y = (double)P[3 * (p0 + i) + 1], z = (double)P[3 * (p0 + i) + 2];
+        const double ax = (double)ic_row(T, x, y, z), ay = (double)ic_row(T + 4, x, y, z), az = (double)ic_row(T + 8, x, y, z);
+        const float* q = Q + 3 * (q0 + j);
+        if (plane) {
+          const float* nn = Nrm + 3 * (q0 + j);
+          ia_add<ICP_PLANE>(acc, ax, ay, az, (double)q[0], (double)q[1], (double)q[2], (double)nn[0], (double)nn[1], (double)nn[2]);
+        } else {
+          ia_add<ICP_POINT>(acc, ax, ay, az, (double)q[0], (double)q[1], (double)q[2], 0.0, 0.0, 0.0);
+        }
+        acc[IC_SD2] += (double)d;
+        acc[IC_CNT] += 1.0;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < IC_NS; ++e) {
+    const double v = wave_sum_f64(acc[e]);
+    if ((tid & 63) == 0) red[tid >> 6][e] = v;
+  }
+  __syncthreads();
+  if (tid < IC_NS) {
+    double s = red[0][tid];
+#pragma unroll
+    for (int w = 1; w < IA_WAVES; ++w) s += red[w][tid];       // the waves in order
+    part[((long long)b * gridDim.x + blockIdx.x) * IC_NS + tid] = s;
+  }
+}
+
+// ---- the step -----------------------------------------------------------------------------------------------------------------------
+
+// A (6x6, full, symmetric) x = g by Cholesky in f64; false for a pivot that is not positive and finite or is <= 1e-12 x the largest
+// diagonal entry
+__device__ bool ic_cholesky6(double (&A)[6][6], const double (&g)[6], double (&x)[6]) {
+  double big = 0.0;
+  for (int i = 0; i < 6; ++i) big = fmax(big, A[i][i]);
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+    for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
+    if (!(d > 0.0) || !isfinite(d) || d <= 1e-12 * big) return false;
+    const double l = sqrt(d);
+    A[j][j] = l;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+      for (int k = 0; k < j; ++k) s -= A[i][k] * A[j][k];
+      A[i][j] = s / l;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {
+    double s = g[i];
+    for (int k = 0; k < i; ++k) s -= A[i][k] * y[k];
+    y[i] = s / A[i][i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+    for (int k = i + 1; k < 6; ++k) s -= A[k][i] * x[k];
+    x[i] = s / A[i][i];
+  }
+  return true;
+}
+
+// one wave per pair.  k: the iteration; last: this is the evaluation after the last step
+__global__ __launch_bounds__(64) void icp_update_kernel(const long long* __restrict__ poff, const double* __restrict__ part, int chunks,
+                                                        const int* __restrict__ metricv, int k, int last, double rel_fitness, double rel_rmse,
+                                                        double* __restrict__ pose, int* __restrict__ state, int* __restrict__ status,
+                                                        int* __restrict__ iterations, double* __restrict__ fitness,
+                                                        double* __restrict__ rmse, double* __restrict__ sums, double* __restrict__ xi) {
+  __shared__ double s[IC_NS];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (state[b] != 0) return;                                   // frozen: the whole wave leaves
+  const long long n = poff[b + 1] - poff[b];
+  const int metric = metricv[b];
+  const int nc = (int)cdiv(n, IA_CHUNK);                       // <= chunks
+  if (lane < IC_NS) {
+    double v = 0.0;
+    for (int c = 0; c < nc && c < chunks; ++c) v += part[((long long)b * chunks + c) * IC_NS + lane];   // ascending chunk order
+    s[lane] = v;
+    sums[(long long)b * IC_NS + lane] = v;
+  }
+  __syncthreads();
+  if (lane != 0) return;
+  const double count = s[IC_CNT];
+  const double fit = n > 0 ? count / (double)n : 0.0;
+  const double rm = count > 0.0 ? sqrt(s[IC_SD2] / count) : 0.0;
+  const double pfit = fitness[b], prm = rmse[b];
+  fitness[b] = fit;
+  rmse[b] = rm;
+  iterations[b] = k;
+  int end = -1;
+  if (last) end = 1;
+  else if (k > 0 && fabs(fit - pfit) < rel_fitness && fabs(rm - prm) < rel_rmse) end = 0;
+  else if (count < (metric == ICP_PLANE ? 6.0 : 3.0)) end = 2;
+  double w[6];
+  if (end < 0) {
+    double A[6][6], g[6];
+    int e = 0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j) {
+        A[i][j] = s[e];
+        A[j][i] = s[e];
+        ++e;
+      }
+    for (int i = 0; i < 6; ++i) g[i] = -s[21 + i];
+    if (!ic_cholesky6(A, g, w)) end = 3;
+  }
+  if (end >= 0) {
+    status[b] = end;
+    state[b] = 1;
+    return;
+  }
+  // dR = Rodrigues(w) = I + a K + c K^2, K = [w]x, a = sin t / t, c = (1 - cos t) / t^2; the series below t = 1e-4
+  const double wx = w[0], wy = w[1], wz = w[2];
+  const double t2 = (wx * wx + wy * wy) + wz * wz, t = sqrt(t2);
+  double a, c;
+  if (t < 1e-4) {
+    a = 1.0 - t2 / 6.0 + t2 * t2 / 120.0;
+    c = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
+  } else {
+    a = sin(t) / t;
+    c = (1.0 - cos(t)) / t2;
+  }
+  double dR[3][3];
+  dR[0][0] = 1.0 - c * (wy * wy + wz * wz); dR[0][1] = c * (wx * wy) - a * wz;        dR[0][2] = c * (wx * wz) + a * wy;
+  dR[1][0] = c * (wx * wy) + a * wz;        dR[1][1] = 1.0 - c * (wx * wx + wz * wz); dR[1][2] = c * (wy * wz) - a * wx;
+  dR[2][0] = c * (wx * wz) - a * wy;        dR[2][1] = c * (wy * wz) + a * wx;        dR[2][2] = 1.0 - c * (wx * wx + wy * wy);
+  double* T = pose + 12 * b;
+  double old[12], nw[12];
+  for (int e = 0; e < 12; ++e) old[e] = T[e];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 4; ++j) nw[4 * i + j] = (dR[i][0] * old[j] + dR[i][1] * old[4 + j]) + dR[i][2] * old[8 + j];
+    nw[4 * i + 3] += w[3 + i];
+  }
+  for (int e = 0; e < 12; ++e) T[e] = nw[e];
+  for (int e = 0; e < 6; ++e) xi[6 * b + e] = w[e];
+}
+
+// ---- the public transform -----------------------------------------------------------------------------------------------------------
+
+__global__ void icp_transform_kernel(const float* __restrict__ P, const long long* __restrict__ off, const double* __restrict__ pose,
+                                     int B, long long N, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const double* T = pose + 12 * sfmi_owner(off, B, i);
+  const double x = (double)P[3 * i], y = (double)P[3 * i + 1], z = (double)P[3 * i + 2];
+  out[3 * i] = ic_row(T, x, y, z);
+  out[3 * i + 1] = ic_row(T + 4, x, y, z);
+  out[3 * i + 2] = ic_row(T + 8, x, y, z);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfmi_icp_query_block(void) { return IC_QB; }
+int sfmi_icp_chunk(void) { return IA_CHUNK; }
+int sfmi_icp_splits(int B, long long N, long long M) { return (B <= 0 || N < 0 || M < 0) ? 0 : ic_splits(B, N, M); }
+
+int sfmi_icp_transform_f32(const float* P, const long long* off, const double* pose, int B, long long N, float* out, void* stream) {
+  if (B <= 0 || N < 0 || !off || !pose) return SFMI_EINVAL;
+  if (N == 0) return SFMI_OK;
+  if (!P || !out) return SFMI_EINVAL;
+  hipLaunchKernelGGL(icp_transform_kernel, dim3(blocks256(N)), dim3(256), 0, (hipStream_t)stream, P, off, pose, B, N, out);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+
+int sfmi_icp_begin_f32(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
+                       const double* pose, const int* metric, int B, long long N, long long M, long long max_n, long long max_m,
+                       int* bad, long long* block_off, int* state, int* status, int* iterations, double* fitness, double* rmse, void* stream) {
+  if (B <= 0 || B > 65535 || N < 0 || M < 0 || max_n < 0 || max_m < 0 || max_n >= (1ll << 31) || max_m >= (1ll << 31) || !soff || !toff ||
+      !pose || !metric || !bad || !block_off || !state || !status || !iterations || !fitness || !rmse || (N > 0 && !src) || (M > 0 && !tgt))
+    return SFMI_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st) != hipSuccess) return SFMI_ELAUNCH;
+  const long long most = max_n > max_m ? max_n : max_m;
+  if (most > 0)
+    hipLaunchKernelGGL(icp_check_kernel, dim3((unsigned)cdiv(most, 1024), (unsigned)B), dim3(256), 0, st, src, tgt, nrm, soff, toff, metric, bad);
+  hipLaunchKernelGGL(icp_begin_kernel, dim3(blocks256(B)), dim3(256), 0, st, soff, pose, (const int*)bad, B, block_off, state, status,
+                     iterations, fitness, rmse);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+
+int sfmi_icp_iterate_f32(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
+                         const long long* block_off, int B, long long N, long long M, long long max_n, const int* metric, const float* maxd2, int k,
+                         int last, double rel_fitness, double rel_rmse, double* pose, int* state, int* status, int* iterations,
+                         double* fitness, double* rmse, int* idx, float* d2, float* part_d2, int* part_idx, double* part, double* sums,
+                         double* xi, void* stream) {
+  if (B <= 0 || B > 65535 || N < 0 || M < 0 || M >= (1ll << 31) || max_n < 0 || max_n >= (1ll << 31) ||
+      !metric || !maxd2 || k < 0 || !soff || !toff || !block_off || !pose || !state || !status || !iterations ||
+      !fitness || !rmse || !part || !sums || !xi || (N > 0 && (!src || !idx || !d2)) || (M > 0 && !tgt))
+    return SFMI_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int S = ic_splits(B, N, M);
+  if (N > 0 && S > 1 && (!part_d2 || !part_idx)) return SFMI_EINVAL;
+  const int chunks = (int)(max_n > 0 ? cdiv(max_n, IA_CHUNK) : 1);
+  if (N > 0) {
+    const dim3 grid((unsigned)ic_qblocks(B, N), (unsigned)S);
+    if (S == 1) {
+      hipLaunchKernelGGL(icp_correspond_kernel, grid, dim3(IC_THREADS), 0, st, src, tgt, soff, toff, block_off, (const double*)pose,
+                         (const int*)state, B, N, d2, idx);
+    } else {
+      hipLaunchKernelGGL(icp_correspond_kernel, grid, dim3(IC_THREADS), 0, st, src, tgt, soff, toff, block_off, (const double*)pose,
+                         (const int*)state, B, N, part_d2, part_idx);
+      hipLaunchKernelGGL(icp_merge_kernel, dim3(blocks256(N)), dim3(256), 0, st, (const float*)part_d2, (const int*)part_idx, soff,
+                         (const int*)state, B, S, N, d2, idx);
+    }
+    const dim3 agrid((unsigned)chunks, (unsigned)B);
+    hipLaunchKernelGGL(icp_accumulate_kernel, agrid, dim3(IA_THREADS), 0, st, src, tgt, nrm, soff, toff, (const double*)pose,
+                       (const int*)state, (const int*)idx, (const float*)d2, metric, maxd2, part);
+  }
+  hipLaunchKernelGGL(icp_update_kernel, dim3((unsigned)B), dim3(64), 0, st, soff, (const double*)part, chunks, metric, k, last, rel_fitness,
+                     rel_rmse, pose, state, status, iterations, fitness, rmse, sums, xi);
+  SFMI_CHECK_LAUNCH();
+  return SFMI_OK;
+}
+
+}  // extern "C"
