@@ -953,6 +953,74 @@ int sfmi_icp_iterate_f32(const float* src, const float* tgt, const float* nrm, c
                          int* iterations, double* fitness, double* rmse, int* idx, float* d2, float* part_d2, int* part_idx, double* part,
                          double* sums, double* xi, void* stream);
 
+/* ---- Global registration of partial scans: FPFH features and RANSAC over correspondences (csrc/features.hip, csrc/global_register.hip;
+ *      DESIGN.md 5.19).  The interface of Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching, not their
+ *      bits: the statement below is the specification, restated in numpy in tests/global_reg_ref.py.  The reference has no such step.
+ * Ragged sets as in sfmi_knn_f32: P (N,3) f32 points and Nrm (N,3) f32 normals with off (B+1) int64 [device]; idx (N,k) int32 and d2
+ * (N,k) f32 are the rows of sfmi_knn_f32(P, P, k, exclude_self = 1), k <= 64: duplicates of a point remain its neighbours.  With
+ * use_radius a neighbour is kept iff d2 <= r2 in f32 (the hybrid search); an entry with idx = -1 (or outside the set) is skipped.
+ * Pair feature of (p1, n1) against a kept neighbour (p2, n2), the f32 inputs widened to f64, every product and sum rounded on its own,
+ * dot products as (x + y) + z:
+ *   dp = p2 - p1, d = sqrt((dpx^2 + dpy^2) + dpz^2); the pair is skipped unless d > 0;
+ *   a1 = n1.dp / d, a2 = n2.dp / d; if |a1| < |a2| (strict): na = n2, nb = n1, dp = -dp, f2 = -a2; else na = n1, nb = n2, f2 = a1;
+ *   v = dp x na, vn = |v|; the pair is skipped unless vn > 0; v = v / vn, w = na x v, f1 = v.nb, f0 = atan2(w.nb, na.nb);
+ *   b0 = clamp(floor((11 (f0 + pi)) / (2 pi)), 0, 10), b1 = clamp(floor((11 (f1 + 1)) 0.5), 0, 10), b2 likewise from f2.
+ * Everything but atan2 is correctly rounded IEEE arithmetic.  spfh (N,33) int32: the counted pairs of every point per bin (b0 | 11 + b1
+ * | 22 + b2); m (N) int32: the counted pairs. */
+int sfmi_fpfh_spfh_f32(const float* P, const float* Nrm, const long long* off, const int* idx, const float* d2, int B, long long N, int k,
+                       int use_radius, float r2, int* spfh, int* m, void* stream);
+/* The second stage, in f64: s_i[j] = spfh_i[j] (100 / m_i), 0 for m_i = 0; F_i[j] = the sum over the kept neighbours in column order
+ * with d2 > 0 of s_nb[j] / d2 (the f32 value widened); per group g of 11 bins t_g = the sum of F_i[j], j ascending, and F_i[j] *= 100 /
+ * t_g if t_g != 0; out (N,33) f32 = f32(F_i[j] + s_i[j]). */
+int sfmi_fpfh_features_f32(const long long* off, const int* idx, const float* d2, const int* spfh, const int* m, int B, long long N, int k,
+                           int use_radius, float r2, float* out, void* stream);
+/* Normals turned away from each set's centroid, in place: c = the mean of the set's finite points, summed in f64 in a fixed order (a
+ * lane's points ascending, wave_sum_f64, a fixed tree over the waves), and n <- -n where ((px - cx) nx + (py - cy) ny) + (pz - cz) nz <
+ * 0 in f64.  One workgroup per set: a set's result depends on that set alone, a non-finite point turns nothing.  B <= 65535. */
+int sfmi_fpfh_orient_f32(const float* P, const long long* off, int B, long long N, float* Nrm, void* stream);
+/* Nearest neighbours in feature space: for every row of A (N,33) f32 (sets aoff) the nearest row of its pair's set of Bf (M,33) f32
+ * (sets boff): acc = d_0 d_0 in f32, then acc = fmaf(d_j, d_j, acc), j = 1..32, d_j = a_j - b_j in f32; a strict `<` in ascending
+ * index, so the lowest index wins among equal distances; a NaN distance is +inf; idx (N) int32 local, d2 (N) f32, (-1, +inf) without a
+ * candidate.  q: queries per lane, 2 or 4 (0: the default); a workgroup serves sfmi_fpfh_query_block(q) queries of one pair;
+ * block_off (B+1) int64 [device]: the exclusive prefix sums of ceil(n_b / query block), n_blocks = block_off[B].  splits: into how
+ * many chunks every target set is cut (0: sfmi_fpfh_nn_splits(B, N, M, q), at most 64); the chunks are merged in ascending order with
+ * a strict `<`, so the result does not depend on it.  part_d2 (S N) f32 / part_idx (S N) int32: unused for S = 1. */
+int sfmi_fpfh_query_block(int q);
+int sfmi_fpfh_tile(void);
+int sfmi_fpfh_nn_splits(int B, long long N, long long M, int q);
+int sfmi_fpfh_nn_f32(const float* A, const float* Bf, const long long* aoff, const long long* boff, const long long* block_off, int B,
+                     long long N, long long M, long long n_blocks, int splits, int q, int* idx, float* d2, float* part_d2, int* part_idx,
+                     void* stream);
+/* RANSAC over correspondences.  Pairs as in sfmi_icp_*: src / soff, tgt / toff; corr (C,2) int32 (source index, target index) local to
+ * the pair's sets, with coff (B+1) int64 [device]; triples (B,H,3) int32: a hypothesis is three correspondence indices local to the
+ * pair.  A hypothesis is invalid when an index repeats or lies outside the pair's correspondences (or a correspondence outside its
+ * sets); a coordinate is not finite; two of its source points or two of its target points coincide; an edge fails ls >= sim lt and lt
+ * >= sim ls (the edge lengths of the source and target triangles in f64); the second singular value of the centred source triangle, or
+ * of the cross-covariance, is <= 1e-12 x the first.  Otherwise its pose is the least-squares rigid motion of the three pairs (Kabsch,
+ * proper rotation) in f64: M = sum q' s'^T = U S V^T by one-sided Jacobi, u3 = u1 x u2, v3 = v1 x v2, R = sum u_i v_i^T, t = cq - R cs.
+ * poses (B,H,12) f64 row-major [R | t] (NaN for an invalid one); valid (B,H) int32.  C: the number of correspondences of the batch; src,
+ * tgt and corr (and, in the refit, inlier) may be NULL only when it is 0. */
+int sfmi_greg_poses_f32(const float* src, const float* tgt, const long long* soff, const long long* toff, const int* corr,
+                        const long long* coff, const int* triples, int B, int H, long long C, double similarity, double* poses,
+                        int* valid, void* stream);
+/* count (B,H) int32 = the correspondences c with d2(T_h s_c, t_c) <= maxd2: the transform of sfmi_icp_transform_f32, d2 =
+ * fmaf(dz, dz, fmaf(dy, dy, dx dx)) in f32; -1 for an invalid hypothesis (valid (B,H) int32, NULL: all valid) and for every hypothesis
+ * of a pair with bad[b] != 0 (bad (B) int32 or NULL).  best (B) int32: the valid hypothesis of largest count, the lowest h among
+ * equals, -1 without one.  status (B) int32: 0 ok, 1 no valid hypothesis, 4 bad[b] != 0.  max_c: the largest correspondence set (it
+ * sizes the grid only).  Integer atomics only: a function of the input. */
+int sfmi_greg_score_f32(const float* src, const float* tgt, const long long* soff, const long long* toff, const int* corr,
+                        const long long* coff, const double* poses, const int* valid, const int* bad, int B, int H, long long max_c,
+                        float maxd2, int* count, int* best, int* status, void* stream);
+/* The refit over the winner's inliers: count, the sums of the source and target points, and the 9 cross terms (q_r - cq_r)(s_c - cs_c)
+ * about the centroids in a second pass, all f64 in a fixed order (a lane's correspondences ascending, wave_sum_f64, a fixed tree over
+ * the waves): sums (B,16) f64 = count | sum s | sum q | M row-major.  Kabsch as above -> pose (B,12) f64; inlier (C) uint8 and n_in (B)
+ * int32 under the new pose.  refit == 0: the winner's own pose and inliers.  status (B) int32 [in / out]: a pair with status 0 whose
+ * winner has fewer than 3 inliers, or whose refit is degenerate, gets 2; a pair with status != 0 keeps it; in both cases the pose is
+ * the identity, the mask 0 and n_in 0. */
+int sfmi_greg_refit_f32(const float* src, const float* tgt, const long long* soff, const long long* toff, const int* corr,
+                        const long long* coff, const double* poses, const int* best, int B, int H, long long C, float maxd2, int refit,
+                        int* status, double* pose, unsigned char* inlier, int* n_in, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

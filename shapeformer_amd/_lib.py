@@ -256,6 +256,17 @@ PROTOTYPES = {
     "sfmi_icp_transform_f32": (i32, [c_ptr] * 3 + [i32, i64, c_ptr, c_ptr]),
     "sfmi_icp_begin_f32": (i32, [c_ptr] * 7 + [i32, i64, i64, i64, i64] + [c_ptr] * 8),
     "sfmi_icp_iterate_f32": (i32, [c_ptr] * 6 + [i32, i64, i64, i64, c_ptr, c_ptr, i32, i32, C.c_double, C.c_double] + [c_ptr] * 14),
+    # FPFH features and their nearest neighbours (csrc/features.hip), RANSAC over correspondences (csrc/global_register.hip)
+    "sfmi_fpfh_spfh_f32": (i32, [c_ptr] * 5 + [i32, i64, i32, i32, C.c_float] + [c_ptr] * 3),
+    "sfmi_fpfh_features_f32": (i32, [c_ptr] * 5 + [i32, i64, i32, i32, C.c_float] + [c_ptr] * 2),
+    "sfmi_fpfh_orient_f32": (i32, [c_ptr, c_ptr, i32, i64, c_ptr, c_ptr]),
+    "sfmi_fpfh_query_block": (i32, [i32]),
+    "sfmi_fpfh_tile": (i32, []),
+    "sfmi_fpfh_nn_splits": (i32, [i32, i64, i64, i32]),
+    "sfmi_fpfh_nn_f32": (i32, [c_ptr] * 5 + [i32, i64, i64, i64, i32, i32] + [c_ptr] * 5),
+    "sfmi_greg_poses_f32": (i32, [c_ptr] * 7 + [i32, i32, i64, C.c_double] + [c_ptr] * 3),
+    "sfmi_greg_score_f32": (i32, [c_ptr] * 9 + [i32, i32, i64, C.c_float] + [c_ptr] * 4),
+    "sfmi_greg_refit_f32": (i32, [c_ptr] * 8 + [i32, i32, i64, C.c_float, i32] + [c_ptr] * 6),
 }
 
 

@@ -18,7 +18,23 @@ for bit; a pair that has ended is frozen on the device, so the result does not d
 states every check_every iterations to stop early.  Everything is refused with SfmiError on the host before a launch; there is no CPU
 fallback.
 
-status: 0 converged, 1 max_iter reached, 2 fewer than 3 (point) / 6 (plane) inliers, 3 the normal equations are not positive definite,
+Global registration (csrc/features.hip, csrc/global_register.hip) gives ICP its start when the scans are not roughly
+aligned beforehand - Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching for ragged batches:
+
+  fpfh_dev(points, normals, off, k, radius)                        -> feature (N,33) f32, spfh (N,33) int32, m (N,) int32
+  fpfh_from_spfh_dev(points, off, k, radius, spfh, m)              -> the second stage alone
+  match_features_dev(fs, ft, s_off, t_off, mutual)                 -> corr (C,2) int32, c_off (B+1,) host, idx (N,), d2 (N,)
+  correspondence_hypotheses(sizes, H, seed)                        -> (B,H,3) int32 draws on the host (scan.plane_hypotheses)
+  hypothesis_poses_dev(..., corr, c_off, triples, similarity)      -> poses (B,H,12) f64, valid (B,H) int32
+  score_poses_dev(..., corr, c_off, max_dist, poses)               -> count (B,H) int32
+  ransac_correspondences_dev(..., corr, c_off, max_dist, ...)      -> pose (B,4,4) f64, fitness, inlier (C,), n_in, count (B,H), best, status
+  global_registration_dev(source, target, ..., voxel, max_dist)    -> the same, from the clouds alone
+  merge_scans_dev(..., global_init={...})                          -> the global pose is the init of the ICP that follows
+
+Its contract is stated in include/sfmi.h and restated in numpy in tests/global_reg_ref.py; its status: 0 ok, 1 no valid hypothesis,
+2 fewer than 3 inliers or a degenerate refit, 4 a non-finite value in the pair; with 1, 2, 4 the pose is the identity.
+
+ICP's status: 0 converged, 1 max_iter reached, 2 fewer than 3 (point) / 6 (plane) inliers, 3 the normal equations are not positive definite,
 4 a non-finite coordinate, normal or initial pose in the pair.  With 2, 3 and 4 the pose stays where it was.
 """
 from __future__ import annotations
@@ -27,7 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import host_offsets, on_device, point_sets, points_arg
+from ._ragged import excl_at, host_offsets, on_device, point_sets, points_arg
 
 METRICS = ("point", "plane")
 N_SUMS = 29
@@ -259,16 +275,406 @@ def icp_multiscale_dev(source, target, s_off=None, t_off=None, voxels=(0.04, 0.0
     return out
 
 
-def merge_scans_dev(clouds, offs=None, voxel=None, **icp):
+# ---- global registration: FPFH features and RANSAC over correspondences (csrc/features.hip, csrc/global_register.hip)
+
+FPFH_BINS = 33
+GREG_SUMS = 16
+
+
+def _radius_arg(radius, what, name="radius"):
+    """None, or a finite number > 0 -> (use_radius, f32(radius^2)) rounded as radius_outlier_mask_dev rounds its radius"""
+    if radius is None:
+        return 0, 0.0
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not 0 < float(radius) < float("inf"):
+        raise L.SfmiError(f"{what}: {name} must be None or a finite number > 0, got {radius!r}")
+    return 1, float(np.float32(float(radius) ** 2))
+
+
+def _normals_arg(normals, x, what):
+    if not isinstance(normals, torch.Tensor) or normals.shape[-1:] != (3,) or normals.reshape(-1, 3).shape != x.shape:
+        raise L.SfmiError(f"{what}: normals must be a tensor with one (3,) normal per point")
+    return normals.reshape(-1, 3)
+
+
+def _fpfh_stage2(o, idx, d2, spfh, m, k, use, r2, dev):
+    B, N = len(o) - 1, idx.shape[0]
+    out = torch.empty(N, FPFH_BINS, device=dev, dtype=torch.float32)
+    if N:
+        od = torch.from_numpy(o).to(dev)
+        L.check(L.lib().sfmi_fpfh_features_f32(L.ptr(od), L.ptr(idx), L.ptr(d2), L.ptr(spfh), L.ptr(m), B, N, k, use, r2, L.ptr(out),
+                                               L.stream_ptr()), "sfmi_fpfh_features_f32")
+    return out
+
+
+def _fpfh_from_knn(xf, nf, o, idx, d2, k, use, r2):
+    """both stages on given neighbour rows: xf / nf (N,3) f32 contiguous, idx / d2 (N,k) -> feature, spfh, m"""
+    dev = xf.device
+    B, N = len(o) - 1, xf.shape[0]
+    spfh = torch.empty(N, FPFH_BINS, device=dev, dtype=torch.int32)
+    m = torch.empty(N, device=dev, dtype=torch.int32)
+    if N:
+        od = torch.from_numpy(o).to(dev)
+        L.check(L.lib().sfmi_fpfh_spfh_f32(L.ptr(xf), L.ptr(nf), L.ptr(od), L.ptr(idx), L.ptr(d2), B, N, k, use, r2, L.ptr(spfh), L.ptr(m),
+                                           L.stream_ptr()), "sfmi_fpfh_spfh_f32")
+    return _fpfh_stage2(o, idx, d2, spfh, m, k, use, r2, dev), spfh, m
+
+
+def fpfh_dev(points, normals, off=None, k=32, radius=None):
+    """Fast point feature histograms (Open3D's compute_fpfh_feature): 3 x 11 bins per point.
+
+    points (N,3) f32 HIP tensor with (B+1,) offsets (None: one set) or a (B,M,3) batch; normals of the same shape, used as given.  The
+    neighbourhood is scan.knn_dev(points, points, k, exclude_self=True), k <= 64; with `radius` a neighbour farther than it is dropped
+    (d2 <= f32(radius^2) in f32: the hybrid search).  -> feature (N,33) f32, spfh (N,33) int32 the simplified histograms' counts, m (N,)
+    int32 the counted pairs of every point ((B,M,..) for a batch).  The pair feature, the bins and the weighting are include/sfmi.h's;
+    the counts are exact up to the bits of atan2 at a bin edge, bit-identical from run to run and independent of the batch."""
+    from .scan import _check_k, _launch_knn
+    what = "fpfh_dev"
+    k = _check_k(k, what)
+    use, r2 = _radius_arg(radius, what)
+    x, o, shape = point_sets(points, off, what)
+    n = _normals_arg(normals, x, what)
+    dev = on_device(what, x, n)
+    xf, nf = x.float().contiguous(), n.float().contiguous()
+    d2, idx = _launch_knn(xf, xf, o, o, k, True)
+    feat, spfh, m = _fpfh_from_knn(xf, nf, o, idx, d2, k, use, r2)
+    return (feat.reshape(*shape, FPFH_BINS), spfh.reshape(*shape, FPFH_BINS), m.reshape(shape)) if shape else (feat, spfh, m)
+
+
+def fpfh_from_spfh_dev(points, off=None, k=32, radius=None, spfh=None, m=None):
+    """The second stage of fpfh_dev alone, on given counts: spfh (N,33) int32 and m (N,) int32 -> feature (N,33) f32."""
+    from .scan import _check_k, _launch_knn
+    what = "fpfh_from_spfh_dev"
+    k = _check_k(k, what)
+    use, r2 = _radius_arg(radius, what)
+    x, o, shape = point_sets(points, off, what)
+    N = x.shape[0]
+    if not isinstance(spfh, torch.Tensor) or not isinstance(m, torch.Tensor) or spfh.numel() != N * FPFH_BINS or m.numel() != N:
+        raise L.SfmiError(f"{what}: spfh must be (N,{FPFH_BINS}) and m (N,) integer tensors for the {N} points")
+    dev = on_device(what, x, spfh, m)
+    xf = x.float().contiguous()
+    d2, idx = _launch_knn(xf, xf, o, o, k, True)
+    feat = _fpfh_stage2(o, idx, d2, spfh.reshape(N, FPFH_BINS).to(torch.int32).contiguous(), m.reshape(N).to(torch.int32).contiguous(), k,
+                        use, r2, dev)
+    return feat.reshape(*shape, FPFH_BINS) if shape else feat
+
+
+def _features_arg(f, what, name):
+    if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[1] != FPFH_BINS or not f.dtype.is_floating_point:
+        raise L.SfmiError(f"{what}: {name} must be an (N,{FPFH_BINS}) float tensor on the HIP device (no CPU fallback)")
+    return f
+
+
+def _feature_nn(fa, fb, ao, bo, splits, q):
+    """rows of fa against their pair's set of fb -> idx (N,) int32 local, d2 (N,) f32"""
+    dev, lib = fa.device, L.lib()
+    B, N, M = len(ao) - 1, fa.shape[0], fb.shape[0]
+    idx = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    d2 = torch.full((N,), float("inf"), device=dev, dtype=torch.float32)
+    if N == 0:
+        return idx, d2
+    qb = int(lib.sfmi_fpfh_query_block(q))
+    block_off = np.concatenate([[0], np.cumsum(-(-np.diff(ao) // qb))]).astype(np.int64)
+    S = splits if splits else int(lib.sfmi_fpfh_nn_splits(B, N, M, q))
+    pd = torch.empty(S * N, device=dev, dtype=torch.float32) if S > 1 else None
+    pi = torch.empty(S * N, device=dev, dtype=torch.int32) if S > 1 else None
+    aod, bod, kod = (torch.from_numpy(v).to(dev) for v in (ao, bo, block_off))
+    L.check(lib.sfmi_fpfh_nn_f32(L.ptr(fa), L.ptr(fb), L.ptr(aod), L.ptr(bod), L.ptr(kod), B, N, M, int(block_off[-1]), S, q, L.ptr(idx),
+                                 L.ptr(d2), L.ptr(pd), L.ptr(pi), L.stream_ptr()), "sfmi_fpfh_nn_f32")
+    return idx, d2
+
+
+def match_features_dev(fs, ft, s_off=None, t_off=None, mutual=True, splits=None, queries_per_lane=None):
+    """Correspondences by nearest neighbours in feature space, pair by pair: for every source feature the nearest target feature of its
+    pair (f32 fmaf distances over the 33 bins, the lowest index among equal distances; include/sfmi.h); with `mutual` it is kept only
+    if the target feature's nearest source feature is that source feature again.
+    fs (N,33) / ft (M,33) f32 HIP tensors with (B+1,) offsets.  -> corr (C,2) int32 (source index, target index) local to the sets, in
+    source order (compacted by prefix counts); c_off (B+1,) host int64 (the counts are read back: one synchronisation); idx (N,) int32
+    and d2 (N,) f32 of the source -> target search.  splits / queries_per_lane: how the library cuts the work (None: its own choice);
+    the result does not depend on them."""
+    what = "match_features_dev"
+    fs, ft = _features_arg(fs, what, "fs"), _features_arg(ft, what, "ft")
+    so, to = host_offsets(s_off, fs.shape[0], f"{what} s_off"), host_offsets(t_off, ft.shape[0], f"{what} t_off")
+    if len(so) != len(to):
+        raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+    if len(so) - 1 > 65535 or (np.diff(so) >= 2 ** 31).any() or (np.diff(to) >= 2 ** 31).any():
+        raise L.SfmiError(f"{what}: at most 65535 pairs, every set below 2^31 rows")
+    if splits is not None and (isinstance(splits, bool) or not isinstance(splits, (int, np.integer)) or not 1 <= int(splits) <= 64):
+        raise L.SfmiError(f"{what}: splits must be None or an integer in [1, 64], got {splits!r}")
+    if queries_per_lane not in (None, 2, 4) or isinstance(queries_per_lane, bool):
+        raise L.SfmiError(f"{what}: queries_per_lane must be None, 2 or 4, got {queries_per_lane!r}")
+    dev = on_device(what, fs, ft)
+    S, q = int(splits or 0), int(queries_per_lane or 0)
+    fs, ft = fs.float().contiguous(), ft.float().contiguous()
+    idx, d2 = _feature_nn(fs, ft, so, to, S, q)
+    N = fs.shape[0]
+    sod, tod = torch.from_numpy(so).to(dev), torch.from_numpy(to).to(dev)
+    sid = torch.repeat_interleave(torch.arange(len(so) - 1, device=dev), torch.from_numpy(np.diff(so)).to(dev), output_size=N)
+    local = torch.arange(N, device=dev) - sod[sid]
+    keep = idx >= 0
+    if mutual and N and ft.shape[0]:
+        back, _ = _feature_nn(ft, fs, to, so, S, q)
+        keep &= back[(idx.long().clamp(min=0) + tod[sid]).clamp(max=ft.shape[0] - 1)].long() == local
+    pre = torch.cumsum(keep, 0, dtype=torch.int64)
+    c_off = torch.cat([pre.new_zeros(1), pre])[sod].cpu().numpy().astype(np.int64)          # the one read-back
+    rows = torch.nonzero(keep)[:, 0]
+    corr = torch.stack([local[rows], idx[rows].long()], 1).to(torch.int32).contiguous()
+    return corr, c_off, idx, d2
+
+
+def correspondence_hypotheses(sizes, H, seed=0):
+    """The RANSAC draws of ransac_correspondences_dev: scan.plane_hypotheses' counter-hash draws over the correspondences of every pair,
+    (B,H,3) int32 on the host.  Repeated indices are not redrawn: the kernel marks such a hypothesis invalid."""
+    from .scan import plane_hypotheses
+    return plane_hypotheses(sizes, H, seed)
+
+
+class _Greg:
+    """The validated arguments of one RANSAC call on the device"""
+
+    def __init__(self, what, source, target, s_off, t_off, corr, c_off):
+        s, t = points_arg(source, f"{what} source"), points_arg(target, f"{what} target")
+        if s.dim() == 3 or t.dim() == 3:
+            if s.dim() != 3 or t.dim() != 3 or s.shape[0] != t.shape[0] or s_off is not None or t_off is not None:
+                raise L.SfmiError(f"{what}: batched (B,N,3) sources need a (B,M,3) target of the same B and no offsets")
+            B = s.shape[0]
+            so, to = np.arange(B + 1, dtype=np.int64) * s.shape[1], np.arange(B + 1, dtype=np.int64) * t.shape[1]
+        else:
+            so, to = host_offsets(s_off, s.shape[0], f"{what} s_off"), host_offsets(t_off, t.shape[0], f"{what} t_off")
+            if len(so) != len(to):
+                raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+        B = len(so) - 1
+        if B < 1 or B > 65535 or (np.diff(so) >= 2 ** 31).any() or (np.diff(to) >= 2 ** 31).any():
+            raise L.SfmiError(f"{what}: between 1 and 65535 pairs, every set below 2^31 points")
+        if not isinstance(corr, torch.Tensor) or corr.dim() != 2 or corr.shape[1] != 2 or corr.dtype.is_floating_point or corr.dtype == torch.bool:
+            raise L.SfmiError(f"{what}: corr must be a (C,2) integer tensor of (source index, target index)")
+        co = host_offsets(c_off, corr.shape[0], f"{what} c_off")
+        if len(co) != B + 1 or (np.diff(co) >= 2 ** 31).any():
+            raise L.SfmiError(f"{what}: c_off must cut the correspondences into the {B} pairs")
+        if corr.shape[0] and (s.numel() == 0 or t.numel() == 0):
+            raise L.SfmiError(f"{what}: corr names points of empty clouds")
+        self.B, self.so, self.to, self.co = B, so, to, co
+        self.s, self.t, self.corr = s.reshape(-1, 3), t.reshape(-1, 3), corr
+
+    def to_device(self, what, *more):
+        dev = self.dev = on_device(what, self.s, self.t, self.corr, *more)
+        self.s, self.t = self.s.float().contiguous(), self.t.float().contiguous()
+        self.corr = self.corr.to(torch.int32).contiguous()
+        self.sod, self.tod, self.cod = (torch.from_numpy(v).to(dev) for v in (self.so, self.to, self.co))
+        self.max_c = int(np.diff(self.co).max())
+        return dev
+
+    def bad_pairs(self):
+        """(B,) int32: a coordinate of the pair is not finite"""
+        out = torch.zeros(self.B, device=self.dev, dtype=torch.int32)
+        for x, od in ((self.s, self.sod), (self.t, self.tod)):
+            z = excl_at(torch.cumsum((~torch.isfinite(x).all(1)).to(torch.int32), 0, dtype=torch.int32), od)
+            out |= ((z[1:] - z[:-1]) > 0).to(torch.int32)
+        return out
+
+    def poses(self, trd, similarity):
+        H = trd.shape[1]
+        poses = torch.empty(self.B, H, 12, device=self.dev, dtype=torch.float64)
+        valid = torch.empty(self.B, H, device=self.dev, dtype=torch.int32)
+        L.check(L.lib().sfmi_greg_poses_f32(L.ptr(self.s), L.ptr(self.t), L.ptr(self.sod), L.ptr(self.tod), L.ptr(self.corr), L.ptr(self.cod),
+                                            L.ptr(trd), self.B, H, self.corr.shape[0], similarity, L.ptr(poses), L.ptr(valid), L.stream_ptr()),
+                "sfmi_greg_poses_f32")
+        return poses, valid
+
+    def score(self, poses, valid, bad, maxd2):
+        H = poses.shape[1]
+        i32 = dict(device=self.dev, dtype=torch.int32)
+        count, best, status = torch.empty(self.B, H, **i32), torch.empty(self.B, **i32), torch.empty(self.B, **i32)
+        L.check(L.lib().sfmi_greg_score_f32(L.ptr(self.s), L.ptr(self.t), L.ptr(self.sod), L.ptr(self.tod), L.ptr(self.corr), L.ptr(self.cod),
+                                            L.ptr(poses), L.ptr(valid), L.ptr(bad), self.B, H, self.max_c, maxd2, L.ptr(count), L.ptr(best),
+                                            L.ptr(status), L.stream_ptr()), "sfmi_greg_score_f32")
+        return count, best, status
+
+    def refit(self, poses, best, status, maxd2, refit):
+        H, C = poses.shape[1], self.corr.shape[0]
+        pose = torch.empty(self.B, 12, device=self.dev, dtype=torch.float64)
+        inlier = torch.zeros(C, device=self.dev, dtype=torch.uint8)
+        n_in = torch.empty(self.B, device=self.dev, dtype=torch.int32)
+        sums = torch.empty(self.B, GREG_SUMS, device=self.dev, dtype=torch.float64)
+        L.check(L.lib().sfmi_greg_refit_f32(L.ptr(self.s), L.ptr(self.t), L.ptr(self.sod), L.ptr(self.tod), L.ptr(self.corr), L.ptr(self.cod),
+                                            L.ptr(poses), L.ptr(best), self.B, H, C, maxd2, int(bool(refit)), L.ptr(status), L.ptr(pose),
+                                            L.ptr(inlier), L.ptr(n_in), L.ptr(sums), L.stream_ptr()), "sfmi_greg_refit_f32")
+        return pose, inlier, n_in, sums
+
+
+def _triples_arg(tr, B, what):
+    if not isinstance(tr, torch.Tensor):
+        tr = np.asarray(tr)
+        if tr.dtype == np.bool_ or not np.issubdtype(tr.dtype, np.integer):
+            raise L.SfmiError(f"{what}: triples must be integers")
+    elif tr.dtype.is_floating_point or tr.dtype == torch.bool:
+        raise L.SfmiError(f"{what}: triples must be integers")
+    if tr.ndim != 3 or tr.shape[0] != B or tr.shape[1] < 1 or tr.shape[2] != 3:
+        raise L.SfmiError(f"{what}: triples must be ({B},H,3) with H >= 1, got {tuple(tr.shape)}")
+    return tr
+
+
+def _triples_dev(tr, dev):
+    return (tr if isinstance(tr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tr)).to(dev)).to(torch.int32).contiguous()
+
+
+def _check_similarity(v, what):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) <= 1:
+        raise L.SfmiError(f"{what}: similarity must be a number in [0, 1], got {v!r}")
+    return float(v)
+
+
+def _maxd2(max_dist, what):
+    return float(np.float32(_check_max_dist(max_dist, what) ** 2))
+
+
+def hypothesis_poses_dev(source, target, s_off=None, t_off=None, corr=None, c_off=None, triples=None, similarity=0.9):
+    """The poses of RANSAC hypotheses: triples (B,H,3) of correspondence indices local to each pair -> poses (B,H,12) f64 row-major
+    [R | t] (NaN for an invalid hypothesis), valid (B,H) int32.  The validity rules and the three-pair Kabsch are include/sfmi.h's."""
+    what = "hypothesis_poses_dev"
+    a = _Greg(what, source, target, s_off, t_off, corr, c_off)
+    tr = _triples_arg(triples, a.B, what)
+    sim = _check_similarity(similarity, what)
+    dev = a.to_device(what, *([tr] if isinstance(tr, torch.Tensor) else []))
+    return a.poses(_triples_dev(tr, dev), sim)
+
+
+def score_poses_dev(source, target, s_off=None, t_off=None, corr=None, c_off=None, max_dist=None, poses=None):
+    """count (B,H) int32: how many correspondences of pair b lie within max_dist under pose h of the pair - the transform of
+    transform_points_dev, d2 by nn_dist's f32 rule, d2 <= f32(max_dist^2).  poses (B,H,12) / (B,H,3,4) / (B,H,4,4) f64."""
+    what = "score_poses_dev"
+    a = _Greg(what, source, target, s_off, t_off, corr, c_off)
+    maxd2 = _maxd2(max_dist, what)
+    p = poses.detach().to(torch.float64) if isinstance(poses, torch.Tensor) else torch.from_numpy(np.asarray(poses, np.float64))
+    if p.dim() == 4 and p.shape[2:] == (4, 4):
+        p = p[:, :, :3, :]
+    if p.dim() < 3 or p.shape[0] != a.B or p.shape[1] < 1 or p[0, 0].numel() != 12:
+        raise L.SfmiError(f"{what}: poses must be ({a.B},H,12), ({a.B},H,3,4) or ({a.B},H,4,4), got {tuple(poses.shape)}")
+    dev = a.to_device(what)
+    p = p.reshape(a.B, p.shape[1], 12).to(dev).contiguous()
+    return a.score(p, None, None, maxd2)[0]
+
+
+def _ransac(what, a, max_dist, hypotheses, seed, triples, similarity, refit, extra_bad=None):
+    from .scan import _check_count
+    maxd2 = _maxd2(max_dist, what)
+    sim = _check_similarity(similarity, what)
+    tr = (correspondence_hypotheses(np.diff(a.co), _check_count(hypotheses, what, "hypotheses"), seed) if triples is None
+          else _triples_arg(triples, a.B, what))
+    dev = a.to_device(what, *([tr] if isinstance(tr, torch.Tensor) else []))
+    trd = _triples_dev(tr, dev)
+    bad = a.bad_pairs()
+    if extra_bad is not None:
+        bad |= extra_bad.to(torch.int32)
+    poses, valid = a.poses(trd, sim)
+    count, best, status = a.score(poses, valid, bad, maxd2)
+    pose, inlier, n_in, sums = a.refit(poses, best, status, maxd2, refit)
+    C = torch.from_numpy(np.diff(a.co)).to(dev).double()
+    fitness = torch.where(C > 0, n_in.double() / C.clamp(min=1), torch.zeros_like(C))
+    return (_pose44(pose), fitness, inlier, n_in, count, best, status), dict(poses=poses, valid=valid, sums=sums)
+
+
+def ransac_correspondences_dev(source, target, s_off=None, t_off=None, corr=None, c_off=None, max_dist=None, hypotheses=4096, seed=0,
+                               triples=None, similarity=0.9, refit=True, details=False):
+    """RANSAC over correspondences for a ragged batch of pairs (Open3D's registration_ransac_based_on_feature_matching with its edge
+    length checker), exact in its counts and deterministic.
+
+    source / target / offsets as icp_dev takes them; corr (C,2) integers (source index, target index) local to the pair's sets with
+    (B+1,) offsets c_off, as match_features_dev returns them.  A hypothesis is a triple of correspondence indices of the pair:
+    correspondence_hypotheses(sizes, hypotheses, seed), or `triples` (B,H,3).  Its pose is the least-squares rigid motion of the three
+    pairs; it is invalid (count -1) when an index repeats or lies outside, two of its points coincide, an edge of the two triangles
+    fails ls >= similarity lt and lt >= similarity ls, or the triangle is degenerate.  count[b,h] = the correspondences within max_dist
+    under pose h (score_poses_dev's rule); best[b] = the valid hypothesis of largest count, the lowest h among equal counts.
+    refit=True: the least-squares motion of the winner's inliers (f64 sums in a fixed order) and the inliers under it.
+    -> pose (B,4,4) f64, fitness (B,) f64 = n_in / C, inlier (C,) uint8, n_in (B,) int32, count (B,H) int32, best (B,) int32, status (B,)
+    int32, all on the device: 0 ok, 1 no valid hypothesis (fewer than 3 correspondences included), 2 the winner has fewer than 3
+    inliers or the refit is degenerate, 4 a non-finite coordinate in the pair; with 1, 2 and 4 the pose is the identity.  With
+    `details` a dict(poses (B,H,12), valid (B,H), sums (B,16)) follows.  Bit-identical from run to run; a pair's results depend on that
+    pair alone."""
+    what = "ransac_correspondences_dev"
+    a = _Greg(what, source, target, s_off, t_off, corr, c_off)
+    out, more = _ransac(what, a, max_dist, hypotheses, seed, triples, similarity, refit)
+    return out + (more,) if details else out
+
+
+def _oriented_normals(x, o, k, viewpoint):
+    """estimate_normals_dev, turned towards the viewpoints or, without them, away from each set's centroid (a frame-covariant choice; the
+    centroid is the set's own, summed in a fixed order on the device: a set's normals do not depend on the batch around it).  x: (N,3) f32
+    contiguous"""
+    from .scan import estimate_normals_dev
+    if viewpoint is not None:
+        return estimate_normals_dev(x, o, k, viewpoint)[0]
+    n = estimate_normals_dev(x, o, k)[0].contiguous()
+    if x.shape[0]:
+        od = torch.from_numpy(o).to(x.device)
+        L.check(L.lib().sfmi_fpfh_orient_f32(L.ptr(x), L.ptr(od), len(o) - 1, x.shape[0], L.ptr(n), L.stream_ptr()), "sfmi_fpfh_orient_f32")
+    return n
+
+
+def global_registration_dev(source, target, s_off=None, t_off=None, voxel=None, normals_k=16, feature_k=32, feature_radius=None,
+                            max_dist=None, viewpoints=None, mutual=True, **ransac):
+    """Coarse alignment of every (source, target) pair without a starting pose: both clouds are reduced by scan.voxel_downsample_dev
+    (voxel=None: used as they are), get normals (scan.estimate_normals_dev with normals_k, turned towards `viewpoints` = (source (B,3),
+    target (B,3)) or, with None, away from each set's centroid), FPFH features (fpfh_dev with feature_k, feature_radius), correspondences
+    (match_features_dev) and a pose by ransac_correspondences_dev(max_dist, **ransac); max_dist defaults to 1.5 x voxel.
+    -> ransac_correspondences_dev's results; the correspondences index the reduced clouds.  The pose is a start for icp_dev."""
+    from .scan import _check_k, _check_voxel, voxel_downsample_dev
+    what = "global_registration_dev"
+    s, so, _ = point_sets(source, s_off, f"{what} source")
+    t, to, _ = point_sets(target, t_off, f"{what} target")
+    if len(so) != len(to):
+        raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+    if not 1 <= len(so) - 1 <= 65535:
+        raise L.SfmiError(f"{what}: between 1 and 65535 pairs")
+    if voxel is not None:
+        voxel = _check_voxel(voxel, what)
+    if max_dist is None:
+        if voxel is None:
+            raise L.SfmiError(f"{what}: max_dist is needed when voxel is None")
+        max_dist = 1.5 * voxel
+    _check_max_dist(max_dist, what)
+    _check_k(normals_k, what)
+    _check_k(feature_k, what)
+    _radius_arg(feature_radius, what, "feature_radius")
+    bad_kw = set(ransac) - {"hypotheses", "seed", "triples", "similarity", "refit"}
+    if bad_kw:
+        raise L.SfmiError(f"{what}: unknown arguments {sorted(bad_kw)}")
+    vs, vt = (None, None)
+    if viewpoints is not None:
+        if not isinstance(viewpoints, (tuple, list)) or len(viewpoints) != 2:
+            raise L.SfmiError(f"{what}: viewpoints must be None or a pair (source viewpoints, target viewpoints)")
+        vs, vt = viewpoints
+    on_device(what, s, t)
+    s, t = s.float().contiguous(), t.float().contiguous()
+    if voxel is not None:
+        s, so = voxel_downsample_dev(s, so, voxel)[:2]
+        t, to = voxel_downsample_dev(t, to, voxel)[:2]
+    ns, nt = _oriented_normals(s, so, normals_k, vs), _oriented_normals(t, to, normals_k, vt)
+    fs, ft = fpfh_dev(s, ns, so, feature_k, feature_radius)[0], fpfh_dev(t, nt, to, feature_k, feature_radius)[0]
+    corr, co, _, _ = match_features_dev(fs, ft, so, to, mutual)
+    a = _Greg(what, s, t, so, to, corr, co)
+    a.to_device(what)
+    extra = torch.zeros(a.B, device=a.dev, dtype=torch.int32)
+    for v, od in ((ns, a.sod), (fs, a.sod), (nt, a.tod), (ft, a.tod)):
+        z = excl_at(torch.cumsum((~torch.isfinite(v).all(1)).to(torch.int32), 0, dtype=torch.int32), od)
+        extra |= ((z[1:] - z[:-1]) > 0).to(torch.int32)
+    return _ransac(what, a, max_dist, ransac.get("hypotheses", 4096), ransac.get("seed", 0), ransac.get("triples"),
+                   ransac.get("similarity", 0.9), ransac.get("refit", True), extra)[0]
+
+
+def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, **icp):
     """Several partial scans of one object, each in its own frame, merged in the frame of scan 0.
 
     clouds: a list of (n_i,3) HIP tensors, or one (N,3) tensor with (S+1,) offsets `offs`.  Scans 1.. are registered onto scan 0 in one
     batch - icp_dev(**icp), or icp_multiscale_dev when `voxels` is among the keyword arguments - and transformed; the clouds are
     concatenated in scan order and, with `voxel`, reduced by scan.voxel_downsample_dev.  A scan whose status is >= 2 is left out and
-    reported.  -> merged (K,3) f32, poses (S,4,4) f64 (identity for scan 0), status (S,) host int32 (0 for scan 0).  The statuses are
-    read back (one synchronisation)."""
+    reported.  global_init: a dict of global_registration_dev's arguments; the pose it finds for a scan is the `init` of the ICP that
+    follows, for scans that are not roughly aligned beforehand (a scan whose global status is >= 1 keeps the identity); None: the scans
+    start from `init` or the identity.  -> merged (K,3) f32, poses (S,4,4) f64 (identity for scan 0), status (S,) host int32 (0 for
+    scan 0).  The statuses are read back (one synchronisation)."""
     from .scan import voxel_downsample_dev
     what = "merge_scans_dev"
+    if global_init is not None and (not isinstance(global_init, dict) or "init" in icp):
+        raise L.SfmiError(f"{what}: global_init must be a dict of global_registration_dev arguments and replaces init")
     if voxel is not None and not (isinstance(voxel, (int, float, np.integer, np.floating)) and not isinstance(voxel, bool) and 0 < float(voxel) < float("inf")):
         raise L.SfmiError(f"{what}: voxel must be a finite number > 0, got {voxel!r}")
     if isinstance(clouds, (list, tuple)):
@@ -295,6 +701,9 @@ def merge_scans_dev(clouds, offs=None, voxel=None, **icp):
         src, so = x[int(o[1]):], o[1:] - o[1]
         tgt, to = first.repeat(S - 1, 1), np.arange(S, dtype=np.int64) * first.shape[0]
         run = icp_multiscale_dev if "voxels" in icp else icp_dev
+        if global_init is not None:
+            g = global_registration_dev(src, tgt, so, to, **global_init)
+            icp = dict(icp, init=torch.where((g[6] < 1)[:, None, None], g[0], poses[1:]))
         pose, _, _, _, st = run(src, tgt, so, to, **icp)
         poses[1:] = pose
         status[1:] = st.cpu().numpy()
