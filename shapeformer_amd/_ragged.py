@@ -33,6 +33,18 @@ def host_offsets(off, n, what, empty_ok=False, flatten=False):
     return o
 
 
+def check_count(v, what, name, lo=1):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < 2 ** 31:
+        raise L.SfmiError(f"{what}: {name} must be an integer in [{lo}, 2^31), got {v!r}")
+    return int(v)
+
+
+def check_nonneg(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
+        raise L.SfmiError(f"{what}: {name} must be a finite number >= 0, got {v!r}")
+    return float(v)
+
+
 def on_device(what, *tensors):
     """-> the one HIP device all the tensors are on.  Every caller's last check."""
     dev = tensors[0].device
@@ -109,6 +121,11 @@ def batch_meshes(meshes, dev):
 
 
 # ---- prefix sums and sorted runs (any device) ------------------------------------------------------------------------------
+
+def set_ids(o, dev):
+    """host offsets (B+1,) -> (N,) int64 on dev: the set of every row"""
+    return torch.repeat_interleave(torch.arange(len(o) - 1, device=dev), torch.from_numpy(np.diff(o)).to(dev), output_size=int(o[-1]))
+
 
 def excl(x):
     """(n,) counts -> (n+1,) int32 exclusive prefix sums"""

@@ -101,7 +101,6 @@ __device__ __forceinline__ void fps_block_count(int& c, int& f, int* red) {
   __syncthreads();                                             // red may be written again (never is: one call per workgroup)
 }
 
-__device__ __forceinline__ bool fps_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // P / valid: the set's own base; nb <= FPS_THREADS * R.  -> the number of picks made (0 with status != 0)
 template <int R>
@@ -121,7 +120,7 @@ __device__ __forceinline__ int fps_resident(const float* __restrict__ P, const u
     z[r] = in ? P[3 * (long long)i + 2] : 0.f;
     d[r] = ok ? INFINITY : -1.f;                               // -1: not (or no longer) a candidate; min(-1, d2 >= 0) stays -1
     cand += ok;
-    bad |= ok && !fps_finite(x[r], y[r], z[r]);
+    bad |= ok && !sfmi_finite3(x[r], y[r], z[r]);
   }
   fps_block_count(cand, bad, red);
   status = cand == 0 ? 1 : (bad ? 2 : 0);
@@ -183,7 +182,7 @@ __device__ __forceinline__ int fps_streaming(const float* __restrict__ P, const 
       const bool ok = in && (!valid || valid[j] != 0);
       v[e] = ok ? INFINITY : -1.f;
       cand += ok;
-      if (ok) bad |= !fps_finite(P[3 * j], P[3 * j + 1], P[3 * j + 2]);
+      if (ok) bad |= !sfmi_finite3(P[3 * j], P[3 * j + 1], P[3 * j + 2]);
       if (v[e] > bd) {
         bd = v[e];
         bi = (int)(j - pbeg);

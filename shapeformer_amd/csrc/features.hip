@@ -10,15 +10,15 @@
 //    group sums run through the lanes in ascending bin order.
 //    orient_kernel: one workgroup per set turns the normals away from the set's centroid (f64 sums in a fixed order), the
 //    frame-covariant orientation global_registration_dev uses without viewpoints.
-// 3. feature_nn_kernel: the tiling of pointdist.hip's nn_kernel / register.hip's icp_correspond_kernel for rows of 33 floats: Q
+// 3. feature_nn_kernel: sfmi_search.h's split plan, chunk ranges and merge around a tile scan of its own for rows of 33 floats: Q
 //    queries per lane in registers (33 VGPRs each), the targets through an LDS tile of 64 rows padded to 36 floats = 9 float4, read
 //    as broadcast ds_read_b128; acc = d0 d0, then acc = fmaf(dj, dj, acc) for j = 1..32 (the three pad columns would add fmaf(0, 0,
 //    acc) = acc and are not computed); a strict `<` over ascending indices.  When there are too few query blocks the targets are cut
-//    into S chunks (grid.y) and feature_merge_kernel merges them in ascending chunk order with a strict `<`.
+//    into S chunks (grid.y) and the shared merge takes them in ascending chunk order with a strict `<`.
 //
 // Loop discipline: no kernel waits on another workgroup, there are no spins, every loop around a barrier has workgroup-uniform
 // bounds.  An index is range-checked before the row it names is read.
-#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_search.h"   // the split search (plan, chunk ranges, merge) and the ragged-batch helpers: DESIGN.md §5.5a
 
 // the pair feature and the second stage are written once, here and in numpy: every product and sum rounded on its own
 #pragma clang fp contract(off)
@@ -36,20 +36,10 @@ constexpr int FN_THREADS = 256;
 constexpr int FN_TILE = 64;                      // target rows per LDS tile
 constexpr int FN_W = 36;                         // floats per row of the tile: 33 padded to 9 float4
 constexpr int FN_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
-constexpr int FN_MAX_SPLITS = 64;
-constexpr int FN_MIN_CHUNK = 512;                // fewest target rows (on average) per split
 constexpr int FN_Q_DEFAULT = 2;
 
 inline bool fn_q_ok(int q) { return q == 2 || q == 4; }
-inline long long fn_qblocks(int B, long long N, int q) { return cdiv(N, (long long)FN_THREADS * q) + B; }
-
-inline int fn_splits(int B, long long N, long long M, int q) {
-  long long s = cdiv(FN_TARGET_BLOCKS, fn_qblocks(B, N, q));
-  const long long by_m = M / ((long long)B * FN_MIN_CHUNK);
-  if (s > by_m) s = by_m;
-  if (s > FN_MAX_SPLITS) s = FN_MAX_SPLITS;
-  return s < 1 ? 1 : (int)s;
-}
+inline int fn_splits(int B, long long N, long long M, int q) { return sfmi_splits(B, N, M, FN_TARGET_BLOCKS, FN_THREADS * q); }
 
 // clamp(floor(t), 0, 10); a NaN falls into bin 0 (fmax returns its other argument)
 __device__ __forceinline__ int fp_bin(double t) { return (int)fmin(fmax(floor(t), 0.0), 10.0); }
@@ -144,18 +134,6 @@ __global__ __launch_bounds__(FP_THREADS) void fpfh_kernel(const long long* __res
 
 // ---- normals turned away from the set's centroid ----------------------------------------------------------------------------------------
 
-// the workgroup's sum in every lane: wave_sum_f64, then the 16 wave sums through the same xor tree.  red: OR_WAVES doubles.
-__device__ __forceinline__ double or_block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();                                             // the previous use of red is over
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = red[threadIdx.x & (OR_WAVES - 1)];
-#pragma unroll
-  for (int o = OR_WAVES / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  return t;
-}
-
 // one workgroup per set: the centroid of the set's finite points in f64 in a fixed order (a lane's points ascending, wave_sum_f64, a
 // fixed tree over the 16 waves), then n <- -n where (p - c).n < 0.  A set's result depends on that set alone.
 __global__ __launch_bounds__(OR_THREADS) void orient_kernel(const float* __restrict__ P, const long long* __restrict__ off,
@@ -168,12 +146,12 @@ __global__ __launch_bounds__(OR_THREADS) void orient_kernel(const float* __restr
   double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
   for (long long i = tid; i < n; i += OR_THREADS) {
     const double x = (double)Pb[3 * i], y = (double)Pb[3 * i + 1], z = (double)Pb[3 * i + 2];
-    if (isfinite(x) && isfinite(y) && isfinite(z)) {
+    if (sfmi_finite3(x, y, z)) {
       sx += x; sy += y; sz += z; sc += 1.0;
     }
   }
-  sx = or_block_sum(sx, red); sy = or_block_sum(sy, red); sz = or_block_sum(sz, red);
-  sc = or_block_sum(sc, red);                                  // whole numbers below 2^31: exact in f64
+  sx = sfmi_block_sum_f64<OR_WAVES>(sx, red); sy = sfmi_block_sum_f64<OR_WAVES>(sy, red); sz = sfmi_block_sum_f64<OR_WAVES>(sz, red);
+  sc = sfmi_block_sum_f64<OR_WAVES>(sc, red);                  // whole numbers below 2^31: exact in f64
   if (!(sc > 0.0)) return;                                     // workgroup-uniform: no finite point, nothing is turned
   const double cx = sx / sc, cy = sy / sc, cz = sz / sc;
   for (long long i = tid; i < n; i += OR_THREADS) {
@@ -212,10 +190,9 @@ __global__ __launch_bounds__(FN_THREADS) void feature_nn_kernel(const float* __r
     best[r] = INFINITY;
     bi[r] = -1;
   }
-  const long long q0 = boff[b], q1 = boff[b + 1];
-  const long long chunk = cdiv(q1 - q0, (long long)gridDim.y);
-  long long j0 = q0 + (long long)blockIdx.y * chunk, j1 = j0 + chunk;
-  if (j1 > q1) j1 = q1;
+  const long long q0 = boff[b];
+  long long j0, j1;
+  sfmi_chunk_range(q0, boff[b + 1], gridDim.y, blockIdx.y, j0, j1);
   for (long long t0 = j0; t0 < j1; t0 += FN_TILE) {            // workgroup-uniform bounds
     __syncthreads();                                           // the previous tile is consumed
     for (int e = tid; e < FN_TILE * FN_W; e += FN_THREADS) {
@@ -260,22 +237,6 @@ __global__ __launch_bounds__(FN_THREADS) void feature_nn_kernel(const float* __r
       ii[i] = bi[r];
     }
   }
-}
-
-// merge the S partials of every query in ascending chunk order (strict `<`: the lower index wins a tie)
-__global__ void feature_merge_kernel(const float* __restrict__ pd, const int* __restrict__ pi, int S, long long N, float* __restrict__ d2,
-                                     int* __restrict__ idx) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  float best = pd[i];
-  int bi = pi[i];
-  for (int s = 1; s < S; ++s) {
-    const float d = pd[(long long)s * N + i];
-    const int k = pi[(long long)s * N + i];
-    if (d < best) { best = d; bi = k; }
-  }
-  d2[i] = best;
-  idx[i] = bi;
 }
 
 template <int Q>
@@ -332,7 +293,7 @@ int sfmi_fpfh_nn_f32(const float* A, const float* Bf, const long long* aoff, con
                      void* stream) {
   q = q ? q : FN_Q_DEFAULT;
   if (B <= 0 || B > 65535 || N < 0 || M < 0 || n_blocks < 0 || n_blocks >= (1ll << 31) || !fn_q_ok(q) || splits < 0 ||
-      splits > FN_MAX_SPLITS || !aoff || !boff || !block_off)
+      splits > SFMI_MAX_SPLITS || !aoff || !boff || !block_off)
     return SFMI_EINVAL;
   if (N == 0 || n_blocks == 0) return SFMI_OK;
   if (!A || !idx || !d2 || (M > 0 && !Bf)) return SFMI_EINVAL;
@@ -343,8 +304,7 @@ int sfmi_fpfh_nn_f32(const float* A, const float* Bf, const long long* aoff, con
   int* i = S > 1 ? part_idx : idx;
   if (q == 2) fn_launch<2>(A, Bf, aoff, boff, block_off, B, N, n_blocks, S, d, i, st);
   else fn_launch<4>(A, Bf, aoff, boff, block_off, B, N, n_blocks, S, d, i, st);
-  if (S > 1)
-    hipLaunchKernelGGL(feature_merge_kernel, dim3(blocks256(N)), dim3(256), 0, st, (const float*)part_d2, (const int*)part_idx, S, N, d2, idx);
+  if (S > 1) sfmi_nn_merge<true, false>(part_d2, part_idx, nullptr, nullptr, B, S, N, d2, idx, st);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

@@ -8,10 +8,11 @@
 //    proper rotation) in f64.  The cross-covariance of three pairs has rank 2, so its singular vectors come from a one-sided Jacobi
 //    iteration on its columns (squaring it first would square its condition number), and the third pair of singular vectors is the
 //    cross product of the first two on either side: the rotation is proper by construction.
-// 2. greg_score_kernel, as segment.hip's ps_score_kernel: grid (correspondence chunks, hypothesis tiles, pairs).  The tile's 64 poses
+// 2. greg_score_kernel, built as segment.hip's ps_score_kernel and ending in the same sfmi_commit_counts (sfmi_ragged.h): grid
+//    (correspondence chunks, hypothesis tiles, pairs).  The tile's 64 poses
 //    go to LDS once per workgroup, read as broadcasts; a lane keeps 4 correspondences in registers; the wave's count of a hypothesis is
 //    the sum over the 4 of popcount(ballot(inlier)); lane h keeps the count of hypothesis h, the four waves meet in LDS and one integer
-//    atomicAdd per (workgroup, hypothesis) reaches `count`.  greg_best_kernel: the arg max, the lowest h among equal counts.
+//    atomicAdd per (workgroup, hypothesis) reaches `count`.  greg_best_kernel: sfmi_best_of_row, the lowest h among equal counts.
 // 3. greg_refit_kernel, one workgroup per pair: the winner's inliers, their two centroids and the 9 centred cross terms in f64 by two
 //    passes in a fixed order (a lane's correspondences ascending, wave_sum_f64, a fixed tree over the 16 waves), Kabsch again, and the
 //    final mask under the refit pose.  A batch equals per-pair calls bit for bit.
@@ -20,7 +21,7 @@
 //
 // Loop discipline: no kernel waits on another workgroup, there are no spins, every loop around a barrier has workgroup-uniform
 // bounds.  Integer atomics only.  An index is range-checked before the point it names is read.
-#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_ragged.h"   // the ragged-batch helpers, the pose row and the RANSAC pieces shared with segment.hip: DESIGN.md §5.5a
 
 // the transform and the inlier test are written once, here and in numpy: every product and sum rounded on its own
 #pragma clang fp contract(off)
@@ -31,20 +32,11 @@ constexpr int GS_THREADS = 256;
 constexpr int GS_WAVES = GS_THREADS / 64;
 constexpr int GS_R = 4;                          // correspondences per lane
 constexpr int GS_CHUNK = GS_THREADS * GS_R;      // correspondences per workgroup pass
-constexpr int GS_HT = 64;                        // hypotheses per tile: lane h of a wave keeps the count of hypothesis h
+constexpr int GS_HT = SFMI_HT;                   // hypotheses per tile
 constexpr int GR_THREADS = 1024;
 constexpr int GR_WAVES = GR_THREADS / 64;
-constexpr int GR_SWEEPS = 8;                     // a 3x3 in f64 is converged to the last bit after 5 or 6
 constexpr int GR_NS = 16;                        // count | sum s (3) | sum q (3) | centred cross terms (9, row-major q x s)
-constexpr unsigned GREG_MAX_GRID = 65535;
 constexpr double GR_RANK_TOL = 1e-12;            // sigma_2 <= tol x sigma_1: degenerate
-
-__device__ __forceinline__ double gr_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-// x' = f32(((r0 x + r1 y) + r2 z) + t) in f64, the f32 point widened first; T: one row of the pose (4 doubles)
-__device__ __forceinline__ float gr_row(const double* __restrict__ T, double x, double y, double z) {
-  return (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
-}
 
 // one rotation of a one-sided Jacobi iteration: columns p and q of m (and of the accumulated v) are turned so that they are orthogonal
 __device__ __forceinline__ void gr_rot(double& m0p, double& m1p, double& m2p, double& m0q, double& m1q, double& m2q, double& v0p, double& v1p,
@@ -69,7 +61,7 @@ __device__ __forceinline__ void gr_swap(double& a, double& b) { const double t =
 // ordered so that sg[0] >= sg[1] >= sg[2] (sg = the column norms)
 __device__ __forceinline__ void gr_svd3(double (&m)[9], double (&v)[9], double (&sg)[3]) {
   v[0] = 1.0; v[1] = 0.0; v[2] = 0.0; v[3] = 0.0; v[4] = 1.0; v[5] = 0.0; v[6] = 0.0; v[7] = 0.0; v[8] = 1.0;
-  for (int sweep = 0; sweep < GR_SWEEPS; ++sweep) {
+  for (int sweep = 0; sweep < SFMI_JACOBI_SWEEPS; ++sweep) {
     gr_rot(m[0], m[3], m[6], m[1], m[4], m[7], v[0], v[3], v[6], v[1], v[4], v[7]);   // columns (0, 1)
     gr_rot(m[0], m[3], m[6], m[2], m[5], m[8], v[0], v[3], v[6], v[2], v[5], v[8]);   // columns (0, 2)
     gr_rot(m[1], m[4], m[7], m[2], m[5], m[8], v[1], v[4], v[7], v[2], v[5], v[8]);   // columns (1, 2)
@@ -129,7 +121,8 @@ __device__ __forceinline__ bool gr_gather(const float* __restrict__ Sb, const fl
 
 // d2(T s, q) by nn_dist's rule on the f32 transformed point
 __device__ __forceinline__ float gr_d2(const double* __restrict__ T, const double (&s)[3], const float (&q)[3]) {
-  const float dx = gr_row(T, s[0], s[1], s[2]) - q[0], dy = gr_row(T + 4, s[0], s[1], s[2]) - q[1], dz = gr_row(T + 8, s[0], s[1], s[2]) - q[2];
+  const float dx = sfmi_pose_row(T, s[0], s[1], s[2]) - q[0], dy = sfmi_pose_row(T + 4, s[0], s[1], s[2]) - q[1],
+              dz = sfmi_pose_row(T + 8, s[0], s[1], s[2]) - q[2];
   return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
@@ -151,7 +144,7 @@ __global__ __launch_bounds__(256) void greg_pose_kernel(const float* __restrict_
   bool ok = t0 >= 0 && t1 >= 0 && t2 >= 0 && t0 < C && t1 < C && t2 < C && t0 != t1 && t0 != t2 && t1 != t2;
   double s[3][3], q[3][3], pose[12];
 #pragma unroll
-  for (int e = 0; e < 12; ++e) pose[e] = gr_nan();
+  for (int e = 0; e < 12; ++e) pose[e] = sfmi_nan_f64();
   if (ok) {
     const int tr[3] = {t0, t1, t2};
 #pragma unroll
@@ -203,7 +196,7 @@ __global__ __launch_bounds__(256) void greg_pose_kernel(const float* __restrict_
     ok = ok && gr_kabsch(M, cs, cq, pose);
     if (!ok) {
 #pragma unroll
-      for (int e = 0; e < 12; ++e) pose[e] = gr_nan();
+      for (int e = 0; e < 12; ++e) pose[e] = sfmi_nan_f64();
     }
   }
 #pragma unroll
@@ -228,7 +221,7 @@ __global__ __launch_bounds__(GS_THREADS) void greg_score_kernel(const float* __r
                                                                 const int* __restrict__ bad, int H, float maxd2, int* __restrict__ count) {
   __shared__ double ps[GS_HT][12];                             // an invalid hypothesis: NaN, the pose of no inlier
   __shared__ int wc[GS_WAVES][GS_HT];
-  const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63;
   const long long c0 = coff[b], C = coff[b + 1] - c0;
   if ((long long)blockIdx.x * GS_CHUNK >= C) return;           // workgroup-uniform, before any barrier
   const long long ns = soff[b + 1] - soff[b], nt = toff[b + 1] - toff[b];
@@ -240,7 +233,7 @@ __global__ __launch_bounds__(GS_THREADS) void greg_score_kernel(const float* __r
   for (int e = tid; e < GS_HT * 12; e += GS_THREADS) {
     const int hh = e / 12, k = e - 12 * hh, h = h0 + hh;
     const bool ok = h < H && !pair_bad && (!valid || valid[(long long)b * H + h] != 0);
-    ps[hh][k] = ok ? poses[12 * ((long long)b * H + h) + k] : gr_nan();
+    ps[hh][k] = ok ? poses[12 * ((long long)b * H + h) + k] : sfmi_nan_f64();
   }
   __syncthreads();
   for (long long c = blockIdx.x; c * GS_CHUNK < C; c += gridDim.x) {   // workgroup-uniform bounds
@@ -252,7 +245,7 @@ __global__ __launch_bounds__(GS_THREADS) void greg_score_kernel(const float* __r
       if (!(i < C && gr_gather(Sb, Tb, cb, i, ns, nt, s[r], q[r]))) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) {                          // padding: NaN is an inlier of nothing
-          s[r][e] = gr_nan();
+          s[r][e] = sfmi_nan_f64();
           q[r][e] = __int_as_float(0x7FC00000);
         }
       }
@@ -266,59 +259,23 @@ __global__ __launch_bounds__(GS_THREADS) void greg_score_kernel(const float* __r
       for (int r = 0; r < GS_R; ++r) cnt += __popcll(__ballot(gr_d2(Tp, s[r], q[r]) <= maxd2));
       mine = lane == hh ? cnt : mine;
     }
-    wc[w][lane] = mine;
-    __syncthreads();
-    if (tid < GS_HT) {
-      int tot = 0;
-#pragma unroll
-      for (int v = 0; v < GS_WAVES; ++v) tot += wc[v][tid];
-      if (tot > 0) atomicAdd(count + (long long)b * H + h0 + tid, tot);   // tot > 0 only for a valid hypothesis, so h0 + tid < H
-    }
-    __syncthreads();                                           // wc is consumed before the next pass writes it
+    sfmi_commit_counts(wc, mine, count + (long long)b * H + h0);
   }
 }
 
-// (c, h) <- the better of the two under (larger count, then lower h)
-__device__ __forceinline__ void gr_take(int& c, int& h, int oc, int oh) {
-  const bool take = oc > c || (oc == c && oh < h);
-  c = take ? oc : c;
-  h = take ? oh : h;
-}
-
-__global__ __launch_bounds__(256) void greg_best_kernel(int H, const int* __restrict__ count, const int* __restrict__ bad,
-                                                        int* __restrict__ best, int* __restrict__ status) {
-  __shared__ int sc[4], sh[4];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int* row = count + (long long)b * H;
-  int bc = -1, bh = 0x7FFFFFFF;
-  for (int h = tid; h < H; h += 256) gr_take(bc, bh, row[h], h);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gr_take(bc, bh, __shfl_xor(bc, o, 64), __shfl_xor(bh, o, 64));
-  if ((tid & 63) == 0) {
-    sc[tid >> 6] = bc;
-    sh[tid >> 6] = bh;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int v = 1; v < 4; ++v) gr_take(bc, bh, sc[v], sh[v]);
+__global__ __launch_bounds__(SFMI_BEST_THREADS) void greg_best_kernel(int H, const int* __restrict__ count,
+                                                                      const int* __restrict__ bad,
+                                                                      int* __restrict__ best, int* __restrict__ status) {
+  const int b = blockIdx.x;
+  int bc, bh;
+  sfmi_best_of_row(count + (long long)b * H, H, bc, bh);
+  if (threadIdx.x == 0) {
     best[b] = bc >= 0 ? bh : -1;
     status[b] = (bad && bad[b] != 0) ? 4 : (bc >= 0 ? 0 : 1);
   }
 }
 
 // ---- the refit ------------------------------------------------------------------------------------------------------------------------
-
-// the workgroup's sum in every lane: wave_sum_f64, then the 16 wave sums through the same xor tree.  red: GR_WAVES doubles.
-__device__ __forceinline__ double gr_block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();                                             // the previous use of red is over
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = red[threadIdx.x & (GR_WAVES - 1)];
-#pragma unroll
-  for (int o = GR_WAVES / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  return t;
-}
 
 __global__ __launch_bounds__(GR_THREADS) void greg_refit_kernel(const float* __restrict__ S, const float* __restrict__ T,
                                                                 const long long* __restrict__ soff, const long long* __restrict__ toff,
@@ -338,7 +295,7 @@ __global__ __launch_bounds__(GR_THREADS) void greg_refit_kernel(const float* __r
   const bool ok = status[b] == 0 && h >= 0 && h < H;           // workgroup-uniform
   double W[12];
 #pragma unroll
-  for (int e = 0; e < 12; ++e) W[e] = ok ? poses[12 * ((long long)b * H + h) + e] : gr_nan();
+  for (int e = 0; e < 12; ++e) W[e] = ok ? poses[12 * ((long long)b * H + h) + e] : sfmi_nan_f64();
   // pass 1: the winner's inliers, their number and the sums of their points
   double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (long long i = tid; i < C; i += GR_THREADS) {
@@ -353,7 +310,7 @@ __global__ __launch_bounds__(GR_THREADS) void greg_refit_kernel(const float* __r
     }
   }
 #pragma unroll
-  for (int e = 0; e < 7; ++e) acc[e] = gr_block_sum(acc[e], red);   // the count: whole numbers below 2^31, exact in f64
+  for (int e = 0; e < 7; ++e) acc[e] = sfmi_block_sum_f64<GR_WAVES>(acc[e], red);   // the count: whole numbers below 2^31, exact in f64
   const int cnt = (int)acc[0];
   double P[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
   double M[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -373,7 +330,7 @@ __global__ __launch_bounds__(GR_THREADS) void greg_refit_kernel(const float* __r
       }
     }
 #pragma unroll
-    for (int e = 0; e < 9; ++e) M[e] = gr_block_sum(M[e], red);
+    for (int e = 0; e < 9; ++e) M[e] = sfmi_block_sum_f64<GR_WAVES>(M[e], red);
     good = gr_kabsch(M, cs, cq, P);
   } else if (good) {
 #pragma unroll
@@ -405,7 +362,7 @@ __global__ __launch_bounds__(GR_THREADS) void greg_refit_kernel(const float* __r
       mask[i] = in ? 1 : 0;
       mm += in ? 1 : 0;
     }
-    mcount = (int)gr_block_sum((double)mm, red);
+    mcount = (int)sfmi_block_sum_f64<GR_WAVES>((double)mm, red);
   }
   if (tid == 0) {
 #pragma unroll
@@ -414,8 +371,6 @@ __global__ __launch_bounds__(GR_THREADS) void greg_refit_kernel(const float* __r
   }
 }
 
-inline unsigned greg_grid(long long n) { return (unsigned)(n < 1 ? 1 : (n > GREG_MAX_GRID ? GREG_MAX_GRID : n)); }
-
 }  // namespace
 
 extern "C" {
@@ -423,7 +378,7 @@ extern "C" {
 int sfmi_greg_poses_f32(const float* src, const float* tgt, const long long* soff, const long long* toff, const int* corr,
                         const long long* coff, const int* triples, int B, int H, long long C, double similarity, double* poses,
                         int* valid, void* stream) {
-  if (B <= 0 || B > (int)GREG_MAX_GRID || H < 1 || C < 0 || !(similarity >= 0.0 && similarity <= 1.0) || !soff || !toff || !coff ||
+  if (B <= 0 || B > (int)SFMI_MAX_GRID || H < 1 || C < 0 || !(similarity >= 0.0 && similarity <= 1.0) || !soff || !toff || !coff ||
       !triples || !poses || !valid || (C > 0 && (!src || !tgt || !corr)))
     return SFMI_EINVAL;
   hipLaunchKernelGGL(greg_pose_kernel, dim3(blocks256((long long)B * H)), dim3(256), 0, (hipStream_t)stream, src, tgt, soff, toff, corr, coff,
@@ -435,15 +390,15 @@ int sfmi_greg_poses_f32(const float* src, const float* tgt, const long long* sof
 int sfmi_greg_score_f32(const float* src, const float* tgt, const long long* soff, const long long* toff, const int* corr,
                         const long long* coff, const double* poses, const int* valid, const int* bad, int B, int H, long long max_c,
                         float maxd2, int* count, int* best, int* status, void* stream) {
-  if (B <= 0 || B > (int)GREG_MAX_GRID || H < 1 || cdiv(H, GS_HT) > GREG_MAX_GRID || max_c < 0 || max_c >= (1ll << 31) ||
+  if (B <= 0 || B > (int)SFMI_MAX_GRID || H < 1 || cdiv(H, GS_HT) > SFMI_MAX_GRID || max_c < 0 || max_c >= (1ll << 31) ||
       !(maxd2 >= 0.f) || !soff || !toff || !coff || !poses || !count || !best || !status || (max_c > 0 && (!src || !tgt || !corr)))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(greg_init_kernel, dim3(blocks256((long long)B * H)), dim3(256), 0, st, valid, bad, B, H, count);
   if (max_c > 0)
-    hipLaunchKernelGGL(greg_score_kernel, dim3(greg_grid(cdiv(max_c, GS_CHUNK)), (unsigned)cdiv(H, GS_HT), (unsigned)B), dim3(GS_THREADS), 0,
-                       st, src, tgt, soff, toff, corr, coff, poses, valid, bad, H, maxd2, count);
-  hipLaunchKernelGGL(greg_best_kernel, dim3((unsigned)B), dim3(256), 0, st, H, (const int*)count, bad, best, status);
+    hipLaunchKernelGGL(greg_score_kernel, dim3(sfmi_grid_cap(cdiv(max_c, GS_CHUNK)), (unsigned)cdiv(H, GS_HT), (unsigned)B),
+                       dim3(GS_THREADS), 0, st, src, tgt, soff, toff, corr, coff, poses, valid, bad, H, maxd2, count);
+  hipLaunchKernelGGL(greg_best_kernel, dim3((unsigned)B), dim3(SFMI_BEST_THREADS), 0, st, H, (const int*)count, bad, best, status);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

@@ -3,9 +3,10 @@
 // the host (xgutils/geoutil.py:362-366 points_dist: cKDTree(p2).query(p1, k)); its real-scan datasets (shapeformer/data/imnet_datasets/
 // redwood.py, realtest.py) feed raw .pts clouds, flying pixels included, straight to the encoder.  DESIGN.md §5.14.
 //
-// 1. knn_kernel<K, R, EXCL, SLOTS>: brute force, the sibling of nn_kernel in pointdist.hip.  The same feed (256 lanes x R queries per lane in
-//    registers, Q through a 256-point float4 LDS tile read as a broadcast ds_read_b128) and the same distance expression in the same
-//    order, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), so column 0 is nn_kernel's result bit for bit.
+// 1. knn_kernel<K, R, EXCL, SLOTS>: brute force, on sfmi_search.h's split plan, block offsets and chunk ranges like nn_kernel in
+//    pointdist.hip.  The feed of sfmi_search3 (256 lanes x R queries per lane in registers, Q through a 256-point float4 LDS tile read
+//    as a broadcast ds_read_b128) and its distance expression in the same order, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), so column 0
+//    is nn_kernel's result bit for bit; the inner loop is its own, because it keeps a list.
 //    Each query keeps a sorted list of K (d2, index) pairs in registers.  A candidate is first compared with the list's last entry
 //    (the common case ends there: one compare on top of nn_kernel's work); only a smaller one runs a fully unrolled
 //    compare-and-shift chain through the K slots.  Every list index is a compile-time constant: nothing goes to scratch.
@@ -21,15 +22,13 @@
 // 2. knn_mean_dist_kernel: per point the mean over the k columns of sqrt(d2) in f64, in column order.
 // 3. knn_normals_kernel: one lane per point: centroid and 3x3 covariance of its neighbours in f64 in the table's column order, the
 //    eigenvector of the smallest eigenvalue by a fixed number of cyclic Jacobi sweeps in f64 (no data-dependent trip count).
-#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_search.h"   // the split search (plan, block offsets, chunk ranges) and the ragged-batch helpers: DESIGN.md §5.5a
 
 namespace {
 
 constexpr int KNN_THREADS = 256;
 constexpr int KNN_TILE = 256;                    // Q points per LDS tile (float4: 4 KiB)
 constexpr int KNN_MAX_K = 64;
-constexpr int KNN_MAX_SPLITS = 64;
-constexpr int KNN_MIN_CHUNK = 512;               // fewest Q points (on average) per chunk
 constexpr size_t KNN_MAX_PARTIAL = (size_t)256 << 20;   // bytes of partial lists: the split is cut down to stay below it
 
 // the instance that serves k: its list length, its queries per lane, and how many workgroups the split aims at (a workgroup is one
@@ -38,28 +37,9 @@ inline int knn_instance(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 
 inline int knn_r(int K) { return K == 8 ? 4 : (K == 16 ? 2 : 1); }
 inline int knn_target_blocks(int K) { return K <= 16 ? 1280 : (K == 32 ? 1024 : 768); }
 
-// query-block upper bound: sum_b ceil(N_b / QB) <= ceil(N / QB) + B
-inline long long knn_qblocks(int B, long long N, int QB) { return cdiv(N, QB) + B; }
-
+// the split is also cut down to keep the partial lists below KNN_MAX_PARTIAL
 inline int knn_splits(int B, long long N, long long M, int K) {
-  long long s = cdiv(knn_target_blocks(K), knn_qblocks(B, N, KNN_THREADS * knn_r(K)));
-  const long long by_m = M / ((long long)B * KNN_MIN_CHUNK);
-  if (s > by_m) s = by_m;
-  if (s > KNN_MAX_SPLITS) s = KNN_MAX_SPLITS;
-  const long long by_ws = (long long)(KNN_MAX_PARTIAL / ((size_t)(N > 0 ? N : 1) * K * 8));
-  if (s > by_ws) s = by_ws;
-  return s < 2 ? 1 : (int)s;
-}
-
-// block_off[b] = sum_{b' < b} ceil(N_b' / QB): which query blocks belong to which set (one lane; B is small)
-__global__ void knn_block_offsets_kernel(const long long* __restrict__ poff, long long* __restrict__ block_off, int B, int QB) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long acc = 0;
-  for (int b = 0; b < B; ++b) {
-    block_off[b] = acc;
-    acc += cdiv(poff[b + 1] - poff[b], QB);
-  }
-  block_off[B] = acc;
+  return sfmi_splits(B, N, M, knn_target_blocks(K), KNN_THREADS * knn_r(K), (long long)(KNN_MAX_PARTIAL / ((size_t)(N > 0 ? N : 1) * K * 8)));
 }
 
 // (d, j) enters the sorted list when it is smaller than the last entry: every entry that d is strictly smaller than moves one slot
@@ -136,10 +116,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const float* __restric
       il[r][c] = -1;
     }
   }
-  const long long q0 = qoff[b], q1 = qoff[b + 1];
-  const long long chunk = cdiv(q1 - q0, (long long)gridDim.y);
-  long long j0 = q0 + (long long)blockIdx.y * chunk, j1 = j0 + chunk;
-  if (j1 > q1) j1 = q1;
+  const long long q0 = qoff[b];
+  long long j0, j1;
+  sfmi_chunk_range(q0, qoff[b + 1], gridDim.y, blockIdx.y, j0, j1);
   float thr = INFINITY;                                        // SLOTS > 0: the last list entry as of the latest flush
   int cnt = 0;                                                 //            pending candidates of this lane
   for (long long t0 = j0; t0 < j1; t0 += KNN_TILE) {
@@ -247,9 +226,10 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
 }
 
 template <int K, int R, int SLOTS>
-void knn_launch(const float* P, const float* Q, const long long* poff, const long long* qoff, const long long* block_off, int B,
+void knn_launch(const float* P, const float* Q, const long long* poff, const long long* qoff, long long* block_off, int B,
                 long long N, int k, int S, bool excl, float* d2, int* idx, float* pd, int* pi, hipStream_t st) {
-  const dim3 grid((unsigned)knn_qblocks(B, N, KNN_THREADS * R), (unsigned)S);
+  hipLaunchKernelGGL(sfmi_block_offsets_kernel<KNN_THREADS * R>, dim3(1), dim3(64), 0, st, poff, block_off, B);
+  const dim3 grid((unsigned)sfmi_qblocks(B, N, KNN_THREADS * R), (unsigned)S);
   float* dd = S == 1 ? d2 : pd;
   int* ii = S == 1 ? idx : pi;
   if (excl)
@@ -272,7 +252,7 @@ __global__ void knn_mean_dist_kernel(const float* __restrict__ d2, long long N, 
 
 // ---- normals by local PCA -------------------------------------------------------------------------------------------------------
 
-// jacobi_rot and KNN_JACOBI_SWEEPS: sfmi_ragged.h (csrc/segment.hip's plane refit runs the same solver)
+// jacobi_rot and SFMI_JACOBI_SWEEPS: sfmi_ragged.h (csrc/segment.hip's plane refit runs the same solver)
 __global__ void knn_normals_kernel(const float* __restrict__ P, const long long* __restrict__ off, const int* __restrict__ idx, int B,
                                    long long N, int k, const double* __restrict__ view, float* __restrict__ normal,
                                    float* __restrict__ variation) {
@@ -306,7 +286,7 @@ __global__ void knn_normals_kernel(const float* __restrict__ P, const long long*
   }
   a00 /= n; a01 /= n; a02 /= n; a11 /= n; a12 /= n; a22 /= n;
   double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;   // v[row][column]
-  for (int sweep = 0; sweep < KNN_JACOBI_SWEEPS; ++sweep) {
+  for (int sweep = 0; sweep < SFMI_JACOBI_SWEEPS; ++sweep) {
     jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);   // (0, 1), third axis 2
     jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);   // (0, 2), third axis 1
     jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);   // (1, 2), third axis 0
@@ -362,7 +342,6 @@ int sfmi_knn_f32(const float* P, const float* Q, const long long* poff, const lo
   long long* block_off = (long long*)workspace;
   float* pd = (float*)((char*)workspace + align256((size_t)(B + 1) * 8));
   int* pi = (int*)((char*)pd + align256((size_t)S * K * N * 4));
-  hipLaunchKernelGGL(knn_block_offsets_kernel, dim3(1), dim3(64), 0, st, poff, block_off, B, KNN_THREADS * knn_r(K));
   const bool ex = exclude_self != 0;
   if (K == 8) knn_launch<8, 4, 0>(P, Q, poff, qoff, block_off, B, N, k, S, ex, d2, idx, pd, pi, st);
   else if (K == 16) knn_launch<16, 2, 0>(P, Q, poff, qoff, block_off, B, N, k, S, ex, d2, idx, pd, pi, st);

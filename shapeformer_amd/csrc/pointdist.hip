@@ -13,42 +13,21 @@
 //    Filling the chip: when there are too few query blocks, Q_b is cut into S contiguous chunks (grid.y); chunk s writes a
 //    partial (d2, idx) per query and a second launch merges the S partials in ascending chunk order with a strict `<` (the
 //    lower index wins a tie again).  No atomics: results are bit-identical from run to run and do not depend on S.
+//    The plan, the block offsets, the search and the merge are sfmi_search.h's, shared with knn.hip, register.hip and features.hip;
+//    nn_kernel is the block's owner and the plain query load around sfmi_search3.
 // 2. Area-weighted surface sampling of a batch of indexed meshes: per-face areas in f64, a per-shape inclusive f64 CDF (one
 //    workgroup per shape, fixed summation order), then one thread per sample: the face by binary search on a counter-hash
 //    uniform of (seed, sample), barycentric weights 1-sqrt(u), sqrt(u)(1-v), sqrt(u) v as in geoutil.sampleMesh.
-#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_search.h"   // the split search (plan, block offsets, scan, merge) and the ragged-batch helpers: DESIGN.md §5.5a
 
 namespace {
 
-constexpr int NN_THREADS = 256;
+constexpr int NN_THREADS = SFMI_SCAN_TILE;
 constexpr int NN_R = 8;                          // queries per lane (registers: 3 coordinates + best d2 + best index each)
 constexpr int NN_QB = NN_THREADS * NN_R;         // queries per workgroup
-constexpr int NN_TILE = 256;                     // Q points per LDS tile (float4: 4 KiB)
 constexpr int NN_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
-constexpr int NN_MAX_SPLITS = 64;
-constexpr int NN_MIN_CHUNK = 512;                // fewest Q points (on average) per chunk
 
-// query-block upper bound: sum_b ceil(N_b / QB) <= ceil(N / QB) + B
-inline long long nn_qblocks(int B, long long N) { return cdiv(N, NN_QB) + B; }
-
-inline int nn_splits(int B, long long N, long long M) {
-  long long s = cdiv(NN_TARGET_BLOCKS, nn_qblocks(B, N));
-  const long long by_m = M / ((long long)B * NN_MIN_CHUNK);
-  if (s > by_m) s = by_m;
-  if (s > NN_MAX_SPLITS) s = NN_MAX_SPLITS;
-  return s < 1 ? 1 : (int)s;
-}
-
-// block_off[b] = sum_{b' < b} ceil(N_b' / QB): which query blocks belong to which set (one lane; B is small)
-__global__ void nn_block_offsets_kernel(const long long* __restrict__ poff, long long* __restrict__ block_off, int B) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long acc = 0;
-  for (int b = 0; b < B; ++b) {
-    block_off[b] = acc;
-    acc += cdiv(poff[b + 1] - poff[b], NN_QB);
-  }
-  block_off[B] = acc;
-}
+inline int nn_splits(int B, long long N, long long M) { return sfmi_splits(B, N, M, NN_TARGET_BLOCKS, NN_QB); }
 
 // grid (query blocks upper bound, S).  S == 1: d_out / i_out are the results (i_out may be null); S > 1: partial buffers,
 // chunk s at d_out + s * N.
@@ -56,77 +35,16 @@ __global__ __launch_bounds__(NN_THREADS) void nn_kernel(const float* __restrict_
                                                         const long long* __restrict__ poff, const long long* __restrict__ qoff,
                                                         const long long* __restrict__ block_off, int B, long long N,
                                                         float* __restrict__ d_out, int* __restrict__ i_out) {
-  __shared__ float4 tile[NN_TILE];
   const long long g = blockIdx.x;
   if (g >= block_off[B]) return;                               // block-uniform: the grid is an upper bound
   const int b = sfmi_owner(block_off, B, g);
-  const int tid = threadIdx.x;
-  const long long pend = poff[b + 1];
-  const long long qbase = poff[b] + (g - block_off[b]) * NN_QB;
-  float px[NN_R], py[NN_R], pz[NN_R], best[NN_R];
-  int bi[NN_R];
-#pragma unroll
-  for (int r = 0; r < NN_R; ++r) {
-    const long long i = qbase + r * NN_THREADS + tid;
-    const bool ok = i < pend;
-    px[r] = ok ? P[3 * i] : 0.f;
-    py[r] = ok ? P[3 * i + 1] : 0.f;
-    pz[r] = ok ? P[3 * i + 2] : 0.f;
-    best[r] = INFINITY;
-    bi[r] = -1;
-  }
-  const long long q0 = qoff[b], q1 = qoff[b + 1];
-  const long long chunk = cdiv(q1 - q0, (long long)gridDim.y);
-  long long j0 = q0 + (long long)blockIdx.y * chunk, j1 = j0 + chunk;
-  if (j1 > q1) j1 = q1;
-  for (long long t0 = j0; t0 < j1; t0 += NN_TILE) {
-    __syncthreads();                                           // the previous tile is consumed
-    {
-      const long long j = t0 + tid;
-      // padding past the chunk: +inf coordinates give d2 = inf, never < best (strict), so they are never selected
-      tile[tid] = j < j1 ? make_float4(Q[3 * j], Q[3 * j + 1], Q[3 * j + 2], 0.f) : make_float4(INFINITY, INFINITY, INFINITY, 0.f);
-    }
-    __syncthreads();
-    const int jb = (int)(t0 - q0);                             // local index of the tile's first point (M_b < 2^31)
-#pragma unroll 4
-    for (int jj = 0; jj < NN_TILE; ++jj) {
-      const float4 q = tile[jj];                               // broadcast ds_read_b128
-#pragma unroll
-      for (int r = 0; r < NN_R; ++r) {
-        const float dx = px[r] - q.x, dy = py[r] - q.y, dz = pz[r] - q.z;
-        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-        const bool lt = d2 < best[r];
-        best[r] = lt ? d2 : best[r];
-        bi[r] = lt ? jb + jj : bi[r];
-      }
-    }
-  }
-  float* dd = d_out + (long long)blockIdx.y * N;
-  int* ii = i_out ? i_out + (long long)blockIdx.y * N : nullptr;
-#pragma unroll
-  for (int r = 0; r < NN_R; ++r) {
-    const long long i = qbase + r * NN_THREADS + tid;
-    if (i < pend) {
-      dd[i] = best[r];
-      if (ii) ii[i] = bi[r];
-    }
-  }
-}
-
-// merge the S partials of every query in ascending chunk order (strict `<`: the lower index wins a tie)
-__global__ void nn_merge_kernel(const float* __restrict__ pd, const int* __restrict__ pi, int S, long long N, float* __restrict__ d2,
-                                int* __restrict__ idx) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  float best = pd[i];
-  int bi = pi[i];
-  for (int s = 1; s < S; ++s) {
-    const float d = pd[(long long)s * N + i];
-    const int k = pi[(long long)s * N + i];
-    if (d < best) { best = d; bi = k; }
-  }
-  d2[i] = best;
-  if (idx) idx[i] = bi;
+  const auto load = [P](long long i, bool ok, float& x, float& y, float& z) {
+    x = ok ? P[3 * i] : 0.f;
+    y = ok ? P[3 * i + 1] : 0.f;
+    z = ok ? P[3 * i + 2] : 0.f;
+  };
+  sfmi_search3<NN_R>(Q, qoff[b], qoff[b + 1], poff[b] + (g - block_off[b]) * NN_QB, poff[b + 1], load,
+                      d_out + (long long)blockIdx.y * N, i_out ? i_out + (long long)blockIdx.y * N : nullptr);
 }
 
 // ---- mesh sampling ---------------------------------------------------------------------------------------------------------
@@ -151,7 +69,7 @@ __global__ void mesh_area_kernel(const float* __restrict__ verts, const int* __r
   const double e1x = p[1][0] - p[0][0], e1y = p[1][1] - p[0][1], e1z = p[1][2] - p[0][2];
   const double e2x = p[2][0] - p[0][0], e2y = p[2][1] - p[0][1], e2z = p[2][2] - p[0][2];
   const double cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
-  area[t] = ok ? 0.5 * sqrt(cx * cx + cy * cy + cz * cz) : __longlong_as_double(0x7FF8000000000000ll);
+  area[t] = ok ? 0.5 * sqrt(cx * cx + cy * cy + cz * cz) : sfmi_nan_f64();
 }
 
 // one workgroup per shape: area -> inclusive CDF in place, in a fixed order (each lane a contiguous run, Hillis-Steele over the
@@ -243,15 +161,16 @@ int sfmi_nn_dist_f32(const float* P, const float* Q, const long long* poff, cons
   hipStream_t st = (hipStream_t)stream;
   const int S = nn_splits(B, N, M);
   long long* block_off = (long long*)workspace;
-  hipLaunchKernelGGL(nn_block_offsets_kernel, dim3(1), dim3(64), 0, st, poff, block_off, B);
-  const dim3 grid((unsigned)nn_qblocks(B, N), (unsigned)S);
+  hipLaunchKernelGGL(sfmi_block_offsets_kernel<NN_QB>, dim3(1), dim3(64), 0, st, poff, block_off, B);
+  const dim3 grid((unsigned)sfmi_qblocks(B, N, NN_QB), (unsigned)S);
   if (S == 1) {
     hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)block_off, B, N, d2, idx);
   } else {
     float* pd = (float*)((char*)workspace + align256((size_t)(B + 1) * 8));
     int* pi = (int*)((char*)pd + align256((size_t)S * N * 4));
     hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)block_off, B, N, pd, pi);
-    hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, (const float*)pd, (const int*)pi, S, N, d2, idx);
+    if (idx) sfmi_nn_merge<true, false>(pd, pi, nullptr, nullptr, B, S, N, d2, idx, st);
+    else sfmi_nn_merge<false, false>(pd, pi, nullptr, nullptr, B, S, N, d2, idx, st);
   }
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

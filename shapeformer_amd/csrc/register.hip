@@ -4,10 +4,11 @@
 //
 // The pose of a pair is 12 doubles on the device, row-major [R | t]; it is always applied to the ORIGINAL f32 source, so nothing
 // accumulates in f32.  One iteration is three launches (four when the target is split), and nothing is read back:
-// 1. icp_correspond_kernel: the tiled search of pointdist.hip's nn_kernel - 256 lanes x 8 queries in registers, the target through a
-//    256-point float4 LDS tile read as a broadcast, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), a strict `<` over ascending indices - with
-//    the pose applied as the query is loaded.  (idx, d2) are the bits nn_dist gives on the transformed cloud.  When there are too
-//    few query blocks the target is cut into S chunks (grid.y) and icp_merge_kernel merges them in ascending chunk order.
+// 1. icp_correspond_kernel: sfmi_search.h's sfmi_search3, the search pointdist.hip's nn_kernel runs - 256 lanes x 8 queries in registers,
+//    the target through a 256-point float4 LDS tile read as a broadcast, d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), a strict `<` over
+//    ascending indices - with the pose applied as the query is loaded.  (idx, d2) are the bits nn_dist gives on the transformed cloud.
+//    When there are too few query blocks the target is cut into S chunks (grid.y) and the shared merge, skipping frozen pairs, merges
+//    them in ascending chunk order.
 // 2. icp_accumulate_kernel: grid (source chunks of 1024 points, pairs).  A lane gathers q (and n) of its 4 points, ascending, into
 //    29 f64 accumulators (the 21 upper entries of A = sum J^T J, the 6 of sum J^T r, sum d2, count); wave_sum_f64; the 4 waves in
 //    order; one partial per chunk.  Chunks start at the set's first point: a pair's sums do not depend on the batch around it.
@@ -18,20 +19,17 @@
 //
 // Loop discipline: no kernel waits on another workgroup, there are no spins, every loop around a barrier has workgroup-uniform
 // bounds.  No float atomics: every sum has one fixed order.  An index is range-checked before the point it names is read.
-#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_search.h"   // the split search (plan, block offsets, scan, merge) and the ragged-batch helpers: DESIGN.md §5.5a
 
 // the transform and the residuals are written once, here and in numpy (tests/icp_ref.py): every product and sum rounded on its own
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int IC_THREADS = 256;
+constexpr int IC_THREADS = SFMI_SCAN_TILE;
 constexpr int IC_R = 8;                          // queries per lane
 constexpr int IC_QB = IC_THREADS * IC_R;         // queries per workgroup
-constexpr int IC_TILE = 256;                     // target points per LDS tile (float4: 4 KiB)
 constexpr int IC_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
-constexpr int IC_MAX_SPLITS = 64;
-constexpr int IC_MIN_CHUNK = 512;                // fewest target points (on average) per split
 constexpr int IA_THREADS = 256;
 constexpr int IA_WAVES = IA_THREADS / 64;
 constexpr int IA_R = 4;                          // points per lane
@@ -40,22 +38,7 @@ constexpr int IC_NS = 29;                        // A (21, upper, row-major) | J
 constexpr int IC_SD2 = 27, IC_CNT = 28;
 constexpr int ICP_POINT = 0, ICP_PLANE = 1;
 
-inline long long ic_qblocks(int B, long long N) { return cdiv(N, IC_QB) + B; }
-
-inline int ic_splits(int B, long long N, long long M) {
-  long long s = cdiv(IC_TARGET_BLOCKS, ic_qblocks(B, N));
-  const long long by_m = M / ((long long)B * IC_MIN_CHUNK);
-  if (s > by_m) s = by_m;
-  if (s > IC_MAX_SPLITS) s = IC_MAX_SPLITS;
-  return s < 1 ? 1 : (int)s;
-}
-
-// x' = f32(((r0 x + r1 y) + r2 z) + t) in f64, the f32 point widened first; T: one row of the pose (4 doubles)
-__device__ __forceinline__ float ic_row(const double* __restrict__ T, double x, double y, double z) {
-  return (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
-}
-
-__device__ __forceinline__ bool ic_finite3(const float* __restrict__ p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
+inline int ic_splits(int B, long long N, long long M) { return sfmi_splits(B, N, M, IC_TARGET_BLOCKS, IC_QB); }
 
 // ---- start of a call ----------------------------------------------------------------------------------------------------------------
 
@@ -70,10 +53,10 @@ __global__ __launch_bounds__(256) void icp_check_kernel(const float* __restrict_
   bool x = false;
   for (int r = 0; r < 4; ++r) {
     const long long i = ((long long)blockIdx.x * 4 + r) * 256 + threadIdx.x;
-    if (i < n) x |= !ic_finite3(src + 3 * (s0 + i));
+    if (i < n) x |= !sfmi_finite3(src + 3 * (s0 + i));
     if (i < m) {
-      x |= !ic_finite3(tgt + 3 * (t0 + i));
-      if (plane) x |= !ic_finite3(nrm + 3 * (t0 + i));
+      x |= !sfmi_finite3(tgt + 3 * (t0 + i));
+      if (plane) x |= !sfmi_finite3(nrm + 3 * (t0 + i));
     }
   }
   if (__any(x) && (threadIdx.x & 63) == 0) atomicOr(bad + b, 1);
@@ -84,14 +67,7 @@ __global__ void icp_begin_kernel(const long long* __restrict__ soff, const doubl
                                  int B, long long* __restrict__ block_off, int* __restrict__ state, int* __restrict__ status,
                                  int* __restrict__ iterations, double* __restrict__ fitness, double* __restrict__ rmse) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b == 0) {
-    long long acc = 0;
-    for (int c = 0; c < B; ++c) {
-      block_off[c] = acc;
-      acc += cdiv(soff[c + 1] - soff[c], IC_QB);
-    }
-    block_off[B] = acc;
-  }
+  if (b == 0) sfmi_block_offsets(soff, block_off, B, IC_QB);
   if (b >= B) return;
   bool ok = bad[b] == 0;
   for (int e = 0; e < 12; ++e) ok = ok && isfinite(pose[12 * b + e]);
@@ -111,82 +87,19 @@ __global__ __launch_bounds__(IC_THREADS) void icp_correspond_kernel(const float*
                                                                     const long long* __restrict__ block_off,
                                                                     const double* __restrict__ pose, const int* __restrict__ state, int B,
                                                                     long long N, float* __restrict__ d_out, int* __restrict__ i_out) {
-  __shared__ float4 tile[IC_TILE];
   const long long g = blockIdx.x;
   if (g >= block_off[B]) return;                               // block-uniform: the grid is an upper bound
   const int b = sfmi_owner(block_off, B, g);
   if (state[b] != 0) return;                                   // a frozen pair: block-uniform, before any barrier
-  const int tid = threadIdx.x;
-  const long long pend = poff[b + 1];
-  const long long qbase = poff[b] + (g - block_off[b]) * IC_QB;
   const double* T = pose + 12 * b;
-  float px[IC_R], py[IC_R], pz[IC_R], best[IC_R];
-  int bi[IC_R];
-#pragma unroll
-  for (int r = 0; r < IC_R; ++r) {
-    const long long i = qbase + r * IC_THREADS + tid;
-    const bool ok = i < pend;
+  const auto load = [P, T](long long i, bool ok, float& px, float& py, float& pz) {   // the pose is applied as the query is loaded
     const double x = ok ? (double)P[3 * i] : 0.0, y = ok ? (double)P[3 * i + 1] : 0.0, z = ok ? (double)P[3 * i + 2] : 0.0;
-    px[r] = ic_row(T, x, y, z);
-    py[r] = ic_row(T + 4, x, y, z);
-    pz[r] = ic_row(T + 8, x, y, z);
-    best[r] = INFINITY;
-    bi[r] = -1;
-  }
-  const long long q0 = qoff[b], q1 = qoff[b + 1];
-  const long long chunk = cdiv(q1 - q0, (long long)gridDim.y);
-  long long j0 = q0 + (long long)blockIdx.y * chunk, j1 = j0 + chunk;
-  if (j1 > q1) j1 = q1;
-  for (long long t0 = j0; t0 < j1; t0 += IC_TILE) {            // workgroup-uniform bounds
-    __syncthreads();                                           // the previous tile is consumed
-    {
-      const long long j = t0 + tid;
-      // padding past the chunk: +inf coordinates give d2 = inf (or NaN), never < best (strict), so they are never selected
-      tile[tid] = j < j1 ? make_float4(Q[3 * j], Q[3 * j + 1], Q[3 * j + 2], 0.f) : make_float4(INFINITY, INFINITY, INFINITY, 0.f);
-    }
-    __syncthreads();
-    const int jb = (int)(t0 - q0);                             // local index of the tile's first point (M_b < 2^31)
-#pragma unroll 4
-    for (int jj = 0; jj < IC_TILE; ++jj) {
-      const float4 q = tile[jj];                               // broadcast ds_read_b128
-#pragma unroll
-      for (int r = 0; r < IC_R; ++r) {
-        const float dx = px[r] - q.x, dy = py[r] - q.y, dz = pz[r] - q.z;
-        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-        const bool lt = d2 < best[r];
-        best[r] = lt ? d2 : best[r];
-        bi[r] = lt ? jb + jj : bi[r];
-      }
-    }
-  }
-  float* dd = d_out + (long long)blockIdx.y * N;
-  int* ii = i_out + (long long)blockIdx.y * N;
-#pragma unroll
-  for (int r = 0; r < IC_R; ++r) {
-    const long long i = qbase + r * IC_THREADS + tid;
-    if (i < pend) {
-      dd[i] = best[r];
-      ii[i] = bi[r];
-    }
-  }
-}
-
-// merge the S partials of every query of a running pair in ascending chunk order (strict `<`: the lower index wins a tie)
-__global__ void icp_merge_kernel(const float* __restrict__ pd, const int* __restrict__ pi, const long long* __restrict__ poff,
-                                 const int* __restrict__ state, int B, int S, long long N, float* __restrict__ d2,
-                                 int* __restrict__ idx) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  if (state[sfmi_owner(poff, B, i)] != 0) return;
-  float best = pd[i];
-  int bi = pi[i];
-  for (int s = 1; s < S; ++s) {
-    const float d = pd[(long long)s * N + i];
-    const int k = pi[(long long)s * N + i];
-    if (d < best) { best = d; bi = k; }
-  }
-  d2[i] = best;
-  idx[i] = bi;
+    px = sfmi_pose_row(T, x, y, z);
+    py = sfmi_pose_row(T + 4, x, y, z);
+    pz = sfmi_pose_row(T + 8, x, y, z);
+  };
+  sfmi_search3<IC_R>(Q, qoff[b], qoff[b + 1], poff[b] + (g - block_off[b]) * IC_QB, poff[b + 1], load,
+                      d_out + (long long)blockIdx.y * N, i_out + (long long)blockIdx.y * N);
 }
 
 // ---- the normal equations -----------------------------------------------------------------------------------------------------------
@@ -249,7 +162,8 @@ __global__ __launch_bounds__(IA_THREADS) void icp_accumulate_kernel(const float*
       const float d = d2[p0 + i];
       if (j >= 0 && j < m && d <= maxd2) {                     // the index is checked before the point is read
         const double x = (double)P[3 * (p0 + i)], y = (double)P[3 * (p0 + i) + 1], z = (double)P[3 * (p0 + i) + 2];
-        const double ax = (double)ic_row(T, x, y, z), ay = (double)ic_row(T + 4, x, y, z), az = (double)ic_row(T + 8, x, y, z);
+        const double ax = (double)sfmi_pose_row(T, x, y, z), ay = (double)sfmi_pose_row(T + 4, x, y, z),
+                     az = (double)sfmi_pose_row(T + 8, x, y, z);
         const float* q = Q + 3 * (q0 + j);
         if (plane) {
           const float* nn = Nrm + 3 * (q0 + j);
@@ -392,9 +306,9 @@ __global__ void icp_transform_kernel(const float* __restrict__ P, const long lon
   if (i >= N) return;
   const double* T = pose + 12 * sfmi_owner(off, B, i);
   const double x = (double)P[3 * i], y = (double)P[3 * i + 1], z = (double)P[3 * i + 2];
-  out[3 * i] = ic_row(T, x, y, z);
-  out[3 * i + 1] = ic_row(T + 4, x, y, z);
-  out[3 * i + 2] = ic_row(T + 8, x, y, z);
+  out[3 * i] = sfmi_pose_row(T, x, y, z);
+  out[3 * i + 1] = sfmi_pose_row(T + 4, x, y, z);
+  out[3 * i + 2] = sfmi_pose_row(T + 8, x, y, z);
 }
 
 }  // namespace
@@ -445,15 +359,14 @@ int sfmi_icp_iterate_f32(const float* src, const float* tgt, const float* nrm, c
   if (N > 0 && S > 1 && (!part_d2 || !part_idx)) return SFMI_EINVAL;
   const int chunks = (int)(max_n > 0 ? cdiv(max_n, IA_CHUNK) : 1);
   if (N > 0) {
-    const dim3 grid((unsigned)ic_qblocks(B, N), (unsigned)S);
+    const dim3 grid((unsigned)sfmi_qblocks(B, N, IC_QB), (unsigned)S);
     if (S == 1) {
       hipLaunchKernelGGL(icp_correspond_kernel, grid, dim3(IC_THREADS), 0, st, src, tgt, soff, toff, block_off, (const double*)pose,
                          (const int*)state, B, N, d2, idx);
     } else {
       hipLaunchKernelGGL(icp_correspond_kernel, grid, dim3(IC_THREADS), 0, st, src, tgt, soff, toff, block_off, (const double*)pose,
                          (const int*)state, B, N, part_d2, part_idx);
-      hipLaunchKernelGGL(icp_merge_kernel, dim3(blocks256(N)), dim3(256), 0, st, (const float*)part_d2, (const int*)part_idx, soff,
-                         (const int*)state, B, S, N, d2, idx);
+      sfmi_nn_merge<true, true>(part_d2, part_idx, soff, state, B, S, N, d2, idx, st);   // a frozen pair's (idx, d2) stay
     }
     const dim3 agrid((unsigned)chunks, (unsigned)B);
     hipLaunchKernelGGL(icp_accumulate_kernel, agrid, dim3(IA_THREADS), 0, st, src, tgt, nrm, soff, toff, (const double*)pose,

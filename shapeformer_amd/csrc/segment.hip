@@ -8,8 +8,9 @@
 //    ps_score_kernel: grid (point chunks, hypothesis tiles, sets).  The tile's 64 planes (n, d, thr2 * nn) go to LDS once per
 //    workgroup, 5 doubles each, read as broadcasts; a lane keeps 4 points in registers as f64 and walks the tile; the wave's count of
 //    a hypothesis is the sum over the 4 points of popcount(ballot(inlier)), a scalar; lane h of the wave keeps the count of hypothesis h,
-//    the four waves meet in LDS and one integer atomicAdd per (workgroup, hypothesis) reaches `count`.  ps_best_kernel: one workgroup
-//    per set takes the arg max (lowest h among equal counts) and settles the status.  Integer atomics only: the result is a function
+//    the four waves meet in LDS and one integer atomicAdd per (workgroup, hypothesis) reaches `count` (sfmi_commit_counts).
+//    ps_best_kernel: one workgroup per set takes the arg max (sfmi_best_of_row: lowest h among equal counts) and settles the
+//    status.  Integer atomics only: the result is a function
 //    of the input.
 // 2. Plane refit (Open3D's last step), one workgroup per set: the seed plane's inliers, their centroid and covariance in f64 by two
 //    passes in a fixed order (a lane's points ascending, wave_sum_f64, a fixed tree over the 16 waves), the eigenvector of the smallest
@@ -23,7 +24,7 @@
 //
 // Loop discipline: no kernel waits on another workgroup; every loop around a barrier has workgroup-uniform bounds; the only
 // data-dependent loops are the union-find walks, whose termination argument is the header's (chains strictly descend).
-#include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_ragged.h"   // the ragged-batch helpers and the RANSAC pieces shared with global_register.hip: DESIGN.md §5.5a
 
 // the plane expressions are written once, here and in numpy: every product and sum rounded on its own
 #pragma clang fp contract(off)
@@ -34,7 +35,7 @@ constexpr int PS_THREADS = 256;
 constexpr int PS_WAVES = PS_THREADS / 64;
 constexpr int PS_R = 4;                          // points per lane, in registers as f64
 constexpr int PS_CHUNK = PS_THREADS * PS_R;      // points per workgroup pass
-constexpr int PS_HT = 64;                        // hypotheses per tile: lane h of a wave keeps the count of hypothesis h
+constexpr int PS_HT = SFMI_HT;                   // hypotheses per tile
 constexpr int RF_THREADS = 1024;
 constexpr int RF_WAVES = RF_THREADS / 64;
 constexpr int CL_THREADS = 256;
@@ -42,9 +43,6 @@ constexpr int CL_R = 2;                          // i points per lane
 constexpr int CL_IB = CL_THREADS * CL_R;         // i points per block
 constexpr int CL_TILE = 256;                     // j points per LDS tile
 constexpr int CL_JC = 512;                       // j points per workgroup: equal to CL_IB, so block indices compare directly
-constexpr unsigned SEG_MAX_GRID = 65535;
-
-__device__ __forceinline__ double seg_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // the plane through points i0, i1, i2 of the set that starts at Pb and has n points: normal (not unit), d = n . p0, nn = |n|^2.
 // false (and nothing read out of bounds) when an index repeats or lies outside the set, or when nn > 0 is false (collinear, NaN)
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __res
                                                               int* __restrict__ count, int* __restrict__ status) {
   __shared__ double pl[PS_HT][5];                              // (nx, ny, nz, d, thr2 * nn); an invalid hypothesis: (0, 0, 0, 0, -1)
   __shared__ int wc[PS_WAVES][PS_HT];
-  const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63;
   const long long base = off[b], n = off[b + 1] - base;
   if ((long long)blockIdx.x * PS_CHUNK >= n) return;           // workgroup-uniform, before any barrier
   const int h0 = blockIdx.y * PS_HT;
@@ -112,10 +110,10 @@ __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __res
     for (int r = 0; r < PS_R; ++r) {
       const long long i = c * PS_CHUNK + r * PS_THREADS + tid;
       const bool in = i < n;
-      x[r] = in ? (double)Pb[3 * i] : seg_nan();               // padding: NaN is an inlier of nothing
-      y[r] = in ? (double)Pb[3 * i + 1] : seg_nan();
-      z[r] = in ? (double)Pb[3 * i + 2] : seg_nan();
-      bad |= in && !(isfinite(x[r]) && isfinite(y[r]) && isfinite(z[r]));
+      x[r] = in ? (double)Pb[3 * i] : sfmi_nan_f64();          // padding: NaN is an inlier of nothing
+      y[r] = in ? (double)Pb[3 * i + 1] : sfmi_nan_f64();
+      z[r] = in ? (double)Pb[3 * i + 2] : sfmi_nan_f64();
+      bad |= in && !sfmi_finite3(x[r], y[r], z[r]);
     }
     int mine = 0;
 #pragma unroll 4
@@ -129,63 +127,27 @@ __global__ __launch_bounds__(PS_THREADS) void ps_score_kernel(const float* __res
       }
       mine = lane == hh ? cnt : mine;
     }
-    wc[w][lane] = mine;
-    __syncthreads();
-    if (tid < PS_HT) {
-      int tot = 0;
-#pragma unroll
-      for (int v = 0; v < PS_WAVES; ++v) tot += wc[v][tid];
-      if (tot > 0) atomicAdd(count + (long long)b * H + h0 + tid, tot);   // tot > 0 only for a valid hypothesis, so h0 + tid < H
-    }
-    __syncthreads();                                           // wc is consumed before the next pass writes it
+    sfmi_commit_counts(wc, mine, count + (long long)b * H + h0);
   }
   if (blockIdx.y == 0 && __any(bad) && lane == 0) atomicOr(status + b, 2);
 }
 
-// (c, h) <- the better of the two under (larger count, then lower h)
-__device__ __forceinline__ void ps_take(int& c, int& h, int oc, int oh) {
-  const bool take = oc > c || (oc == c && oh < h);
-  c = take ? oc : c;
-  h = take ? oh : h;
-}
-
-__global__ __launch_bounds__(256) void ps_best_kernel(int H, int* __restrict__ count, int* __restrict__ best, int* __restrict__ status) {
-  __shared__ int sc[4], sh[4];
-  const int b = blockIdx.x, tid = threadIdx.x;
+__global__ __launch_bounds__(SFMI_BEST_THREADS) void ps_best_kernel(int H, int* __restrict__ count, int* __restrict__ best,
+                                                                    int* __restrict__ status) {
+  const int b = blockIdx.x;
   int* row = count + (long long)b * H;
   const bool nonfinite = (status[b] & 2) != 0;                 // set by ps_score_kernel, an earlier launch; workgroup-uniform
-  int bc = -1, bh = 0x7FFFFFFF;
-  for (int h = tid; h < H; h += 256) {
-    if (nonfinite) row[h] = -1;
-    else ps_take(bc, bh, row[h], h);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ps_take(bc, bh, __shfl_xor(bc, o, 64), __shfl_xor(bh, o, 64));
-  if ((tid & 63) == 0) {
-    sc[tid >> 6] = bc;
-    sh[tid >> 6] = bh;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int v = 1; v < 4; ++v) ps_take(bc, bh, sc[v], sh[v]);
+  if (nonfinite)                                               // a lane reads back below what it wrote itself: no count is >= 0
+    for (int h = threadIdx.x; h < H; h += SFMI_BEST_THREADS) row[h] = -1;
+  int bc, bh;
+  sfmi_best_of_row(row, H, bc, bh);
+  if (threadIdx.x == 0) {
     best[b] = bc >= 0 ? bh : -1;
     status[b] = nonfinite ? 2 : (bc >= 0 ? 0 : 1);
   }
 }
 
 // ---- plane refit --------------------------------------------------------------------------------------------------------------------
-
-// the workgroup's sum in every lane: wave_sum_f64, then the 16 wave sums through the same xor tree.  red: RF_WAVES doubles.
-__device__ __forceinline__ double rf_block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();                                             // the previous use of red is over
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = red[threadIdx.x & (RF_WAVES - 1)];
-#pragma unroll
-  for (int o = RF_WAVES / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  return t;
-}
 
 __global__ __launch_bounds__(RF_THREADS) void rf_kernel(const float* __restrict__ P, const long long* __restrict__ off,
                                                         const int* __restrict__ triples, const int* __restrict__ best,
@@ -225,8 +187,8 @@ __global__ __launch_bounds__(RF_THREADS) void rf_kernel(const float* __restrict_
       sx += x; sy += y; sz += z; sc += 1.0;
     }
   }
-  sx = rf_block_sum(sx, red); sy = rf_block_sum(sy, red); sz = rf_block_sum(sz, red);
-  sc = rf_block_sum(sc, red);                                  // whole numbers below 2^31: exact in f64
+  sx = sfmi_block_sum_f64<RF_WAVES>(sx, red); sy = sfmi_block_sum_f64<RF_WAVES>(sy, red); sz = sfmi_block_sum_f64<RF_WAVES>(sz, red);
+  sc = sfmi_block_sum_f64<RF_WAVES>(sc, red);                  // whole numbers below 2^31: exact in f64
   const int cnt = (int)sc;
   if (!refit) {                                                // the seed's own mask is the result
     if (tid == 0) n_in[b] = cnt;
@@ -234,7 +196,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_kernel(const float* __restrict_
   }
   if (cnt < 3) {                                               // workgroup-uniform
     for (long long i = tid; i < n; i += RF_THREADS) mask[i] = 0;
-    if (tid < 4) plane[4 * b + tid] = seg_nan();
+    if (tid < 4) plane[4 * b + tid] = sfmi_nan_f64();
     if (tid == 0) n_in[b] = 0;
     return;
   }
@@ -247,10 +209,11 @@ __global__ __launch_bounds__(RF_THREADS) void rf_kernel(const float* __restrict_
       a00 += x * x; a01 += x * y; a02 += x * z; a11 += y * y; a12 += y * z; a22 += z * z;
     }
   }
-  a00 = rf_block_sum(a00, red) / sc; a01 = rf_block_sum(a01, red) / sc; a02 = rf_block_sum(a02, red) / sc;
-  a11 = rf_block_sum(a11, red) / sc; a12 = rf_block_sum(a12, red) / sc; a22 = rf_block_sum(a22, red) / sc;
+  a00 = sfmi_block_sum_f64<RF_WAVES>(a00, red) / sc; a01 = sfmi_block_sum_f64<RF_WAVES>(a01, red) / sc;
+  a02 = sfmi_block_sum_f64<RF_WAVES>(a02, red) / sc; a11 = sfmi_block_sum_f64<RF_WAVES>(a11, red) / sc;
+  a12 = sfmi_block_sum_f64<RF_WAVES>(a12, red) / sc; a22 = sfmi_block_sum_f64<RF_WAVES>(a22, red) / sc;
   double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;   // v[row][column]
-  for (int sweep = 0; sweep < KNN_JACOBI_SWEEPS; ++sweep) {
+  for (int sweep = 0; sweep < SFMI_JACOBI_SWEEPS; ++sweep) {
     jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);   // (0, 1), third axis 2
     jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);   // (0, 2), third axis 1
     jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);   // (1, 2), third axis 0
@@ -282,7 +245,7 @@ __global__ __launch_bounds__(RF_THREADS) void rf_kernel(const float* __restrict_
     mask[i] = in ? 1 : 0;
     m += in ? 1 : 0;
   }
-  const double mt = rf_block_sum((double)m, red);
+  const double mt = sfmi_block_sum_f64<RF_WAVES>((double)m, red);
   if (tid == 0) {
     plane[4 * b] = ex; plane[4 * b + 1] = ey; plane[4 * b + 2] = ez; plane[4 * b + 3] = dd;
     n_in[b] = (int)mt;
@@ -364,23 +327,21 @@ __global__ void cl_flatten_kernel(const long long* __restrict__ off, int B, long
   sfmi_uf_store(parent + i, cur);
 }
 
-inline unsigned seg_grid(long long n) { return (unsigned)(n < 1 ? 1 : (n > SEG_MAX_GRID ? SEG_MAX_GRID : n)); }
-
 }  // namespace
 
 extern "C" {
 
 int sfmi_plane_score_f32(const float* P, const long long* off, const int* triples, int B, long long N, int H, long long max_n,
                          double thr2, int* count, int* best, int* status, void* stream) {
-  if (B <= 0 || B > (int)SEG_MAX_GRID || N < 0 || H < 1 || cdiv(H, PS_HT) > SEG_MAX_GRID || max_n < 0 || max_n >= (1ll << 31) ||
+  if (B <= 0 || B > (int)SFMI_MAX_GRID || N < 0 || H < 1 || cdiv(H, PS_HT) > SFMI_MAX_GRID || max_n < 0 || max_n >= (1ll << 31) ||
       !(thr2 >= 0.0) || !off || !triples || !count || !best || !status || (N > 0 && !P))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(ps_init_kernel, dim3(blocks256((long long)B * H)), dim3(256), 0, st, P, off, triples, B, H, count, status);
   if (N > 0)
-    hipLaunchKernelGGL(ps_score_kernel, dim3(seg_grid(cdiv(max_n, PS_CHUNK)), (unsigned)cdiv(H, PS_HT), (unsigned)B), dim3(PS_THREADS), 0,
+    hipLaunchKernelGGL(ps_score_kernel, dim3(sfmi_grid_cap(cdiv(max_n, PS_CHUNK)), (unsigned)cdiv(H, PS_HT), (unsigned)B), dim3(PS_THREADS), 0,
                        st, P, off, triples, H, thr2, count, status);
-  hipLaunchKernelGGL(ps_best_kernel, dim3((unsigned)B), dim3(256), 0, st, H, count, best, status);
+  hipLaunchKernelGGL(ps_best_kernel, dim3((unsigned)B), dim3(SFMI_BEST_THREADS), 0, st, H, count, best, status);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -397,12 +358,12 @@ int sfmi_plane_refit_f32(const float* P, const long long* off, const int* triple
 }
 
 int sfmi_cluster_f32(const float* P, const long long* off, int B, long long N, long long max_n, float r2, int* root, void* stream) {
-  if (B <= 0 || B > (int)SEG_MAX_GRID || N < 0 || max_n < 0 || max_n >= (1ll << 31) || !off) return SFMI_EINVAL;
+  if (B <= 0 || B > (int)SFMI_MAX_GRID || N < 0 || max_n < 0 || max_n >= (1ll << 31) || !off) return SFMI_EINVAL;
   if (N == 0) return SFMI_OK;
   if (!P || !root) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(cl_init_kernel, dim3(blocks256(N)), dim3(256), 0, st, off, B, N, root);
-  const unsigned nb = seg_grid(cdiv(max_n, CL_IB));
+  const unsigned nb = sfmi_grid_cap(cdiv(max_n, CL_IB));
   hipLaunchKernelGGL(cl_hook_kernel, dim3(nb, nb, (unsigned)B), dim3(CL_THREADS), 0, st, P, off, r2, root);
   hipLaunchKernelGGL(cl_flatten_kernel, dim3(blocks256(N)), dim3(256), 0, st, off, B, N, root);
   SFMI_CHECK_LAUNCH();

@@ -1,8 +1,10 @@
-// Shared pieces of the mesh tools: what csrc/pointdist.hip, meshsdf.hip, hpr.hip, iso_sparse.hip, simplify.hip,
-// components.hip and morph.hip all need for ragged batches.  A ragged batch is B sets stored back to back with (B+1) nondecreasing
-// offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b with off[b] <= x < off[b+1].  Everything here is
-// inlined into its caller; apart from jacobi_rot below none of it holds a multiply-add, and a caller's `#pragma clang fp contract(off)`
-// comes after this include, so it changes nothing in here.
+// Shared pieces of the mesh and scan tools: what csrc/pointdist.hip, meshsdf.hip, hpr.hip, iso_sparse.hip, simplify.hip,
+// components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip and global_register.hip need
+// for ragged batches (the split nearest-neighbour search of the scan tools is sfmi_search.h, which includes this file).  A ragged batch
+// is B sets stored back to back with (B+1) nondecreasing offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b
+// with off[b] <= x < off[b+1].  Everything here is inlined into its caller.  A caller's `#pragma clang fp contract(off)` comes after
+// this include, so it changes nothing in here.  Two functions below have a product feeding a sum: sfmi_pose_row, whose callers all
+// compile without contraction, carries `#pragma clang fp contract(off)` in its body; jacobi_rot is compiled under the build's setting.
 #pragma once
 #include "sfmi_common.h"
 
@@ -10,7 +12,8 @@
 // Two forms of one function: for nondecreasing offsets with off[0] <= x < off[B] both return the largest b in [0, B) with
 // off[b] <= x, so empty sets are skipped.
 //   sfmi_owner     binary search: ~log2 B dependent loads.  Used by the kernels over point sets, queries, faces and query blocks of
-//                  pointdist / meshsdf / hpr (64-bit offsets) and over the points of morph (32-bit offsets).
+//                  pointdist / meshsdf / hpr and of the scan tools knn / downsample / poisson / segment / register / features
+//                  (64-bit offsets) and over the points of morph (32-bit offsets).
 //   sfmi_shape_of  linear count: B - 1 independent loads at wave-uniform addresses, no branch.  Used by the kernels over mesh
 //                  vertices, faces, cells and bitmap words of components / simplify / iso_sparse, whose batches are a few shapes.
 // They are different code, so which kernel runs which is part of that kernel's recorded timings: switch one only with a measurement.
@@ -85,6 +88,22 @@ __device__ __forceinline__ double wave_max_f64(double v) {
   return v;
 }
 
+// the sum over a workgroup of WAVES waves (a power of two; 16 in orient_kernel, rf_kernel and greg_refit_kernel) in every lane:
+// wave_sum_f64, then the WAVES wave sums through the same xor tree.  red: WAVES doubles of LDS; every lane of the workgroup calls.
+// NOT the order of poisson.hip's cg_block_sum ((r0 + r1) + (r2 + r3)) nor of icp_accumulate_kernel (the waves in order): each of the
+// three is a different f64 rounding fixed by its numpy restatement, so those two stay where they are.
+template <int WAVES>
+__device__ __forceinline__ double sfmi_block_sum_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  __syncthreads();                                             // the previous use of red is over
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = red[threadIdx.x & (WAVES - 1)];
+#pragma unroll
+  for (int o = WAVES / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  return t;
+}
+
 // splitmix64 finalizer: the counter hash of the mesh samplers
 __device__ __forceinline__ unsigned long long sfmi_mix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -94,8 +113,8 @@ __device__ __forceinline__ unsigned long long sfmi_mix64(unsigned long long x) {
 }
 
 // ---- symmetric 3x3 eigen-solver in f64: the cyclic Jacobi step of knn.hip's normals and segment.hip's plane refit -------------------
-// (the one piece of this header with products feeding sums: it is compiled under the build's contraction setting in every includer,
-// because each includer's `#pragma clang fp contract(off)` comes after this include)
+// (products feeding sums, compiled under the build's contraction setting in every includer, because each includer's
+// `#pragma clang fp contract(off)` comes after this include)
 // one Jacobi rotation of the symmetric 3x3 matrix in the plane (p, q), r the third axis: zeroes a_pq.  v*p / v*q: columns p and q of
 // the accumulated eigenvector matrix.  Branch-free: a_pq == 0 is the identity rotation.
 __device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
@@ -115,7 +134,69 @@ __device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq
   v0p = a0; v0q = b0; v1p = a1; v1q = b1; v2p = a2; v2q = b2;
 }
 
-constexpr int KNN_JACOBI_SWEEPS = 8;             // a 3x3 in f64 is converged to the last bit after 5 or 6
+// sweeps of jacobi_rot (knn.hip, segment.hip) and of global_register.hip's one-sided gr_rot: no data-dependent trip count
+constexpr int SFMI_JACOBI_SWEEPS = 8;            // a 3x3 in f64 is converged to the last bit after 5 or 6
+
+// ---- points and poses of the scan tools ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sfmi_nan_f64() { return __longlong_as_double(0x7FF8000000000000ll); }
+
+template <typename T>
+__device__ __forceinline__ bool sfmi_finite3(T x, T y, T z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+__device__ __forceinline__ bool sfmi_finite3(const float* __restrict__ p) { return sfmi_finite3(p[0], p[1], p[2]); }
+
+// x' = f32(((r0 x + r1 y) + r2 z) + t) in f64, the f32 point widened first; T: one row of the pose (4 doubles).  Every product and sum
+// is rounded on its own, whatever the build's setting: the numpy restatements (tests/icp_ref.py, global_reg_ref.py) fix these bits.
+__device__ __forceinline__ float sfmi_pose_row(const double* __restrict__ T, double x, double y, double z) {
+#pragma clang fp contract(off)
+  return (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+}
+
+// ---- RANSAC over hypotheses (segment.hip's planes, global_register.hip's poses): integer counts, so the result is a function of the input
+constexpr int SFMI_HT = 64;                      // hypotheses per tile: lane h of a wave keeps the count of hypothesis h
+constexpr int SFMI_BEST_THREADS = 256;
+
+// the end of a score kernel's pass over a tile of SFMI_HT hypotheses: `mine` is the count of the wave's points for hypothesis `lane`;
+// the WAVES wave counts are added and one atomicAdd per hypothesis with a positive total reaches tile_count[h] (a positive total
+// belongs to a valid hypothesis, so that slot exists).  Every lane of the workgroup calls; wc is free again on return.
+template <int WAVES>
+__device__ __forceinline__ void sfmi_commit_counts(int (&wc)[WAVES][SFMI_HT], int mine, int* __restrict__ tile_count) {
+  const int tid = threadIdx.x;
+  wc[tid >> 6][tid & 63] = mine;
+  __syncthreads();
+  if (tid < SFMI_HT) {
+    int tot = 0;
+#pragma unroll
+    for (int v = 0; v < WAVES; ++v) tot += wc[v][tid];
+    if (tot > 0) atomicAdd(tile_count + tid, tot);
+  }
+  __syncthreads();                                             // wc is consumed before the next pass writes it
+}
+
+// (c, h) <- the better of the two under (larger count, then lower h)
+__device__ __forceinline__ void sfmi_take(int& c, int& h, int oc, int oh) {
+  const bool take = oc > c || (oc == c && oh < h);
+  c = take ? oc : c;
+  h = take ? oh : h;
+}
+
+// the arg max of row[0 .. H) under sfmi_take, by a workgroup of SFMI_BEST_THREADS: per lane, the wave's butterfly, the four waves in
+// order.  (bc, bh) is the result in thread 0 only; bc = -1 when no count is >= 0.  Every lane of the workgroup calls.
+__device__ __forceinline__ void sfmi_best_of_row(const int* row, int H, int& bc, int& bh) {
+  __shared__ int sc[SFMI_BEST_THREADS / 64], sh[SFMI_BEST_THREADS / 64];
+  const int tid = threadIdx.x;
+  bc = -1;
+  bh = 0x7FFFFFFF;
+  for (int h = tid; h < H; h += SFMI_BEST_THREADS) sfmi_take(bc, bh, row[h], h);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sfmi_take(bc, bh, __shfl_xor(bc, o, 64), __shfl_xor(bh, o, 64));
+  if ((tid & 63) == 0) {
+    sc[tid >> 6] = bc;
+    sh[tid >> 6] = bh;
+  }
+  __syncthreads();
+  if (tid == 0)
+    for (int v = 1; v < SFMI_BEST_THREADS / 64; ++v) sfmi_take(bc, bh, sc[v], sh[v]);
+}
 
 // ---- per-shape mesh validation: flag bits that kernels OR into flags[b], and the status code they stand for ------------------------
 constexpr int SFMI_MESH_NO_VERTS = 1, SFMI_MESH_BAD_INDEX = 2, SFMI_MESH_NON_FINITE = 4;   // the status is the lowest one set
@@ -127,3 +208,5 @@ __device__ __forceinline__ int sfmi_mesh_status(int flags) {
 __host__ __device__ inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }                    // workspace sections start on 256 bytes
 inline unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }         // workgroups of 256 threads over n items
+constexpr unsigned SFMI_MAX_GRID = 65535;                                              // the y and z limits of a grid
+inline unsigned sfmi_grid_cap(long long n) { return (unsigned)(n < 1 ? 1 : (n > SFMI_MAX_GRID ? SFMI_MAX_GRID : n)); }   // for grid-stride loops

@@ -43,7 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import excl_at, host_offsets, on_device, point_sets, points_arg
+from ._ragged import check_count, check_nonneg, excl_at, host_offsets, on_device, point_sets, points_arg, set_ids
 
 METRICS = ("point", "plane")
 N_SUMS = 29
@@ -78,12 +78,6 @@ def _pose44(pose12):
     return out
 
 
-def _check_max_dist(v, what, name="max_dist"):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
-        raise L.SfmiError(f"{what}: {name} must be a finite number >= 0, got {v!r}")
-    return float(v)
-
-
 def _per_pair(v, B, what, name, conv, expect):
     """one value for every pair, or a list / tuple of B values -> a list of B converted values"""
     vals = list(v) if isinstance(v, (list, tuple)) else [v] * B
@@ -93,12 +87,6 @@ def _per_pair(v, B, what, name, conv, expect):
     if any(x is None for x in out):
         raise L.SfmiError(f"{what}: {name} must be {expect}, got {v!r}")
     return out
-
-
-def _check_int(v, what, name, lo):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < 2 ** 31:
-        raise L.SfmiError(f"{what}: {name} must be an integer in [{lo}, 2^31), got {v!r}")
-    return int(v)
 
 
 def _check_tol(v, what, name):
@@ -146,7 +134,7 @@ class _Icp:
         s, t = s.reshape(-1, 3), t.reshape(-1, 3)
         metrics = _per_pair(metric, B, what, "metric", lambda m: m if isinstance(m, str) and m in METRICS else None,
                             f"one of {METRICS}")
-        dists = _per_pair(max_dist, B, what, "max_dist", lambda v: _check_max_dist(v, what), "a finite number >= 0")
+        dists = _per_pair(max_dist, B, what, "max_dist", lambda v: check_nonneg(v, what, "max_dist"), "a finite number >= 0")
         maxd2 = np.array([np.float32(d ** 2) for d in dists], np.float32)         # rounded as radius_outlier_mask_dev rounds its radius
         n = None
         if "plane" in metrics:
@@ -231,8 +219,8 @@ def icp_dev(source, target, s_off=None, t_off=None, max_dist=None, metric="point
     -> pose (B,4,4) f64, fitness (B,) f64, rmse (B,) f64, iterations (B,) int32, status (B,) int32 (the module's table), all on the
     device.  The result is a function of the input: bit-identical from run to run, in any batch, for any check_every."""
     what = "icp_dev"
-    max_iter = _check_int(max_iter, what, "max_iter", 0)
-    check_every = _check_int(check_every, what, "check_every", 1)
+    max_iter = check_count(max_iter, what, "max_iter", 0)
+    check_every = check_count(check_every, what, "check_every", 1)
     rel_fitness, rel_rmse = _check_tol(rel_fitness, what, "rel_fitness"), _check_tol(rel_rmse, what, "rel_rmse")
     st = _Icp(what, source, target, s_off, t_off, max_dist, metric, target_normals, init)
     st.run(max_iter, rel_fitness, rel_rmse, check_every)
@@ -258,7 +246,7 @@ def icp_multiscale_dev(source, target, s_off=None, t_off=None, voxels=(0.04, 0.0
     if len(max_dists) != len(voxels):
         raise L.SfmiError(f"{what}: max_dists must have one entry per level ({len(voxels)}), got {len(max_dists)}")
     for m in max_dists:
-        _check_max_dist(m, what, "max_dists")
+        check_nonneg(m, what, "max_dists")
     s, so, _ = point_sets(source, s_off, f"{what} source")
     t, to, _ = point_sets(target, t_off, f"{what} target")
     if len(so) != len(to):
@@ -408,7 +396,7 @@ def match_features_dev(fs, ft, s_off=None, t_off=None, mutual=True, splits=None,
     idx, d2 = _feature_nn(fs, ft, so, to, S, q)
     N = fs.shape[0]
     sod, tod = torch.from_numpy(so).to(dev), torch.from_numpy(to).to(dev)
-    sid = torch.repeat_interleave(torch.arange(len(so) - 1, device=dev), torch.from_numpy(np.diff(so)).to(dev), output_size=N)
+    sid = set_ids(so, dev)
     local = torch.arange(N, device=dev) - sod[sid]
     keep = idx >= 0
     if mutual and N and ft.shape[0]:
@@ -524,7 +512,7 @@ def _check_similarity(v, what):
 
 
 def _maxd2(max_dist, what):
-    return float(np.float32(_check_max_dist(max_dist, what) ** 2))
+    return float(np.float32(check_nonneg(max_dist, what, "max_dist") ** 2))
 
 
 def hypothesis_poses_dev(source, target, s_off=None, t_off=None, corr=None, c_off=None, triples=None, similarity=0.9):
@@ -555,10 +543,9 @@ def score_poses_dev(source, target, s_off=None, t_off=None, corr=None, c_off=Non
 
 
 def _ransac(what, a, max_dist, hypotheses, seed, triples, similarity, refit, extra_bad=None):
-    from .scan import _check_count
     maxd2 = _maxd2(max_dist, what)
     sim = _check_similarity(similarity, what)
-    tr = (correspondence_hypotheses(np.diff(a.co), _check_count(hypotheses, what, "hypotheses"), seed) if triples is None
+    tr = (correspondence_hypotheses(np.diff(a.co), check_count(hypotheses, what, "hypotheses"), seed) if triples is None
           else _triples_arg(triples, a.B, what))
     dev = a.to_device(what, *([tr] if isinstance(tr, torch.Tensor) else []))
     trd = _triples_dev(tr, dev)
@@ -631,7 +618,7 @@ def global_registration_dev(source, target, s_off=None, t_off=None, voxel=None, 
         if voxel is None:
             raise L.SfmiError(f"{what}: max_dist is needed when voxel is None")
         max_dist = 1.5 * voxel
-    _check_max_dist(max_dist, what)
+    check_nonneg(max_dist, what, "max_dist")
     _check_k(normals_k, what)
     _check_k(feature_k, what)
     _radius_arg(feature_radius, what, "feature_radius")

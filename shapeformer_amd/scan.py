@@ -36,7 +36,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import excl_at, host_offsets, on_device, point_sets, points_arg, run_starts, sorted_runs
+from ._ragged import (check_count, check_nonneg, excl_at, host_offsets, on_device, point_sets, points_arg, run_starts, set_ids,
+                      sorted_runs)
 
 MAX_K = 64
 
@@ -368,23 +369,11 @@ def _mix64(x):
         return x ^ (x >> np.uint64(31))
 
 
-def _check_count(v, what, name, lo=1):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < 2 ** 31:
-        raise L.SfmiError(f"{what}: {name} must be an integer in [{lo}, 2^31), got {v!r}")
-    return int(v)
-
-
-def _check_nonneg(v, what, name):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
-        raise L.SfmiError(f"{what}: {name} must be a finite number >= 0, got {v!r}")
-    return float(v)
-
-
 def plane_hypotheses(sizes, H, seed=0):
     """The RANSAC draws of segment_plane_dev: (B,H,3) int32 on the host, index = sfmi_mix64((seed << 40) + 4 h + slot) mod n_b (uint64
     arithmetic): a function of (seed, h, slot, n) and not of b, so a batch draws what per-set calls draw.  Repeated indices are not
     redrawn: the kernel marks such a hypothesis invalid.  A set of no points gets index 0, which lies outside it."""
-    H = _check_count(H, "plane_hypotheses", "H")
+    H = check_count(H, "plane_hypotheses", "H")
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 23:
         raise L.SfmiError(f"plane_hypotheses: seed must be an integer in [0, 2^23), got {seed!r}")
     n = np.asarray(sizes, np.int64).reshape(-1)
@@ -397,11 +386,6 @@ def plane_hypotheses(sizes, H, seed=0):
 
 def _max_n(o):
     return int(np.diff(o).max()) if len(o) > 1 else 0
-
-
-def _set_ids(o, dev):
-    """(N,) int64: the set of every point"""
-    return torch.repeat_interleave(torch.arange(len(o) - 1, device=dev), torch.from_numpy(np.diff(o)).to(dev), output_size=int(o[-1]))
 
 
 def _up_arg(up, B, what):
@@ -454,13 +438,13 @@ def segment_plane_dev(points, off=None, threshold=0.01, hypotheses=1024, seed=0,
     component of largest magnitude is positive.  A set without a winner, or whose winner has fewer than 3 inliers: plane NaN, mask 0,
     n_in 0.  Bit-identical from run to run; a set's results depend on that set alone."""
     what = "segment_plane_dev"
-    thr = _check_nonneg(threshold, what, "threshold")
+    thr = check_nonneg(threshold, what, "threshold")
     x, o, shape = point_sets(points, off, what)
     B, N = len(o) - 1, x.shape[0]
     if B > 65535 or (np.diff(o) >= 2 ** 31).any():
         raise L.SfmiError(f"{what}: at most 65535 sets, each below 2^31 points")
     if triples is None:
-        tr = plane_hypotheses(np.diff(o), _check_count(hypotheses, what, "hypotheses"), seed)
+        tr = plane_hypotheses(np.diff(o), check_count(hypotheses, what, "hypotheses"), seed)
     else:
         tr = triples
         if not isinstance(tr, torch.Tensor):
@@ -501,7 +485,7 @@ def refit_plane_dev(points, off=None, plane=None, threshold=0.01, up=None):
     -> plane (B,4) f64, inlier (N,) uint8 ((B,M) for a batch), n_in (B,) int32.  A seed that is not finite or has n = 0, or fewer than
     3 seed inliers: plane NaN, mask 0, n_in 0.  Calling it on its own output iterates the fit."""
     what = "refit_plane_dev"
-    thr = _check_nonneg(threshold, what, "threshold")
+    thr = check_nonneg(threshold, what, "threshold")
     x, o, shape = point_sets(points, off, what)
     B, N = len(o) - 1, x.shape[0]
     if isinstance(plane, torch.Tensor):
@@ -533,10 +517,10 @@ def remove_planes_dev(points, off=None, threshold=0.01, max_planes=1, min_ratio=
     Between two rounds the per-set counts are read back (one synchronisation per round after the first) to cut the compacted batch;
     max_planes = 1 reads nothing back."""
     what = "remove_planes_dev"
-    _check_nonneg(threshold, what, "threshold")
-    max_planes = _check_count(max_planes, what, "max_planes")
-    min_ratio = _check_nonneg(min_ratio, what, "min_ratio")
-    _check_count(hypotheses, what, "hypotheses")
+    check_nonneg(threshold, what, "threshold")
+    max_planes = check_count(max_planes, what, "max_planes")
+    min_ratio = check_nonneg(min_ratio, what, "min_ratio")
+    check_count(hypotheses, what, "hypotheses")
     x, o, shape = point_sets(points, off, what)
     B, N = len(o) - 1, x.shape[0]
     _up_arg(up, B, what)
@@ -553,7 +537,7 @@ def remove_planes_dev(points, off=None, threshold=0.01, max_planes=1, min_ratio=
         active = active & (n_in >= 3) & (n_in.double() >= need)
         planes[:, r] = torch.where(active[:, None], plane, planes[:, r])
         taken += active.to(torch.int32)
-        sid = _set_ids(co, dev)
+        sid = set_ids(co, dev)
         drop = inl.bool() & active[sid]
         keep[idx[drop]] = 0
         if r + 1 == max_planes:
@@ -592,7 +576,7 @@ def euclidean_clusters_dev(points, off=None, radius=None, min_points=1, return_r
     what = "euclidean_clusters_dev"
     if radius is None or isinstance(radius, bool) or not float(radius) >= 0:
         raise L.SfmiError(f"{what}: radius must be >= 0, got {radius!r}")
-    min_points = _check_count(min_points, what, "min_points")
+    min_points = check_count(min_points, what, "min_points")
     x, o, shape = point_sets(points, off, what)
     B, N = len(o) - 1, x.shape[0]
     if B > 65535 or (np.diff(o) >= 2 ** 31).any():
@@ -604,7 +588,7 @@ def euclidean_clusters_dev(points, off=None, radius=None, min_points=1, return_r
         out = (root.clone(), torch.empty(0, device=dev, dtype=torch.int32), np.zeros(B + 1, np.int64))
         return out + (root,) if return_root else out
     od = torch.from_numpy(o).to(dev)
-    sid = _set_ids(o, dev)
+    sid = set_ids(o, dev)
     g = root.long() + od[sid]                                                   # the root as a batch index
     size_at = torch.bincount(g, minlength=N)                                    # at a root: its cluster's size; elsewhere 0
     roots = torch.nonzero(size_at >= min_points)[:, 0]                          # ascending: (set, root)
@@ -678,7 +662,7 @@ def isolate_object_dev(points, off=None, plane_threshold=0.01, cluster_radius=0.
         raise L.SfmiError(f"{what}: normalize must be None or one of {NORMALIZE_MODES}, got {normalize!r}")
     if cluster_radius is None or isinstance(cluster_radius, bool) or not float(cluster_radius) >= 0:
         raise L.SfmiError(f"{what}: cluster_radius must be >= 0, got {cluster_radius!r}")
-    _check_count(min_points, what, "min_points")
+    check_count(min_points, what, "min_points")
     x, o, shape = point_sets(points, off, what)
     B = len(o) - 1
     keep, planes, taken = remove_planes_dev(x, o, plane_threshold, max_planes, min_ratio, hypotheses, seed)
@@ -687,7 +671,7 @@ def isolate_object_dev(points, off=None, plane_threshold=0.01, cluster_radius=0.
     rest, ro, ridx = _compact(xf, o, keep)
     plane0 = planes[:, 0].clone()
     if rest.shape[0]:
-        sid = _set_ids(ro, dev)
+        sid = set_ids(ro, dev)
         sd = (rest.double() * plane0[sid, :3]).sum(1) + plane0[sid, 3]
         side = torch.zeros(B, device=dev, dtype=torch.float64).index_add_(0, sid, torch.nan_to_num(sd))
         plane0 = torch.where((side < 0)[:, None], -plane0, plane0)
@@ -700,7 +684,7 @@ def isolate_object_dev(points, off=None, plane_threshold=0.01, cluster_radius=0.
     mask = torch.zeros(xf.shape[0], device=dev, dtype=torch.uint8)
     mask[ridx[kidx]] = 1
     if kept.shape[0]:
-        kept = torch.einsum("nij,nj->ni", rot[_set_ids(k_off, dev)], kept.double()).float()
+        kept = torch.einsum("nij,nj->ni", rot[set_ids(k_off, dev)], kept.double()).float()
     if normalize is not None:
         kw = {} if scale is None else {"scale": scale}
         kept = torch.cat([normalize_scan(kept[int(k_off[b]):int(k_off[b + 1])], normalize, **kw) if k_off[b + 1] > k_off[b]
