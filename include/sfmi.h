@@ -1021,6 +1021,56 @@ int sfmi_greg_refit_f32(const float* src, const float* tgt, const long long* sof
                         const long long* coff, const double* poses, const int* best, int B, int H, long long C, float maxd2, int refit,
                         int* status, double* pose, unsigned char* inlier, int* n_in, double* sums, void* stream);
 
+/* ---- Multiway registration: information matrices and pose-graph optimisation (csrc/posegraph.hip).  The interface of
+ *      Open3D's get_information_matrix_from_point_clouds and global_optimization (Levenberg-Marquardt, a line process over the
+ *      uncertain edges), not their bits: the statement below is the specification, restated in numpy in tests/posegraph_ref.py.  The
+ *      reference has no such step.
+ * Information matrix of a registered pair.  Pairs, poses and correspondences as in the ICP section above: idx (N) int32 / d2 (N) f32 are
+ * what an evaluation under pose (B,12) f64 left; the search is not repeated.  Inlier iff 0 <= idx < m_b (checked before the target
+ * point is read) and d2 <= maxd2[b] (f32, per pair).  With q = the inlier's f32 target point widened to f64 and G = [-[q]x | I]:
+ *   info (B,6,6) f64 = sum G^T G = [[|q|^2 I - q q^T, [q]x], [., I]], symmetric; info[5][5] = count (B) int32.
+ * Ten sums per pair - (qy^2 + qz^2), -(qx qy), -(qx qz), (qx^2 + qz^2), -(qy qz), (qx^2 + qy^2), qx, qy, qz, 1 - every product and sum
+ * rounded on its own, in the order of the ICP sums: a lane's 4 points ascending within chunks of sfmi_icp_chunk() points that start at
+ * the set's first point (sfmi_pg_chunk() is the same number), wave_sum_f64, the 4 waves in order, then the chunk partials in ascending
+ * order by one wave per pair.  No float atomics: a batch equals per-pair calls bit for bit.  A pair with a non-finite source or target
+ * coordinate or pose entry gets info = 0, count = 0, flag[b] = 1 (else 0).  bad (B) int32 scratch; part (B ceil(max_n / chunk) 10) f64. */
+int sfmi_pg_chunk(void);
+int sfmi_pg_information_f32(const float* src, const float* tgt, const long long* soff, const long long* toff, const double* pose,
+                            const int* idx, const float* d2, const float* maxd2, int B, long long N, long long M, long long max_n,
+                            long long max_m, int* bad, double* part, double* info, int* count, int* flag, void* stream);
+/* Pose-graph optimisation for a ragged batch of graphs: noff (Bg+1) / eoff (Bg+1) int64 [device] cut the nodes and edges; at most
+ * sfmi_pg_max_nodes() = 32 nodes and sfmi_pg_max_edges() = 496 edges per graph; max_s = the largest node count of the batch (it sizes
+ * the LDS and the workspaces).  X (S,12) f64 [in / out]: node poses, row-major [R | t], scan frame -> frame of the graph's node 0,
+ * which is held fixed.  Edge e: src, tgt (E) int32 local node indices, src != tgt; T (E,12) f64 with p_tgt = T p_src; Lam (E,36) f64
+ * its information matrix (symmetric; used as given); uncertain (E) int32 (a loop closure); alive (E) int32.  mu (Bg) f64
+ * [device]: the line-process weight of every graph, <= 0: off.
+ * Residual of an edge: D = T^-1 X_tgt^-1 X_src, r = (w, v), v = t_D, w = f vee(R_D - R_D^T) with theta = atan2(|vee| / 2, (tr R_D - 1)
+ * / 2), f = theta / (2 sin theta), below theta = 1e-4: (1 + theta^2/6 + 7 theta^4/360) / 2; theta > 3.1 on an alive edge ends the graph
+ * with status 3.  A node moves as an ICP pose does: R <- dR R, t <- dR t + dv, dR = the Rodrigues formula of dw stated above.  Jacobians:
+ * A = T^-1 X_tgt^-1, Jl^-1(w) = I - [w]x / 2 + k [w]x^2, k = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), below 1e-4: 1/12 +
+ * theta^2/720; J_src = [[Jl^-1 R_A, 0], [-R_A [t_src]x, R_A]], J_tgt = -J_src.  Line process: q_e = r^T Lam r; l_e = (mu / (mu + q_e))^2
+ * for an alive uncertain edge when mu > 0, else 1.  Cost F = sum l_e q_e + sum over those uncertain edges of mu (sqrt(l_e) - 1)^2, over
+ * the alive edges (lane i of one wave adds edges 8 i .. 8 i + 7 in ascending order, then the xor butterfly).  Normal equations over the
+ * 6 (S - 1) free variables: H = sum l_e J^T Lam J, g = -sum l_e J^T Lam r, every entry summed over the alive edges in ascending edge
+ * index; no float atomics.  Loop: lambda = 1e-5 max diag H at the first iteration; (H + lambda I) delta = g by Cholesky in f64; the
+ * step is tried: F_new < F accepts it and lambda <- max(lambda / 3, 1e-12); otherwise lambda <- 2 lambda and the same H is solved
+ * again; lambda > 1e12 ends the graph with status 3.  An accepted step with max |delta| < tol ends it with status 0; so does a step
+ * with max |delta| < tol that does not lower F (a fixed point: the poses stay).  max_iter outer iterations end it with status 1.
+ * status (Bg) int32: 0 converged, 1 max_iter reached, 2 a node that no chain of alive edges joins to node 0 (label propagation on the
+ * device; the poses stay as given), 3 a pivot that is not positive and finite, the lambda overflow or the theta limit (the poses of
+ * the last accepted step), 4 a non-finite pose, transform, information entry, mu or tol, an edge index outside its graph, src = tgt,
+ * or sizes beyond the caps (X untouched, l = 0, cost = 0).  Outputs: X; l (E) f64 and cost (Bg) f64 under the returned poses;
+ * iterations (Bg) int32 outer iterations begun; and of the last solve, for tests, H (Bg, nmax (nmax + 1) / 2) f64 the packed lower
+ * triangle row-major (entry (i, j), j <= i, at i (i + 1) / 2 + j; nmax = 6 (max_s - 1)), g and delta (Bg, nmax) f64, lam (Bg) f64 the
+ * lambda it used.  ework (E,27) f64: the edges' blocks.  One workgroup per graph, one launch: a graph's result depends on that graph
+ * alone, bit for bit, and two runs give the same bits. */
+int sfmi_pg_max_nodes(void);
+int sfmi_pg_max_edges(void);
+int sfmi_pg_optimize_f64(const long long* noff, const long long* eoff, int Bg, int max_s, double* X, const int* src, const int* tgt,
+                         const double* T, const double* Lam, const int* uncertain, const int* alive, const double* mu, int max_iter,
+                         double tol, double* l, double* cost, int* iterations, int* status, double* ework, double* H, double* g,
+                         double* delta, double* lam, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,12 @@ PROTOTYPES = {
     "sfmi_greg_poses_f32": (i32, [c_ptr] * 7 + [i32, i32, i64, C.c_double] + [c_ptr] * 3),
     "sfmi_greg_score_f32": (i32, [c_ptr] * 9 + [i32, i32, i64, C.c_float] + [c_ptr] * 4),
     "sfmi_greg_refit_f32": (i32, [c_ptr] * 8 + [i32, i32, i64, C.c_float, i32] + [c_ptr] * 6),
+    # multiway registration: information matrices, pose-graph optimisation
+    "sfmi_pg_chunk": (i32, []),
+    "sfmi_pg_information_f32": (i32, [c_ptr] * 8 + [i32, i64, i64, i64, i64] + [c_ptr] * 6),
+    "sfmi_pg_max_nodes": (i32, []),
+    "sfmi_pg_max_edges": (i32, []),
+    "sfmi_pg_optimize_f64": (i32, [c_ptr, c_ptr, i32, i32] + [c_ptr] * 8 + [i32, C.c_double] + [c_ptr] * 10),
 }
 
 

@@ -34,6 +34,19 @@ aligned beforehand - Open3D's compute_fpfh_feature and registration_ransac_based
 Its contract is stated in include/sfmi.h and restated in numpy in tests/global_reg_ref.py; its status: 0 ok, 1 no valid hypothesis,
 2 fewer than 3 inliers or a degenerate refit, 4 a non-finite value in the pair; with 1, 2, 4 the pose is the identity.
 
+Multiway registration (csrc/posegraph.hip) is for captures in which not every scan overlaps scan 0 - a ring or a chain:
+pairwise ICP along the edges of a pose graph, one information matrix per edge, and Open3D's global_optimization on the device:
+
+  information_matrix_dev(source, target, ..., max_dist, pose)      -> info (B,6,6) f64, count (B,) int32, fitness, rmse (B,) f64
+  pose_graph_optimize_dev(nodes, src, tgt, transforms, infos, ...) -> poses (S,4,4) f64, l (E,), cost, iterations, status (Bg,)
+  global_optimization_dev(..., preference, max_dist, prune)        -> poses, kept (E,) bool, l of pass one, status of both passes
+  multiway_registration_dev(clouds, offs, pairs, max_dists, ...)   -> poses (S,4,4) f64, status (S,) host int32, a dict of the edges
+  merge_scans_dev(..., multiway={...})                             -> the poses come from multiway_registration_dev
+
+Its contract is stated in include/sfmi.h and restated in numpy in tests/posegraph_ref.py; the optimiser's status: 0 converged, 1
+max_iter reached, 2 a node that no alive edge joins to node 0, 3 the damped system is not positive definite, lambda overflowed or an edge
+turned by more than 3.1 rad, 4 a non-finite input.
+
 ICP's status: 0 converged, 1 max_iter reached, 2 fewer than 3 (point) / 6 (plane) inliers, 3 the normal equations are not positive definite,
 4 a non-finite coordinate, normal or initial pose in the pair.  With 2, 3 and 4 the pose stays where it was.
 """
@@ -43,7 +56,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import check_count, check_nonneg, excl_at, host_offsets, on_device, point_sets, points_arg, set_ids
+from ._ragged import check_count, check_nonneg, excl_at, host_offsets, i32_dev, on_device, point_sets, points_arg, set_ids
 
 METRICS = ("point", "plane")
 N_SUMS = 29
@@ -648,7 +661,7 @@ def global_registration_dev(source, target, s_off=None, t_off=None, voxel=None, 
                    ransac.get("similarity", 0.9), ransac.get("refit", True), extra)[0]
 
 
-def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, **icp):
+def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, multiway=None, **icp):
     """Several partial scans of one object, each in its own frame, merged in the frame of scan 0.
 
     clouds: a list of (n_i,3) HIP tensors, or one (N,3) tensor with (S+1,) offsets `offs`.  Scans 1.. are registered onto scan 0 in one
@@ -657,9 +670,14 @@ def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, **icp):
     reported.  global_init: a dict of global_registration_dev's arguments; the pose it finds for a scan is the `init` of the ICP that
     follows, for scans that are not roughly aligned beforehand (a scan whose global status is >= 1 keeps the identity); None: the scans
     start from `init` or the identity.  -> merged (K,3) f32, poses (S,4,4) f64 (identity for scan 0), status (S,) host int32 (0 for
-    scan 0).  The statuses are read back (one synchronisation)."""
+    scan 0).  The statuses are read back (one synchronisation).
+    multiway: a dict of multiway_registration_dev's arguments (max_dists, pairs, global_init, ICP options ...): the poses come from the
+    pose graph over all pairs instead of the star onto scan 0, for captures in which not every scan overlaps scan 0; every other
+    registration argument then goes into that dict.  None: the star."""
     from .scan import voxel_downsample_dev
     what = "merge_scans_dev"
+    if multiway is not None and (not isinstance(multiway, dict) or global_init is not None or icp):
+        raise L.SfmiError(f"{what}: multiway must be a dict of multiway_registration_dev arguments; global_init and the ICP options go inside it")
     if global_init is not None and (not isinstance(global_init, dict) or "init" in icp):
         raise L.SfmiError(f"{what}: global_init must be a dict of global_registration_dev arguments and replaces init")
     if voxel is not None and not (isinstance(voxel, (int, float, np.integer, np.floating)) and not isinstance(voxel, bool) and 0 < float(voxel) < float("inf")):
@@ -684,7 +702,11 @@ def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, **icp):
     poses = torch.eye(4, device=dev, dtype=torch.float64).repeat(S, 1, 1)
     status = np.zeros(S, np.int32)
     first = x[:int(o[1])]
-    if S > 1:
+    if multiway is not None:
+        poses, status, _ = multiway_registration_dev(x, o, **multiway)
+        moved = transform_points_dev(x, o, poses)
+        merged = torch.cat([moved[int(o[i]):int(o[i + 1])] for i in range(S) if status[i] < 2])
+    elif S > 1:
         src, so = x[int(o[1]):], o[1:] - o[1]
         tgt, to = first.repeat(S - 1, 1), np.arange(S, dtype=np.int64) * first.shape[0]
         run = icp_multiscale_dev if "voxels" in icp else icp_dev
@@ -702,3 +724,347 @@ def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, **icp):
     if voxel is not None and merged.shape[0]:
         merged = voxel_downsample_dev(merged, None, float(voxel))[0]
     return merged, poses, status
+
+
+# ---- multiway registration: information matrices and pose-graph optimisation (csrc/posegraph.hip) -------------------
+
+PG_MAX_NODES, PG_MAX_EDGES = 32, 496
+PG_INFO_SUMS = 10
+
+
+def _information(st):
+    """the information matrices of the pairs of an evaluated _Icp state, from the correspondences it holds -> info, count, flag"""
+    B, dev, lib = st.B, st.dev, st.lib
+    chunks = max(-(-st.max_n // int(lib.sfmi_pg_chunk())), 1)
+    part = torch.empty(B * chunks * PG_INFO_SUMS, device=dev, dtype=torch.float64)
+    info = torch.empty(B, 6, 6, device=dev, dtype=torch.float64)
+    count, flag, bad = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
+    L.check(lib.sfmi_pg_information_f32(L.ptr(st.src), L.ptr(st.tgt), L.ptr(st.sod), L.ptr(st.tod), L.ptr(st.pose), L.ptr(st.idx), L.ptr(st.d2),
+                                        L.ptr(st.maxd2), B, st.N, st.M, st.max_n, st.max_m, L.ptr(bad), L.ptr(part), L.ptr(info), L.ptr(count),
+                                        L.ptr(flag), L.stream_ptr()), "sfmi_pg_information_f32")
+    return info, count, flag
+
+
+def information_matrix_dev(source, target, s_off=None, t_off=None, max_dist=None, pose=None, details=False):
+    """Open3D's get_information_matrix_from_point_clouds for a batch of pairs under the given poses (None: identity): the
+    correspondences of evaluate_registration_dev, and over its inliers info = sum G^T G with G = [-[q]x | I], q the target point - the
+    point metric's J^T J of icp_step_dev with q in place of the moved source point.  max_dist may differ from pair to pair.
+    -> info (B,6,6) f64 symmetric, count (B,) int32 (= info[:,5,5]), fitness (B,) f64, rmse (B,) f64; with `details` also flag (B,) int32:
+    1 for a pair with a non-finite coordinate or pose (info 0, count 0).  f64 sums in icp_dev's fixed order: a batch equals per-pair calls
+    bit for bit."""
+    st = _Icp("information_matrix_dev", source, target, s_off, t_off, max_dist, "point", None, pose, "pose")
+    st.iterate(0, True)
+    info, count, flag = _information(st)
+    return (info, count, st.fitness, st.rmse, flag) if details else (info, count, st.fitness, st.rmse)
+
+
+def _edge_ints(v, E, what, name):
+    a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or a.shape != (E,):
+        raise L.SfmiError(f"{what}: {name} must be ({E},) integers, one per edge")
+    return a.astype(np.int64)
+
+
+def _edge_flags(v, E, what, name, default):
+    """None, a host array or a tensor of E integers / booleans -> host int32 array or the tensor"""
+    if v is None:
+        return np.full(E, default, np.int32)
+    if isinstance(v, torch.Tensor):
+        if v.dtype.is_floating_point or tuple(v.shape) != (E,):
+            raise L.SfmiError(f"{what}: {name} must be ({E},) integers or booleans, one per edge")
+        return v
+    a = np.asarray(v)
+    if not (a.dtype == np.bool_ or np.issubdtype(a.dtype, np.integer)) or a.shape != (E,):
+        raise L.SfmiError(f"{what}: {name} must be ({E},) integers or booleans, one per edge")
+    return (a != 0).astype(np.int32)
+
+
+def _check_unit(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) <= 1:
+        raise L.SfmiError(f"{what}: {name} must be a number in [0, 1], got {v!r}")
+    return float(v)
+
+
+class _Graph:
+    """The validated arguments of one optimiser call: a ragged batch of pose graphs"""
+
+    def __init__(self, what, nodes, src, tgt, transforms, infos, uncertain, alive, n_off, e_off):
+        self.what = what
+        if not hasattr(nodes, "shape") or len(nodes.shape) < 1:
+            raise L.SfmiError(f"{what}: nodes must be (S,4,4), (S,3,4) or (S,12) poses")
+        S = int(nodes.shape[0])
+        self.X = _pose_arg(nodes, S, what, "nodes")
+        E = len(src) if hasattr(src, "__len__") else -1
+        if E < 0:
+            raise L.SfmiError(f"{what}: src must be (E,) integers, one per edge")
+        self.srch, self.tgth = _edge_ints(src, E, what, "src"), _edge_ints(tgt, E, what, "tgt")
+        if not hasattr(transforms, "shape"):
+            raise L.SfmiError(f"{what}: transforms must be ({E},4,4), ({E},3,4) or ({E},12)")
+        self.T = _pose_arg(transforms, E, what, "transforms")
+        if not hasattr(infos, "shape") or tuple(infos.shape) != (E, 6, 6):
+            raise L.SfmiError(f"{what}: infos must be ({E},6,6), one information matrix per edge, got {tuple(getattr(infos, 'shape', ()))}")
+        self.Lam = infos
+        self.unc = _edge_flags(uncertain, E, what, "uncertain", 0)
+        self.alive = _edge_flags(alive, E, what, "alive", 1)
+        no, eo = host_offsets(n_off, S, f"{what} n_off"), host_offsets(e_off, E, f"{what} e_off")
+        if len(no) != len(eo):
+            raise L.SfmiError(f"{what}: n_off describes {len(no) - 1} graphs, e_off {len(eo) - 1}")
+        ns, es = np.diff(no), np.diff(eo)
+        if ns.min() < 1 or ns.max() > PG_MAX_NODES or es.max() > PG_MAX_EDGES:
+            raise L.SfmiError(f"{what}: a graph has between 1 and {PG_MAX_NODES} nodes and at most {PG_MAX_EDGES} edges, got up to {ns.max()} "
+                              f"nodes and {es.max()} edges")
+        size = np.repeat(ns, es)
+        if ((self.srch < 0) | (self.srch >= size) | (self.tgth < 0) | (self.tgth >= size) | (self.srch == self.tgth)).any():
+            raise L.SfmiError(f"{what}: src / tgt must be node indices inside their own graph, and differ")
+        self.S, self.E, self.Bg, self.no, self.eo, self.max_s = S, E, len(no) - 1, no, eo, int(ns.max())
+
+    def to_device(self):
+        t = [v for v in (self.T, self.Lam, self.X, self.unc, self.alive) if isinstance(v, torch.Tensor)]
+        if not t:
+            raise L.SfmiError(f"{self.what} needs HIP device tensors (no CPU fallback)")
+        dev = self.dev = on_device(self.what, *t)
+        f64 = lambda v: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, np.float64))).to(dev).to(torch.float64)
+        i32 = lambda v: ((v != 0) if isinstance(v, torch.Tensor) else torch.from_numpy(v).to(dev)).to(dev).to(torch.int32).contiguous()
+        self.X, self.T = f64(self.X).reshape(self.S, 12).contiguous(), f64(self.T).reshape(self.E, 12).contiguous()
+        self.Lam = f64(self.Lam).reshape(self.E, 36).contiguous()
+        self.unc, self.alive = i32(self.unc), i32(self.alive)
+        self.src, self.tgt = i32_dev(self.srch, dev), i32_dev(self.tgth, dev)
+        self.nod, self.eod = torch.from_numpy(self.no).to(dev), torch.from_numpy(self.eo).to(dev)
+        return dev
+
+    def run(self, X, alive, mu, max_iter, tol):
+        """one launch -> X' (S,12), l, cost, iterations, status, details"""
+        dev, Bg, E = self.dev, self.Bg, self.E
+        nmax = 6 * (self.max_s - 1)
+        f64 = dict(device=dev, dtype=torch.float64)
+        X = X.clone()
+        src, tgt, T, Lam, unc = self.src, self.tgt, self.T, self.Lam, self.unc
+        if E == 0:                                             # no edge in the batch: one unused element each, so no pointer is NULL
+            src = tgt = unc = alive = torch.zeros(1, device=dev, dtype=torch.int32)
+            T = Lam = torch.zeros(36, **f64)
+        l, ework = torch.zeros(max(E, 1), **f64), torch.empty(max(E, 1) * 27, **f64)
+        cost, lam = torch.empty(Bg, **f64), torch.empty(Bg, **f64)
+        it, status = torch.empty(Bg, device=dev, dtype=torch.int32), torch.empty(Bg, device=dev, dtype=torch.int32)
+        H = torch.zeros(Bg, max(nmax * (nmax + 1) // 2, 1), **f64)
+        g, delta = torch.zeros(Bg, max(nmax, 1), **f64), torch.zeros(Bg, max(nmax, 1), **f64)
+        L.check(L.lib().sfmi_pg_optimize_f64(L.ptr(self.nod), L.ptr(self.eod), Bg, self.max_s, L.ptr(X), L.ptr(src), L.ptr(tgt),
+                                             L.ptr(T), L.ptr(Lam), L.ptr(unc), L.ptr(alive), L.ptr(mu), max_iter, tol, L.ptr(l),
+                                             L.ptr(cost), L.ptr(it), L.ptr(status), L.ptr(ework), L.ptr(H), L.ptr(g), L.ptr(delta), L.ptr(lam),
+                                             L.stream_ptr()), "sfmi_pg_optimize_f64")
+        return X, l[:E], cost, it, status, dict(H=H, g=g[:, :nmax], delta=delta[:, :nmax], lam=lam)
+
+
+def _graph_opts(what, max_iter, tol):
+    max_iter = check_count(max_iter, what, "max_iter", 0)
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not 0 <= float(tol) < float("inf"):
+        raise L.SfmiError(f"{what}: tol must be a finite number >= 0, got {tol!r}")
+    return max_iter, float(tol)
+
+
+def pose_graph_optimize_dev(nodes, src, tgt, transforms, infos, uncertain=None, alive=None, n_off=None, e_off=None, mu=0.0, max_iter=100,
+                            tol=1e-10, details=False):
+    """Levenberg-Marquardt over a ragged batch of pose graphs, one workgroup per graph, the whole loop in one launch.
+
+    nodes (S,4,4) / (S,3,4) / (S,12) f64: the starting poses, scan frame -> frame of the graph's node 0 (which is held fixed); src, tgt
+    (E,) integers: node indices local to the edge's graph; transforms (E,4,4): p_tgt = T p_src; infos (E,6,6) f64 information matrices;
+    uncertain (E,): loop closures, which the line process may switch off; alive (E,): None = all.  n_off / e_off: (Bg+1,) offsets of
+    the graphs' nodes and edges (None: one graph); at most 32 nodes and 496 edges per graph.  transforms and infos are HIP tensors;
+    the rest may be host arrays.  mu: the line-process weight, one number, one per graph or a (Bg,) device tensor; <= 0: off.
+    The residual, the Jacobians, the line process and the loop are include/sfmi.h's (numpy: tests/posegraph_ref.py).
+    -> poses (S,4,4) f64, l (E,) f64 the line-process weights under them (1 for certain edges), cost (Bg,), iterations (Bg,), status
+    (Bg,) int32 (the module's table), all on the device; with `details` a dict(H, g, delta, lam) of the last solve follows.  A graph's
+    result depends on that graph alone and is bit-identical from run to run."""
+    what = "pose_graph_optimize_dev"
+    G = _Graph(what, nodes, src, tgt, transforms, infos, uncertain, alive, n_off, e_off)
+    max_iter, tol = _graph_opts(what, max_iter, tol)
+    if isinstance(mu, torch.Tensor):
+        if tuple(mu.shape) != (G.Bg,):
+            raise L.SfmiError(f"{what}: mu must be one number, one per graph or a ({G.Bg},) tensor")
+    else:
+        mu = np.asarray(_per_pair(mu, G.Bg, what, "mu", lambda v: float(v) if isinstance(v, (int, float, np.integer, np.floating)) and
+                                  not isinstance(v, bool) and np.isfinite(v) else None, "a finite number"), np.float64)
+    dev = G.to_device()
+    mu = (mu if isinstance(mu, torch.Tensor) else torch.from_numpy(mu)).to(dev).to(torch.float64).contiguous()
+    X, l, cost, it, status, more = G.run(G.X, G.alive, mu, max_iter, tol)
+    out = (_pose44(X), l, cost, it, status)
+    return out + (more,) if details else out
+
+
+def global_optimization_dev(nodes, src, tgt, transforms, infos, uncertain=None, alive=None, n_off=None, e_off=None, preference=2.0,
+                            max_dist=None, prune=0.25, max_iter=100, tol=1e-10):
+    """Open3D's global_optimization in its two passes, on pose_graph_optimize_dev's arguments.  Pass one runs the line process with mu =
+    preference x the mean over the graph's alive edges of infos[e,5,5] (the inlier count) x max_dist^2; then alive &= l >= prune on the
+    uncertain edges; pass two runs without the line process from pass one's poses.
+    -> poses (S,4,4) f64, kept (E,) bool, l (E,) f64 of pass one, status1 (Bg,), status2 (Bg,) int32, on the device."""
+    what = "global_optimization_dev"
+    G = _Graph(what, nodes, src, tgt, transforms, infos, uncertain, alive, n_off, e_off)
+    max_iter, tol = _graph_opts(what, max_iter, tol)
+    prune = _check_unit(prune, what, "prune")
+    preference = check_nonneg(preference, what, "preference")
+    md2 = check_nonneg(max_dist, what, "max_dist") ** 2
+    G.to_device()
+    w = torch.where(G.alive != 0, G.Lam[:, 35], torch.zeros_like(G.Lam[:, 35]))
+    tot = excl_at(torch.cumsum(w, 0), G.eod)
+    cnt = excl_at(torch.cumsum((G.alive != 0).to(torch.float64), 0), G.eod)
+    tot, cnt = tot[1:] - tot[:-1], cnt[1:] - cnt[:-1]
+    mu = torch.where(cnt > 0, preference * (tot / cnt.clamp(min=1)) * md2, torch.zeros_like(tot)).contiguous()
+    X1, l1, _, _, st1, _ = G.run(G.X, G.alive, mu, max_iter, tol)
+    kept = ((G.alive != 0) & ~((G.unc != 0) & (l1 < prune)))
+    X2, _, _, _, st2, _ = G.run(X1, kept.to(torch.int32).contiguous(), torch.zeros_like(mu), max_iter, tol)
+    return _pose44(X2), kept, l1, st1, st2
+
+
+def _scans_arg(clouds, offs, what):
+    """a list of (n_i,3) HIP tensors, or (N,3) points with (S+1,) offsets -> points (N,3) f32 contiguous, host offsets"""
+    if isinstance(clouds, (list, tuple)):
+        if offs is not None or not clouds:
+            raise L.SfmiError(f"{what}: a non-empty list of clouds takes no offsets")
+        parts = [points_arg(c, what) for c in clouds]
+        if any(c.dim() != 2 for c in parts):
+            raise L.SfmiError(f"{what}: every cloud must be (n,3)")
+        return parts, np.concatenate([[0], np.cumsum([c.shape[0] for c in parts])]).astype(np.int64)
+    x = points_arg(clouds, what)
+    if x.dim() != 2:
+        raise L.SfmiError(f"{what}: expected a list of (n,3) clouds or (N,3) points with offsets")
+    return [x], host_offsets(offs, x.shape[0], f"{what} offs")
+
+
+def _walk(S, edges, T):
+    """node poses by walking the edges breadth-first from scan 0.  edges: (i, j) with T (12,) taking scan j's frame to scan i's
+    -> X (S,12) f64, reached (S,) bool"""
+    def mul(a, b):
+        A, B = a.reshape(3, 4), b.reshape(3, 4)
+        return np.concatenate([A[:, :3] @ B[:, :3], (A[:, :3] @ B[:, 3] + A[:, 3])[:, None]], 1).reshape(12)
+
+    def inv(a):
+        A = a.reshape(3, 4)
+        return np.concatenate([A[:, :3].T, -(A[:, :3].T @ A[:, 3])[:, None]], 1).reshape(12)
+
+    X = np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float64), (S, 1))
+    seen, queue = np.zeros(S, bool), [0]
+    seen[0] = True
+    while queue:
+        a = queue.pop(0)
+        for k, (i, j) in enumerate(edges):
+            if i == a and not seen[j]:
+                X[j], seen[j] = mul(X[i], T[k]), True
+                queue.append(j)
+            elif j == a and not seen[i]:
+                X[i], seen[i] = mul(X[j], inv(T[k])), True
+                queue.append(i)
+    return X, seen
+
+
+def multiway_registration_dev(clouds, offs=None, pairs=None, max_dists=(0.05, 0.01), metric="point", min_fitness=0.1, preference=2.0,
+                              prune=0.25, global_init=None, normals_k=16, graph_max_iter=100, graph_tol=1e-10, **icp):
+    """Several partial scans of one object brought into the frame of scan 0 through a pose graph (Open3D's multiway registration), for
+    captures in which not every scan overlaps scan 0.
+
+    clouds: a list of (n_i,3) HIP tensors, or one (N,3) tensor with (S+1,) offsets `offs`; at most 32 scans.  Edges: all pairs i < j, or
+    `pairs` (a list of (i, j), i < j); the source is scan j and the target scan i.  Every edge is registered in ONE batch by consecutive
+    icp_dev(**icp) stages, one per entry of max_dists, each from the last stage's pose (the first from the identity or, with
+    global_init = a dict of global_registration_dev's arguments, from the global pose of the pairs whose global status is 0); the plane
+    metric takes its normals from scan.estimate_normals_dev(k=normals_k).  An edge is dropped if a stage ends with status >= 2 or its
+    fitness under the last max_dist is below min_fitness.  Edges j = i + 1 are certain, the rest uncertain.  information_matrix_dev at the
+    last max_dist weighs the edges; the node poses start from a breadth-first walk over the kept edges from scan 0 (on the host: the kept
+    mask and the edges' (P,12) poses are read back) and are refined by global_optimization_dev(preference, max_dist = the last stage's,
+    prune).  A scan that no kept edge reaches is reported with status 2 and keeps the identity.
+    -> poses (S,4,4) f64 on the device, status (S,) host int32 (0, or 2, or the optimiser's status >= 2 for every reached scan), and a
+    dict: edges (P,2) host, transforms (P,4,4), fitness (P,), information (P,6,6), l (P,) on the device, registered (P,) / kept (P,) host
+    bool (the edge entered the graph / survived the pruning), icp_status (P,) host, graph_status (pass one, pass two), chain (S,4,4)
+    the breadth-first start."""
+    from .scan import estimate_normals_dev
+    what = "multiway_registration_dev"
+    parts, o = _scans_arg(clouds, offs, what)
+    S = len(o) - 1
+    if not 1 <= S <= PG_MAX_NODES:
+        raise L.SfmiError(f"{what}: between 1 and {PG_MAX_NODES} scans, got {S}")
+    if pairs is None:
+        pairs = [(i, j) for i in range(S) for j in range(i + 1, S)]
+    else:
+        try:
+            pairs = [(int(i), int(j)) for i, j in pairs]
+        except (TypeError, ValueError):
+            raise L.SfmiError(f"{what}: pairs must be a list of (i, j) scan indices") from None
+        if any(not 0 <= i < j < S for i, j in pairs) or len(set(pairs)) != len(pairs):
+            raise L.SfmiError(f"{what}: pairs must be distinct (i, j) with 0 <= i < j < {S}")
+    if len(pairs) > PG_MAX_EDGES:
+        raise L.SfmiError(f"{what}: at most {PG_MAX_EDGES} pairs")
+    try:
+        max_dists = list(max_dists)
+    except TypeError:
+        max_dists = []
+    if not max_dists:
+        raise L.SfmiError(f"{what}: max_dists must be a non-empty sequence, one max_dist per ICP stage")
+    for m in max_dists:
+        check_nonneg(m, what, "max_dists")
+    if metric not in METRICS:
+        raise L.SfmiError(f"{what}: metric must be one of {METRICS}, got {metric!r}")
+    min_fitness = _check_unit(min_fitness, what, "min_fitness")
+    prune = _check_unit(prune, what, "prune")
+    preference = check_nonneg(preference, what, "preference")
+    graph_max_iter, graph_tol = _graph_opts(what, graph_max_iter, graph_tol)
+    bad_kw = set(icp) - {"max_iter", "rel_fitness", "rel_rmse", "check_every"}
+    if bad_kw:
+        raise L.SfmiError(f"{what}: unknown arguments {sorted(bad_kw)}")
+    if global_init is not None and not isinstance(global_init, dict):
+        raise L.SfmiError(f"{what}: global_init must be a dict of global_registration_dev arguments")
+    dev = on_device(what, *parts)
+    x = (torch.cat([c.float() for c in parts]) if len(parts) > 1 else parts[0].float()).contiguous()
+    P = len(pairs)
+    poses = torch.eye(4, device=dev, dtype=torch.float64).repeat(S, 1, 1)
+    status = np.zeros(S, np.int32)
+    edges = np.array(pairs, np.int64).reshape(P, 2)
+    more = dict(edges=edges, transforms=poses[:0], fitness=poses.new_zeros(0), information=poses.new_zeros(0, 6, 6), l=poses.new_zeros(0),
+                registered=np.zeros(P, bool), kept=np.zeros(P, bool), icp_status=np.zeros(P, np.int32), graph_status=(0, 0), chain=poses.clone())
+    if P == 0:
+        status[1:] = 2
+        return poses, status, more
+    scan = [x[int(o[i]):int(o[i + 1])] for i in range(S)]
+    src, tgt = torch.cat([scan[j] for _, j in pairs]), torch.cat([scan[i] for i, _ in pairs])
+    so = np.concatenate([[0], np.cumsum([scan[j].shape[0] for _, j in pairs])]).astype(np.int64)
+    to = np.concatenate([[0], np.cumsum([scan[i].shape[0] for i, _ in pairs])]).astype(np.int64)
+    nrm = None
+    if metric == "plane":
+        n_all = estimate_normals_dev(x, o, normals_k)[0]
+        nrm = torch.cat([n_all[int(o[i]):int(o[i + 1])] for i, _ in pairs])
+    pose = torch.eye(4, device=dev, dtype=torch.float64).repeat(P, 1, 1)
+    if global_init is not None:
+        g = global_registration_dev(src, tgt, so, to, **global_init)
+        pose = torch.where((g[6] < 1)[:, None, None], g[0], pose)
+    dead = torch.zeros(P, device=dev, dtype=torch.bool)
+    st = None
+    for md in max_dists:                                       # a pair that has failed keeps its pose: the stages that follow do not count
+        new, _, _, _, st = icp_dev(src, tgt, so, to, md, metric, nrm, pose, **icp)
+        pose = torch.where(dead[:, None, None], pose, new)
+        dead |= st >= 2
+    ev = _Icp(what, src, tgt, so, to, max_dists[-1], "point", None, pose, "pose")
+    ev.iterate(0, True)
+    info, _, _ = _information(ev)
+    ok = (~dead) & (ev.fitness >= min_fitness)
+    ok_h, st_h, T_h = ok.cpu().numpy(), st.cpu().numpy(), ev.pose.cpu().numpy()      # the read-back: (P,) masks and (P,12) poses
+    reg = [k for k in range(P) if ok_h[k]]
+    X0, seen = _walk(S, [pairs[k] for k in reg], T_h[reg])
+    node = np.cumsum(seen) - 1
+    keep = [k for k in reg if seen[pairs[k][0]] and seen[pairs[k][1]]]
+    status[~seen] = 2
+    chain = torch.from_numpy(X0).to(dev)
+    poses = _pose44(chain)
+    l_all, kept_h, gs = torch.zeros(P, device=dev, dtype=torch.float64), np.zeros(P, bool), (0, 0)
+    if keep:
+        kd = torch.from_numpy(np.array(keep, np.int64)).to(dev)
+        gsrc, gtgt = np.array([node[pairs[k][1]] for k in keep]), np.array([node[pairs[k][0]] for k in keep])
+        unc = np.array([pairs[k][1] != pairs[k][0] + 1 for k in keep], np.int32)
+        sd = torch.from_numpy(np.nonzero(seen)[0]).to(dev)
+        X, kept, l1, s1, s2 = global_optimization_dev(chain[sd], gsrc, gtgt, ev.pose[kd], info[kd], unc, None, None, None, preference,
+                                                      max_dists[-1], prune, graph_max_iter, graph_tol)
+        poses[sd] = X
+        l_all[kd] = l1
+        kept_h[keep] = kept.cpu().numpy()
+        gs = (int(s1.cpu()[0]), int(s2.cpu()[0]))
+        if gs[1] >= 2:
+            status[seen] = gs[1]
+    more.update(transforms=_pose44(ev.pose), fitness=ev.fitness, information=info, l=l_all, kept=kept_h, icp_status=st_h, graph_status=gs,
+                chain=_pose44(chain))
+    more["registered"][keep] = True
+    return poses, status, more
