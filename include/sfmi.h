@@ -1071,6 +1071,40 @@ int sfmi_pg_optimize_f64(const long long* noff, const long long* eoff, int Bg, i
                          double tol, double* l, double* cost, int* iterations, int* status, double* ework, double* H, double* g,
                          double* delta, double* lam, void* stream);
 
+/* ---- Consistent orientation of unoriented normals: tangent-plane propagation over the minimum spanning forest of the k-nearest-
+ *      neighbour graph (csrc/tangent.hip).  Hoppe et al. 1992; the interface of Open3D's
+ *      orient_normals_consistent_tangent_plane, not its bits: the statement below is the specification, restated in numpy in
+ *      tests/orient_ref.py.  The reference has no such step: its real-scan clouds carry neither normals nor a camera.
+ * Ragged sets: off (B+1) int64 [device]; normal (N,3) f32 unit normals of arbitrary sign; idx (N,k) int32 neighbour table local to each
+ * set as sfmi_knn_f32 writes it, 1 <= k <= 64; N < 2^31; max_n = the largest set (it fixes the number of rounds, ceil(log2(max_n))).
+ * Graph: vertex i is dead when its normal is not finite or is (0,0,0).  {i,j}, i != j, is an edge when j appears in row i or i in row
+ * j and both ends are alive; entries < 0, >= n_b or == i are skipped; a pair that appears twice is one edge.
+ * Weight: dot = (nx_i nx_j + ny_i ny_j) + nz_i nz_j with the f32 components widened to f64 (exact products); w = max(0, 1 - |dot|),
+ * flip(i,j) = dot < 0.  Edges are ordered by (bits of w as uint64, min(i,j), max(i,j)) ascending, a strict total order, so the minimum
+ * spanning forest is unique and every output is a function of the input alone: not of the schedule, the batch around a set or the run.
+ *   component (N) int32  the smallest local index of the vertex's tree; a dead vertex is its own component
+ *   tree (N,2) int32     the forest's edges as local (lo, hi), exactly n_b - components_b rows per set in slots of the set, (-1,-1)
+ *                        elsewhere; which slot holds which edge is not part of the contract
+ *   parity (N) uint8     XOR of flip along the tree path from the vertex to the vertex named by component
+ *   rounds (B) int32     Boruvka rounds that hooked something in the set
+ *   status (B) int32     0; 1 when a walk from an old root to its new root reached its cap of n_b steps (a cycle: a bug, never an
+ *                        input; the walk stops there and the set's outputs are not to be used)
+ * Integer atomics only (min, max); no kernel waits on another workgroup.  workspace: sfmi_tangent_workspace_bytes(B, N) bytes, 0 for
+ * arguments the calls refuse. */
+size_t sfmi_tangent_workspace_bytes(int B, long long N);
+int sfmi_tangent_forest_f32(const float* normal, const long long* off, const int* idx, int B, long long N, int k, long long max_n,
+                            int* component, int* tree, unsigned char* parity, int* rounds, int* status, void* workspace, void* stream);
+/* The anchor, one global sign per tree, and the oriented normals.  P (N,3) f32; normal / component / parity as above; B <= 65535.
+ * With m_x = (parity ? -n_x : n_x) and a direction d_x, both in f64, t = (mx dx + my dy) + mz dz with every product and sum rounded on
+ * its own: votes (N,2) int32, row off[b] + c = (#{x in the tree of component c : t > 0}, #{t < 0}), 0 elsewhere; dead vertices, t = 0
+ * and NaN do not vote.  A tree is negated when its second count exceeds its first (a tie leaves it).  viewpoint (B,3) f64 [device]:
+ * d_x = v_b - p_x.  NULL: d_x = p_x - c_b, c_b the centroid of the set's finite points exactly as sfmi_fpfh_orient_f32 sums it (one
+ * workgroup of 16 waves, a lane's points ascending, the fixed f64 tree).  out (N,3) f32: the input normal, or its negation where
+ * parity XOR (the tree is negated): the sign bits alone change; a dead vertex passes through.  Integer atomics only (add of counts).
+ * workspace: as above (used for the centroids). */
+int sfmi_tangent_apply_f32(const float* P, const float* normal, const long long* off, const int* component, const unsigned char* parity,
+                           const double* viewpoint, int B, long long N, int* votes, float* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

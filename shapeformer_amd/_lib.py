@@ -273,6 +273,10 @@ PROTOTYPES = {
     "sfmi_pg_max_nodes": (i32, []),
     "sfmi_pg_max_edges": (i32, []),
     "sfmi_pg_optimize_f64": (i32, [c_ptr, c_ptr, i32, i32] + [c_ptr] * 8 + [i32, C.c_double] + [c_ptr] * 10),
+    # consistent normal orientation: kNN-graph minimum spanning forest, parity, anchor vote (csrc/tangent.hip)
+    "sfmi_tangent_workspace_bytes": (sz, [i32, i64]),
+    "sfmi_tangent_forest_f32": (i32, [c_ptr] * 3 + [i32, i64, i32, i64] + [c_ptr] * 7),
+    "sfmi_tangent_apply_f32": (i32, [c_ptr] * 6 + [i32, i64] + [c_ptr] * 4),
 }
 
 

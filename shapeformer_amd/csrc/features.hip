@@ -143,17 +143,8 @@ __global__ __launch_bounds__(OR_THREADS) void orient_kernel(const float* __restr
   const long long base = off[b], n = off[b + 1] - base;
   const float* Pb = P + 3 * base;
   float* Nb = Nrm + 3 * base;
-  double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
-  for (long long i = tid; i < n; i += OR_THREADS) {
-    const double x = (double)Pb[3 * i], y = (double)Pb[3 * i + 1], z = (double)Pb[3 * i + 2];
-    if (sfmi_finite3(x, y, z)) {
-      sx += x; sy += y; sz += z; sc += 1.0;
-    }
-  }
-  sx = sfmi_block_sum_f64<OR_WAVES>(sx, red); sy = sfmi_block_sum_f64<OR_WAVES>(sy, red); sz = sfmi_block_sum_f64<OR_WAVES>(sz, red);
-  sc = sfmi_block_sum_f64<OR_WAVES>(sc, red);                  // whole numbers below 2^31: exact in f64
-  if (!(sc > 0.0)) return;                                     // workgroup-uniform: no finite point, nothing is turned
-  const double cx = sx / sc, cy = sy / sc, cz = sz / sc;
+  double cx, cy, cz;
+  if (!sfmi_centroid_f64<OR_WAVES>(Pb, n, red, cx, cy, cz)) return;   // workgroup-uniform: no finite point, nothing is turned
   for (long long i = tid; i < n; i += OR_THREADS) {
     const double x = (double)Pb[3 * i] - cx, y = (double)Pb[3 * i + 1] - cy, z = (double)Pb[3 * i + 2] - cz;
     const float nx = Nb[3 * i], ny = Nb[3 * i + 1], nz = Nb[3 * i + 2];

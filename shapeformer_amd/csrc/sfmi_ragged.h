@@ -1,5 +1,5 @@
 // Shared pieces of the mesh and scan tools: what csrc/pointdist.hip, meshsdf.hip, hpr.hip, iso_sparse.hip, simplify.hip,
-// components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip and global_register.hip need
+// components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip, global_register.hip and tangent.hip need
 // for ragged batches (the split nearest-neighbour search of the scan tools is sfmi_search.h, which includes this file).  A ragged batch
 // is B sets stored back to back with (B+1) nondecreasing offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b
 // with off[b] <= x < off[b+1].  Everything here is inlined into its caller.  A caller's `#pragma clang fp contract(off)` comes after
@@ -143,6 +143,28 @@ __device__ __forceinline__ double sfmi_nan_f64() { return __longlong_as_double(0
 template <typename T>
 __device__ __forceinline__ bool sfmi_finite3(T x, T y, T z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 __device__ __forceinline__ bool sfmi_finite3(const float* __restrict__ p) { return sfmi_finite3(p[0], p[1], p[2]); }
+
+// the centroid of a set's finite points by one workgroup of WAVES waves, in f64 in a fixed order: a lane's points ascending (lane t takes
+// points t, t + 64 WAVES, ...), then sfmi_block_sum_f64.  WAVES is part of the order: features.hip's orient_kernel and tangent.hip's
+// tg_centroid_kernel both run it with 16 waves and so get the same bits.  Pb: the set's first point, n its size; red: WAVES doubles of
+// LDS; every lane of the workgroup calls.  false (workgroup-uniform, c untouched) for a set without a finite point.  Sums and one
+// division: nothing here contracts.
+template <int WAVES>
+__device__ __forceinline__ bool sfmi_centroid_f64(const float* __restrict__ Pb, long long n, double* red, double& cx, double& cy,
+                                                  double& cz) {
+  double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
+  for (long long i = threadIdx.x; i < n; i += WAVES * 64) {
+    const double x = (double)Pb[3 * i], y = (double)Pb[3 * i + 1], z = (double)Pb[3 * i + 2];
+    if (sfmi_finite3(x, y, z)) {
+      sx += x; sy += y; sz += z; sc += 1.0;
+    }
+  }
+  sx = sfmi_block_sum_f64<WAVES>(sx, red); sy = sfmi_block_sum_f64<WAVES>(sy, red); sz = sfmi_block_sum_f64<WAVES>(sz, red);
+  sc = sfmi_block_sum_f64<WAVES>(sc, red);                     // whole numbers below 2^31: exact in f64
+  if (!(sc > 0.0)) return false;
+  cx = sx / sc; cy = sy / sc; cz = sz / sc;
+  return true;
+}
 
 // x' = f32(((r0 x + r1 y) + r2 z) + t) in f64, the f32 point widened first; T: one row of the pose (4 doubles).  Every product and sum
 // is rounded on its own, whatever the build's setting: the numpy restatements (tests/icp_ref.py, global_reg_ref.py) fix these bits.

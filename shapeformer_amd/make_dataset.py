@@ -4,7 +4,7 @@ shapeformer/data/imnet_datasets/utils.py:33-70, with the occupancy the IMNet2 st
     python -m shapeformer_amd.make_dataset MESH... --out ROOT --dataset NAME --split train [--grid 64] [--boundary-n 32768]
                                            [--cate NAME=GLOB ...] [--seed 0] [--batch K] [--scale 1.0]
                                            [--occupancy winding|morph|poisson] [--morph-grid 128] [--selem 6] [--morph-samples 1000000]
-                                           [--poisson-grid m*(grid-1)+1]
+                                           [--poisson-grid m*(grid-1)+1] [--orient tangent]
 
 Each mesh (.obj / .off / .ply) is normalised with normalize_point_set (bounding box centred, longest side 2) and multiplied by
 --scale, then batches of K meshes go through the device: lattice occupancy on the grid^3 makeGrid lattice of [-1, 1]^3 and
@@ -16,7 +16,9 @@ fills the box needs --scale 0.9 or so to keep that corner empty.  --occupancy po
 with nx/ny/nz normals (pointing outward) and no faces; a cloud is NOT normalised (a scan's bounding box is noise; normalise it upstream,
 scan.normalize_scan), only multiplied by --scale; Xbd is the cloud resampled to --boundary-n points and the occupancy is
 poisson_field_dev's field > 0 on a --poisson-grid^3 lattice of [-1, 1]^3, which must be m (grid - 1) + 1 nodes per axis so that the
-store's lattice is every m-th Poisson node (default: the smallest such lattice of at least 129 nodes).  The store is what
+store's lattice is every m-th Poisson node (default: the smallest such lattice of at least 129 nodes).  With --orient tangent a
+cloud without normals is accepted: its normals are estimated over 16 neighbours and oriented outward by tangent-plane
+propagation (scan.estimate_normals_dev(orient="tangent")); a cloud that has normals keeps them.  The store is what
 data.Imnet2LowResDataset reads:
 
     ROOT/NAME/SPLIT/Xbd.npy          (n, boundary_n, 3) float32 surface samples
@@ -86,8 +88,9 @@ def check_poisson_grid(grid, poisson_grid=None):
     return (poisson_grid - 1) // (grid - 1)
 
 
-def _poisson_batch(paths, grid, poisson_grid, boundary_n, scale, seed, dev):
-    """.ply clouds with normals -> Xbd (B, boundary_n, 3), occupancy (B, grid, grid, grid) uint8, both on the device"""
+def _poisson_batch(paths, grid, poisson_grid, boundary_n, scale, seed, dev, orient=None):
+    """.ply clouds with normals (orient="tangent": or without) -> Xbd (B, boundary_n, 3), occupancy (B, grid, grid, grid) uint8, both on
+    the device"""
     import torch
     from . import meshio, poisson
     from .hpr import resample_visible_dev
@@ -95,11 +98,14 @@ def _poisson_batch(paths, grid, poisson_grid, boundary_n, scale, seed, dev):
     pts, nrm = [], []
     for p in paths:
         v, _, n = meshio.read_ply(p, with_normals=True)
-        if n is None:
+        if n is None and orient is None:
             raise ValueError(f"{p}: the cloud has no normals (nx/ny/nz): --occupancy poisson needs oriented points")
         if len(v) == 0:
             raise ValueError(f"{p}: no points")
         pts.append(np.asarray(v * scale, np.float32))
+        if n is None:                                              # estimated on the device, on the scaled points
+            from .scan import estimate_normals_dev
+            n = estimate_normals_dev(torch.from_numpy(pts[-1]).to(dev), orient=orient)[0].cpu().numpy()
         nrm.append(np.asarray(n, np.float32))
     off = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
     x, n = torch.from_numpy(np.concatenate(pts)).to(dev), torch.from_numpy(np.concatenate(nrm)).to(dev)
@@ -111,11 +117,13 @@ def _poisson_batch(paths, grid, poisson_grid, boundary_n, scale, seed, dev):
 
 
 def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, cates=None, seed=0, batch=8, device="cuda:0",
-                 log=None, occupancy="winding", morph_grid=128, selem=6, morph_samples=1_000_000, scale=1.0, poisson_grid=None):
+                 log=None, occupancy="winding", morph_grid=128, selem=6, morph_samples=1_000_000, scale=1.0, poisson_grid=None,
+                 orient=None):
     """Read, normalise and sample every mesh of `paths`; write the store.  cates: {name: glob} matched against each path.
     occupancy: "winding" (mesh_occupancy_dev), "morph" (morph_voxelization_dev on a morph_grid^3 grid, ball of selem cells,
     morph_samples surface samples) or "poisson" (paths are .ply clouds with normals: poisson_field_dev on a poisson_grid^3 lattice);
-    scale multiplies the normalised vertices (poisson: the cloud as it is) on every route."""
+    scale multiplies the normalised vertices (poisson: the cloud as it is) on every route.  orient="tangent" (poisson only): clouds
+    without normals get normals over estimate_normals_dev's default neighbourhood, oriented outward by tangent-plane propagation."""
     import torch
     from . import meshio, meshsdf
     from ._ragged import batch_meshes
@@ -126,6 +134,8 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
         raise ValueError(f"scale = {scale!r} must be a positive number")
     if occupancy == "poisson":
         check_poisson_grid(grid, poisson_grid)
+    if orient not in (None, "tangent") or (orient is not None and occupancy != "poisson"):
+        raise ValueError(f"orient = {orient!r} must be None or 'tangent', and goes with occupancy = 'poisson'")
     dev = torch.device(device)
     Xbd, occ = [], []
     lattice = None
@@ -134,7 +144,7 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
         lattice = torch.from_numpy(make_grid([-1, -1, -1.], [1., 1, 1], [grid] * 3).astype(np.float32)).to(dev)
     for s in range(0, len(paths), batch):
         if occupancy == "poisson":
-            x, o = _poisson_batch(paths[s:s + batch], grid, poisson_grid, boundary_n, scale, seed + s, dev)
+            x, o = _poisson_batch(paths[s:s + batch], grid, poisson_grid, boundary_n, scale, seed + s, dev, orient)
             occ.append(o.cpu().numpy())
             Xbd.append(x.cpu().numpy())
             if log:
@@ -180,6 +190,8 @@ def parse_args(argv=None):
                          "poisson: Poisson reconstruction of .ply point clouds with normals")
     ap.add_argument("--poisson-grid", type=int, default=None,
                     help="poisson: nodes per axis of the Poisson lattice, m * (grid - 1) + 1 (default: the smallest such >= 129)")
+    ap.add_argument("--orient", choices=("tangent",), default=None,
+                    help="poisson: accept clouds without normals; estimate them and orient them outward by tangent-plane propagation")
     ap.add_argument("--morph-grid", type=int, default=128, help="morph: voxels per axis of the watertight grid")
     ap.add_argument("--selem", type=int, default=6, help="morph: radius in voxels of the closing's ball (0 .. 16)")
     ap.add_argument("--morph-samples", type=int, default=1_000_000, help="morph: surface samples per mesh")
@@ -196,6 +208,8 @@ def parse_args(argv=None):
             check_poisson_grid(a.grid, a.poisson_grid)
         except ValueError as e:
             ap.error(str(e))
+    if a.orient is not None and a.occupancy != "poisson":
+        ap.error("--orient goes with --occupancy poisson")
     cates = {}
     for c in a.cate:
         name, sep, g = c.partition("=")
@@ -210,7 +224,7 @@ def main(argv=None):
     a = parse_args(argv)
     d = make_dataset(a.meshes, a.out, a.dataset, a.split, a.grid, a.boundary_n, a.cates, a.seed, max(1, a.batch),
                      log=lambda m: print(m, file=sys.stderr), occupancy=a.occupancy, morph_grid=a.morph_grid, selem=a.selem,
-                     morph_samples=a.morph_samples, scale=a.scale, poisson_grid=a.poisson_grid)
+                     morph_samples=a.morph_samples, scale=a.scale, poisson_grid=a.poisson_grid, orient=a.orient)
     print(d)
 
 

@@ -9,8 +9,8 @@ interface of that call, not Open3D's octree output, and parity with Open3D is no
   poisson_solve_dev(rhs, tol, max_iter, check_every)                  -> chi (B,R,R,R), iterations (B,), residual (B,)
   poisson_field_dev(points, normals, off, grid_dim | depth, bbox, tol, max_iter) -> field, W, info
   poisson_sample_dev(lattice, points, off, bbox)                      -> (N,) f32 trilinear samples
-  poisson_recon_dev(points, normals, off, depth, quantile, knn, viewpoint, keep_components, ...) -> verts, faces, voff, toff, density
-  Open3D_Toolbox().poisson_recon(cloud, normals, viewpoint, depth, quantile, knn) -> (vert float64, face int) numpy
+  poisson_recon_dev(points, normals, off, depth, quantile, knn, viewpoint, keep_components, ..., orient) -> verts, faces, voff, toff, density
+  Open3D_Toolbox().poisson_recon(cloud, normals, viewpoint, depth, quantile, knn, orient) -> (vert float64, face int) numpy
 
 The discrete problem (its numpy statement is tests/poisson_ref.py): R nodes per axis over a cubic box, h = (hi - lo) / (R - 1), axes
 those of marching_cubes_dev.  The normals are splatted with trilinear weights onto the lattice's EDGES (Vx (R-1,R,R) at ((i+½),j,k),
@@ -314,7 +314,7 @@ def _trim(verts, faces, vo, to, density, q):
 
 
 def poisson_recon_dev(points, normals=None, off=None, depth=None, quantile=0.0, knn=10, viewpoint=None, keep_components=None,
-                      grid_dim=None, bbox=DEFAULT_BBOX, tol=1e-4, max_iter=None):
+                      grid_dim=None, bbox=DEFAULT_BBOX, tol=1e-4, max_iter=None, orient=None):
     """geoutil.Open3D_Toolbox.poisson_recon on the device, for a ragged batch of clouds: normals (given, or estimate_normals_dev over
     knn neighbours oriented towards `viewpoint`), poisson_field_dev on a lattice of 2^depth + 1 nodes per axis (default depth 7; or
     grid_dim), marching_cubes_dev at 0, then the density trim: a vertex's density is the trilinear sample of W there, and with
@@ -323,9 +323,12 @@ def poisson_recon_dev(points, normals=None, off=None, depth=None, quantile=0.0, 
     forms) filters the connected components after the trim.
     -> verts (V,3) f32, faces (T,3) int32 local per shape, voff, toff (B+1,) host, density (V,) f32.
     normals=None needs a viewpoint ((B,3), or (3,) for one set): the sign rule of estimate_normals_dev without one is not a consistent
-    orientation, and Poisson needs one."""
+    orientation, and Poisson needs one.  orient="tangent" (with normals=None) is the other way to one: the estimated normals are
+    oriented by scan.orient_normals_dev on the same knn table, towards the viewpoint if one is given and outward otherwise."""
     from .components import parse_keep
     what = "poisson_recon_dev"
+    if orient not in (None, "tangent"):
+        raise L.SfmiError(f"{what}: orient must be None or 'tangent', got {orient!r}")
     if grid_dim is None and depth is None:
         depth = 7
     R = _check_grid(grid_dim, depth, what)
@@ -335,14 +338,17 @@ def poisson_recon_dev(points, normals=None, off=None, depth=None, quantile=0.0, 
     keep = parse_keep(keep_components)
     x, n, o = _cloud_args(points, normals, off, what)
     _check_size(len(o) - 1, R, what)
-    if n is None and viewpoint is None:
+    if n is None and viewpoint is None and orient is None:
         raise L.SfmiError(f"{what}: normals=None needs a viewpoint to orient the estimated normals (without one their signs are not "
                           "a consistent orientation)")
+    if n is not None and orient is not None:
+        raise L.SfmiError(f"{what}: orient goes with normals=None (given normals are used as they are; scan.orient_normals_dev "
+                          "orients them)")
     on_device(what, x, *([n] if n is not None else []))
     xf = x.float().contiguous()
     if n is None:
         from .scan import estimate_normals_dev
-        n = estimate_normals_dev(xf, o, knn, viewpoint)[0]
+        n = estimate_normals_dev(xf, o, knn, viewpoint, orient)[0]
     field, W, _ = _field(xf, n.float().contiguous(), o, R, box, tol, max_iter)
     from .mcubes import marching_cubes_dev
     lo_hi = (tuple(box[:3]), tuple(box[3:]))
@@ -366,16 +372,17 @@ class Open3D_Toolbox:
     def __init__(self, device="cuda:0"):
         self.device = device
 
-    def poisson_recon(self, cloud, normals=None, viewpoint=None, depth=6, quantile=.3, knn=10):
-        """cloud (N,3) numpy, normals (N,3) or None (then estimated over knn neighbours and oriented towards viewpoint (3,))
+    def poisson_recon(self, cloud, normals=None, viewpoint=None, depth=6, quantile=.3, knn=10, orient=None):
+        """cloud (N,3) numpy, normals (N,3) or None (then estimated over knn neighbours and oriented towards viewpoint (3,), or with
+        orient="tangent" by tangent-plane propagation, outward when no viewpoint is given)
         -> (vert (V,3) float64, face (T,3) int) numpy"""
         c = np.ascontiguousarray(np.asarray(cloud, np.float32))
         if c.ndim != 2 or c.shape[1] != 3:
             raise L.SfmiError(f"Open3D_Toolbox.poisson_recon: expected an (N,3) cloud, got {c.shape}")
-        if normals is None and viewpoint is None:
+        if normals is None and viewpoint is None and orient is None:
             raise L.SfmiError("Open3D_Toolbox.poisson_recon: normals=None needs a viewpoint to orient the estimated normals")
         dev = torch.device(self.device)
         x = torch.from_numpy(c).to(dev)
         n = None if normals is None else torch.from_numpy(np.ascontiguousarray(np.asarray(normals, np.float32))).to(dev)
-        v, f = poisson_recon_dev(x, n, None, depth=depth, quantile=quantile, knn=knn, viewpoint=viewpoint)[:2]
+        v, f = poisson_recon_dev(x, n, None, depth=depth, quantile=quantile, knn=knn, viewpoint=viewpoint, orient=orient)[:2]
         return v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)

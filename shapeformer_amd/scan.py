@@ -9,7 +9,8 @@ cKDTree.query); here it is exact brute force on the device, the sibling of metri
   knn_mean_dist_dev(points, off, k)                       -> (N,) f64 mean distance to the k nearest other points
   statistical_outlier_mask_dev(points, off, k, std_ratio) -> keep (N,) uint8, count (B,) int32, stat (N,) f64   (PCL's rule)
   radius_outlier_mask_dev(points, off, radius, min_neighbors) -> keep, count
-  estimate_normals_dev(points, off, k, viewpoint)         -> normal (N,3) f32, variation (N,) f32               (local PCA)
+  estimate_normals_dev(points, off, k, viewpoint, orient) -> normal (N,3) f32, variation (N,) f32               (local PCA)
+  orient_normals_dev(points, normals, off, k, idx, anchor, viewpoint, details) -> normals of consistent sign (csrc/tangent.hip, §5.21)
   normalize_scan(points, mode, scale)                     -> the four normalisations of the reference's real-scan datasets (host or device)
   farthest_point_sample_dev(points, off, n, start, valid) -> idx (B,n) int32, d2 (B,n) f32, count (B,), status (B,)   (csrc/downsample.hip,
   voxel_downsample_dev(points, off, voxel, pick)          -> out (M,3) f32, out_off (B+1,) host, first (M,), count (M,)       DESIGN.md §5.15)
@@ -163,25 +164,23 @@ def radius_outlier_mask_dev(points, off, radius, min_neighbors):
     return (keep.reshape(shape) if shape else keep), count
 
 
-def estimate_normals_dev(points, off=None, k=16, viewpoint=None):
+def estimate_normals_dev(points, off=None, k=16, viewpoint=None, orient=None):
     """Point normals by local PCA over the k nearest neighbours, the point itself included (as Open3D and PCL do): the eigenvector
     of the smallest eigenvalue of the neighbourhood's 3x3 covariance, everything in f64 on the device.
     -> normal (N,3) f32 unit vectors, variation (N,) f32 = l0 / (l0 + l1 + l2) (surface variation, 0 on a plane).
     viewpoint: (B,3) (or (3,) for one set) positions, used in f64: the sign is chosen so that n . (viewpoint - p) >= 0.  None: the
     component of largest magnitude is positive (the first such component on a tie).  A point with fewer than 3 neighbours (a set of
-    fewer than 3 points) gets normal (0,0,0) and variation NaN."""
+    fewer than 3 points) gets normal (0,0,0) and variation NaN.
+    orient="tangent": the signs are then made consistent by orient_normals_dev on the same neighbour table, with anchor "viewpoint"
+    when a viewpoint is given and "outward" otherwise.  None: the signs above, as ever."""
     k = _check_k(k, "estimate_normals_dev")
+    if orient not in ORIENT_MODES:
+        raise L.SfmiError(f"estimate_normals_dev: orient must be one of {ORIENT_MODES}, got {orient!r}")
     x, o, shape = point_sets(points, off, "estimate_normals_dev")
     B = len(o) - 1
     view = None
     if viewpoint is not None:
-        view = viewpoint.detach().cpu().numpy() if isinstance(viewpoint, torch.Tensor) else np.asarray(viewpoint)
-        view = np.asarray(view, np.float64)
-        if view.shape == (3,) and B == 1:
-            view = view[None]
-        if view.shape != (B, 3):
-            raise L.SfmiError(f"estimate_normals_dev: expected ({B},3) viewpoints, got {tuple(view.shape)}")
-        view = np.ascontiguousarray(view)
+        view = _viewpoints(viewpoint, B, "estimate_normals_dev")
     dev = on_device("estimate_normals_dev", x)
     xf = x.float().contiguous()
     N = xf.shape[0]
@@ -192,7 +191,113 @@ def estimate_normals_dev(points, off=None, k=16, viewpoint=None):
     vd = torch.from_numpy(view).to(dev) if view is not None else None
     L.check(L.lib().sfmi_knn_normals_f32(L.ptr(xf), L.ptr(od), L.ptr(idx), B, N, k, L.ptr(vd), L.ptr(normal), L.ptr(variation),
                                          L.stream_ptr()), "sfmi_knn_normals_f32")
+    if orient == "tangent":
+        normal = _orient_launch("estimate_normals_dev", xf, normal, o, idx, vd)["normal"]
     return (normal.reshape(*shape, 3), variation.reshape(shape)) if shape else (normal, variation)
+
+
+# ---- consistent orientation without a viewpoint: the kNN graph's minimum spanning forest (csrc/tangent.hip) ---------
+
+ORIENT_MODES = (None, "tangent")
+ANCHORS = ("outward", "viewpoint")
+
+
+def _viewpoints(viewpoint, B, what):
+    view = viewpoint.detach().cpu().numpy() if isinstance(viewpoint, torch.Tensor) else np.asarray(viewpoint)
+    view = np.asarray(view, np.float64)
+    if view.shape == (3,) and B == 1:
+        view = view[None]
+    if view.shape != (B, 3):
+        raise L.SfmiError(f"{what}: expected ({B},3) viewpoints, got {tuple(view.shape)}")
+    return np.ascontiguousarray(view)
+
+
+def _orient_launch(what, xf, nf, o, idx, vd):
+    """xf, nf (N,3) f32 contiguous, idx (N,k) int32 contiguous on one device, o validated host offsets, vd (B,3) f64 device viewpoints
+    or None (outward) -> dict of device tensors.  Reads the (B,) status back: one synchronisation."""
+    dev = xf.device
+    B, N, k = len(o) - 1, xf.shape[0], idx.shape[1]
+    out = torch.empty_like(nf)
+    component = torch.empty(N, device=dev, dtype=torch.int32)
+    tree = torch.empty(N, 2, device=dev, dtype=torch.int32)
+    parity = torch.empty(N, device=dev, dtype=torch.uint8)
+    votes = torch.zeros(N, 2, device=dev, dtype=torch.int32)
+    rounds = torch.zeros(B, device=dev, dtype=torch.int32)
+    if N and B:
+        lib = L.lib()
+        od = torch.from_numpy(o).to(dev)
+        status = torch.empty(B, device=dev, dtype=torch.int32)
+        ws = torch.empty(max(int(lib.sfmi_tangent_workspace_bytes(B, N)), 256), device=dev, dtype=torch.uint8)
+        L.check(lib.sfmi_tangent_forest_f32(L.ptr(nf), L.ptr(od), L.ptr(idx), B, N, k, _max_n(o), L.ptr(component), L.ptr(tree),
+                                            L.ptr(parity), L.ptr(rounds), L.ptr(status), L.ptr(ws), L.stream_ptr()),
+                "sfmi_tangent_forest_f32")
+        L.check(lib.sfmi_tangent_apply_f32(L.ptr(xf), L.ptr(nf), L.ptr(od), L.ptr(component), L.ptr(parity), L.ptr(vd), B, N,
+                                           L.ptr(votes), L.ptr(out), L.ptr(ws), L.stream_ptr()), "sfmi_tangent_apply_f32")
+        bad = np.nonzero(status.cpu().numpy())[0]                  # the one read-back
+        if bad.size:
+            raise L.SfmiError(f"{what}: the walk to a tree's root reached its step cap in set(s) {bad.tolist()} (a cycle in the forest)")
+    return {"normal": out, "component": component, "tree": tree, "parity": parity, "votes": votes, "rounds": rounds}
+
+
+def orient_normals_dev(points, normals, off=None, k=16, idx=None, anchor="outward", viewpoint=None, details=False):
+    """A consistent orientation for normals of arbitrary sign, set by set, without a camera: Hoppe et al.'s tangent-plane propagation
+    (Open3D orient_normals_consistent_tangent_plane), exact and deterministic.
+
+    points / normals (N,3) f32 HIP tensors with (B+1,) offsets (None: one set), or (B,M,3) batches.  idx: the (N,k) ((B,M,k)) int32
+    neighbour table, local to each set, used as it is; None: knn_dev over k neighbours with the point itself included, the table of
+    estimate_normals_dev.  -> the normals, each the input or its exact negation; with details=True also a dict: component, parity,
+    tree, votes, rounds (B,), n_components (B,), on the device.
+    Graph: points i != j of a set are joined when j is in row i or i in row j; a point whose normal is not finite or is (0,0,0) is
+    dead: it joins nothing and passes through.  Weight w = max(0, 1 - |n_i . n_j|) in f64, flip = n_i . n_j < 0.  The minimum spanning
+    forest under the strict order (bits of w, lo, hi) is unique; parity is the XOR of flip along the tree path to the tree's
+    lowest-index point (component); tree (N,2) holds the forest's edges as local (lo, hi) rows, (-1,-1) elsewhere.
+    anchor fixes one sign per tree by an integer vote over its points with m = the normal after parity: votes (N,2) int32 at the row
+    of the tree's component = (#{m . d > 0}, #{m . d < 0}); the tree is negated when the second count is larger.  "outward":
+    d = p - the set's centroid (of the SET, not of the tree: the sum of registration's frame-covariant rule); "viewpoint": d = v - p
+    with viewpoint (B,3) ((3,) for one set), in f64.
+    Trees are the connected pieces of the kNN graph: pieces that k neighbours do not join are oriented independently, each by its own
+    vote (raise k to join them).  Bit-identical from run to run; a set's results depend on that set alone.  The (B,) status is read
+    back: one synchronisation."""
+    what = "orient_normals_dev"
+    if idx is None:
+        k = _check_k(k, what)
+    if anchor not in ANCHORS:
+        raise L.SfmiError(f"{what}: anchor must be one of {ANCHORS}, got {anchor!r}")
+    x, o, shape = point_sets(points, off, what)
+    B = len(o) - 1
+    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != tuple(points.shape):
+        raise L.SfmiError(f"{what}: normals must be a tensor of the points' shape {tuple(points.shape)}, got "
+                          f"{tuple(normals.shape) if isinstance(normals, torch.Tensor) else type(normals).__name__}")
+    if idx is not None:
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+            raise L.SfmiError(f"{what}: idx must be an int32 torch tensor on the HIP device")
+        if idx.dim() != points.dim() or tuple(idx.shape[:-1]) != tuple(points.shape[:-1]):
+            raise L.SfmiError(f"{what}: idx must be {tuple(points.shape[:-1])} + (k,), got {tuple(idx.shape)}")
+        k = _check_k(int(idx.shape[-1]), what)
+    if x.shape[0] >= 2 ** 31 or B > 65535:
+        raise L.SfmiError(f"{what}: at most 65535 sets and fewer than 2^31 points")
+    view = None
+    if anchor == "viewpoint":
+        if viewpoint is None:
+            raise L.SfmiError(f"{what}: anchor='viewpoint' needs ({B},3) viewpoints")
+        view = _viewpoints(viewpoint, B, what)
+    elif viewpoint is not None:
+        raise L.SfmiError(f"{what}: a viewpoint goes with anchor='viewpoint', not with 'outward'")
+    dev = on_device(what, x, normals, *([idx] if idx is not None else []))
+    xf, nf = x.float().contiguous(), normals.reshape(-1, 3).float().contiguous()
+    table = _launch_knn(xf, xf, o, o, k, False)[1] if idx is None else idx.reshape(-1, k).contiguous()
+    r = _orient_launch(what, xf, nf, o, table, torch.from_numpy(view).to(dev) if view is not None else None)
+    out = r.pop("normal")
+    out = out.reshape(*shape, 3) if shape else out
+    if not details:
+        return out
+    N = xf.shape[0]
+    if N:
+        local = torch.arange(N, device=dev) - torch.from_numpy(o).to(dev)[set_ids(o, dev)]
+        r["n_components"] = _counts((r["component"].long() == local).to(torch.uint8), o)
+    else:
+        r["n_components"] = torch.zeros(B, device=dev, dtype=torch.int32)
+    return out, r
 
 
 # ---- the reference's real-scan normalisations (host or device: plain array arithmetic) ---------------------------------------------
