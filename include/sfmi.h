@@ -506,25 +506,27 @@ int sfmi_mesh_sample_f32(const float* verts, const int* faces, const long long* 
 /* ---- Mesh signed distance and occupancy (csrc/meshsdf.hip): exact brute force over the faces of each mesh.
  *      xgutils/geoutil.py:265-269 (signed_distance: igl.signed_distance, winding-number sign, then np.nan_to_num),
  *      :282-291 (mesh2sdf on the makeGrid 'ij' lattice), :455-490 (SDF_sampling: surface samples, near / far jitter). --------- */
-/* workspace for either form: the lattice form passes N = B * G^3 */
+/* workspace for either form: the lattice form passes N = B * G^3.  It holds one int64 winding partial per (face chunk, query). */
 size_t sfmi_mesh_sdf_workspace_bytes(int B, long long N, long long T);
 /* Ragged queries Q (N,3) f32 with qoff (B+1) int64; meshes verts (V,3) f32, faces (T,3) int32 with indices local to each shape,
  * voff / toff (B+1) int64 exclusive offsets (T_b < 2^31).  Query i of set b against mesh b:
  *   d2 = min over faces of fmaf(dz,dz,fmaf(dy,dy,dx*dx)) of q - C_f, C_f the exact closest point of face f (a degenerate face:
  *        of its segment or point); faces scanned in ascending order with a strict `<`: the LOWEST face index wins an f32 tie;
  *   I (N) int32 or NULL: that face, local to the shape;  C (N,3) f32 or NULL: its closest point (|q - C|^2 == d2 in f32);
- *   W (N) f32 or NULL: generalized winding number, sum of van Oosterom-Strackee solid angles / 4 pi;
+ *   W (N) f32 or NULL: generalized winding number, sum of van Oosterom-Strackee solid angles / 4 pi: f32 sums over runs of 64 faces
+ *        counted from the shape's first face, the runs added as 2^-29 fixed-point integers (associative: any split gives the same bits);
  *   S (N) f32: SIGN CONTRACT  S = -sqrt(d2) where |W| > 0.5 (inside), else +sqrt(d2) - libigl's winding-number sign type for
  *        closed, consistently oriented meshes (either orientation); finite inputs never give NaN.
  * status (B) int32: 0 ok; 1 the shape has no faces; 2 a vertex index of one of its faces lies outside [0, V_b).  A query of a
- * shape with status != 0 gets S = NaN, I = -1, C = NaN, W = 0.  Deterministic (no atomics): bit-identical from run to run; d2, I
- * and C do not depend on how the faces are split over workgroups (a batch equals per-shape calls bitwise in I, C and |S|; W
- * may differ in its last bits). */
+ * shape with status != 0 gets S = NaN, I = -1, C = NaN, W = 0; a shape without queries still gets its status.  Deterministic (no
+ * atomics): bit-identical from run to run, and nothing depends on how the faces are split over workgroups: a batch equals per-shape
+ * calls bitwise in S, I, C and W. */
 int sfmi_mesh_sdf_f32(const float* Q, const long long* qoff, const float* verts, const int* faces, const long long* voff,
                       const long long* toff, int B, long long N, long long T, float* S, int* I, float* C, float* W, int* status,
                       void* workspace, void* stream);
 /* Lattice occupancy: occ (B,G,G,G) uint8 = (|W| > 0.5) at makeGrid(lo, hi, [G]*3, mode="on", indexing="ij") (numpy linspace in f64,
- * then f32; generated in the kernel), 0 for a shape with status != 0 (codes as above).  lo, hi: [host] 3 doubles each. */
+ * then f32; generated in the kernel), 0 for a shape with status != 0 (codes as above).  lo, hi: [host] 3 doubles each.  W as above,
+ * so a shape's lattice does not depend on the batch around it. */
 int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long long* voff, const long long* toff, int B, long long T,
                             int G, const double* lo, const double* hi, unsigned char* occ, int* status, void* workspace, void* stream);
 /* SDF_sampling's jitter of B*n surface samples X (B*n,3): sample k < n_near of each shape gets near_std, the rest far_std, times a

@@ -15,11 +15,13 @@
 //      reverse priority (interior, BC, AC, C, AB, B, A): one reciprocal, no branches;
 //    - d2 = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) of q - C; faces scanned in ascending order with a strict `<` (lowest face wins a tie);
 //    - solid angle (van Oosterom & Strackee 1983): tan(Omega/2) = a.(b x c) / (|a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|)
-//      with a, b, c relative to q, accumulated in face order; W = sum Omega / 4 pi.
+//      with a, b, c relative to q; W = sum Omega / 4 pi.  The sum is taken in f32 over runs of SD_WRUN faces aligned to the
+//      shape's first face, and the runs are added as 2^-29 fixed-point integers: integer addition is associative, so W does not
+//      depend on where the chunks are cut, and a shape in a batch gets the bits it gets alone.
 //    The occupancy (lattice) instance needs only the sign: it skips the closest point and generates its queries from the
 //    lattice index (makeGrid 'on' mode, numpy linspace in f64, then f32).
-// 3. Merge launch, always: chunk minima in ascending chunk order with a strict `<`, W partials summed in ascending chunk order,
-//    C recomputed from the winning face, the sign applied, bad shapes overwritten.  d2, I and C do not depend on S.
+// 3. Merge launch, always: chunk minima in ascending chunk order with a strict `<`, the integer W partials added up,
+//    C recomputed from the winning face, the sign applied, bad shapes overwritten.  Nothing depends on S.
 #include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
 
 namespace {
@@ -30,6 +32,8 @@ constexpr int SD_REC = 5;                        // float4 per face record
 constexpr int SD_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
 constexpr int SD_MAX_SPLITS = 64;
 constexpr int SD_MIN_CHUNK = 64;                 // fewest faces (on average) per chunk
+constexpr int SD_WRUN = 64;                      // faces per f32 run of the winding sum; chunks are cut at its multiples
+constexpr float SD_WSCALE = 0x1.0p29f;           // a run's sum x 2^29, rounded, is bits 1.. of the partial: 2^31 faces x pi stay below 2^63
 
 template <bool OCC> struct SdR { static constexpr int R = 4; };       // queries per lane: full form
 template <> struct SdR<true> { static constexpr int R = 8; };         // winding number only
@@ -95,6 +99,24 @@ __device__ __forceinline__ float half_solid_angle(float qx, float qy, float qz, 
   const float den = fmaf(dot3(cx, cy, cz, ax, ay, az), lb,
                          fmaf(dot3(bx, by, bz, cx, cy, cz), la, fmaf(dot3(ax, ay, az, bx, by, bz), lc, la * lb * lc)));
   return atan2f(det, den);
+}
+
+// One run of the winding sum ends: add it to the integer partial and start the next from zero.  Bit 0 of a partial is set, and
+// stays set, once a run was not finite (a non-finite query); the sums themselves are even.
+__device__ __forceinline__ void w_flush(float& run, long long& acc) {
+  acc += __float2ll_rn(run * SD_WSCALE) << 1;
+  acc |= (long long)!(fabsf(run) < 1e6f);
+  run = 0.f;
+}
+
+// the partials of one query, added up: bad when any has bit 0 set
+__device__ __forceinline__ void w_add(long long p, long long& sum, bool& bad) {
+  bad |= (p & 1) != 0;
+  sum += p & ~1ll;
+}
+
+__device__ __forceinline__ float w_value(long long sum, bool bad) {
+  return bad ? __int_as_float(0x7FC00000) : (float)((double)sum * 0x1.0p-30);   // exact up to the one rounding to f32
 }
 
 // ---- setup ------------------------------------------------------------------------------------------------------------------
@@ -196,11 +218,12 @@ __device__ __forceinline__ float lattice_coord(const Lattice& L, int a, long lon
 
 // grid (query blocks upper bound, S).  Writes the chunk partials: pd / pi (full form) and pw at chunk s, offset s * N.
 // OCC: the queries are the G^3 lattice points of every shape (N = B G^3, qoff unused, block_off unused).
+// amdgpu_waves_per_eu(4): with the integer partials the full form would otherwise take 136 VGPRs and lose the fourth wave per SIMD
 template <bool OCC>
-__global__ __launch_bounds__(SD_THREADS) void sdf_kernel(const float* __restrict__ Q, const long long* __restrict__ qoff,
+__global__ __launch_bounds__(SD_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void sdf_kernel(const float* __restrict__ Q, const long long* __restrict__ qoff,
                                                           const long long* __restrict__ toff, const float4* __restrict__ rec,
                                                           const long long* __restrict__ block_off, int B, long long N, Lattice lat,
-                                                          float* __restrict__ pd, int* __restrict__ pi, float* __restrict__ pw) {
+                                                          float* __restrict__ pd, int* __restrict__ pi, long long* __restrict__ pw) {
   constexpr int R = SdR<OCC>::R;
   constexpr int QB = SD_THREADS * R;
   constexpr int NREC = OCC ? 3 : SD_REC;                      // OCC: a, b, c only (r0, r3, r4)
@@ -223,6 +246,7 @@ __global__ __launch_bounds__(SD_THREADS) void sdf_kernel(const float* __restrict
   }
   const int tid = threadIdx.x;
   float qx[R], qy[R], qz[R], best[R], wsum[R];
+  long long wacc[R];
   int bi[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -242,9 +266,10 @@ __global__ __launch_bounds__(SD_THREADS) void sdf_kernel(const float* __restrict
     best[r] = INFINITY;
     bi[r] = -1;
     wsum[r] = 0.f;
+    wacc[r] = 0;
   }
   const long long t0b = toff[b], t1b = toff[b + 1];
-  const long long chunk = cdiv(t1b - t0b, (long long)gridDim.y);
+  const long long chunk = cdiv(cdiv(t1b - t0b, (long long)gridDim.y), (long long)SD_WRUN) * SD_WRUN;   // tiles start at multiples of SD_WRUN
   const long long j0 = t0b + (long long)blockIdx.y * chunk;
   const long long j1 = j0 + chunk < t1b ? j0 + chunk : t1b;
   for (long long t0 = j0; t0 < j1; t0 += SD_TILE) {
@@ -263,23 +288,28 @@ __global__ __launch_bounds__(SD_THREADS) void sdf_kernel(const float* __restrict
     }
     __syncthreads();
     const int jb = (int)(t0 - t0b);                           // local index of the tile's first face (T_b < 2^31)
-    for (int jj = 0; jj < nt; ++jj) {                         // nt is block-uniform: no divergence
-      if (OCC) {
-        const float4 a = tile[0][jj], bb = tile[1][jj], c = tile[2][jj];   // broadcast reads
+    for (int j0r = 0; j0r < nt; j0r += SD_WRUN) {             // nt is block-uniform: no divergence
+      const int j1r = j0r + SD_WRUN < nt ? j0r + SD_WRUN : nt;
+      for (int jj = j0r; jj < j1r; ++jj) {
+        if (OCC) {
+          const float4 a = tile[0][jj], bb = tile[1][jj], c = tile[2][jj];   // broadcast reads
 #pragma unroll
-        for (int r = 0; r < R; ++r) wsum[r] = fmaf(bb.w, half_solid_angle(qx[r], qy[r], qz[r], a, bb, c), wsum[r]);
-      } else {
-        const float4 r0 = tile[0][jj], r1 = tile[1][jj], r2 = tile[2][jj], r3 = tile[3][jj], r4 = tile[4][jj];
+          for (int r = 0; r < R; ++r) wsum[r] = fmaf(bb.w, half_solid_angle(qx[r], qy[r], qz[r], a, bb, c), wsum[r]);
+        } else {
+          const float4 r0 = tile[0][jj], r1 = tile[1][jj], r2 = tile[2][jj], r3 = tile[3][jj], r4 = tile[4][jj];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-          float v, w;
-          const float d2 = closest_vw(qx[r], qy[r], qz[r], r0, r1, r2, v, w);
-          const bool lt = d2 < best[r];
-          best[r] = lt ? d2 : best[r];
-          bi[r] = lt ? jb + jj : bi[r];
-          wsum[r] = fmaf(r3.w, half_solid_angle(qx[r], qy[r], qz[r], r0, r3, r4), wsum[r]);
+          for (int r = 0; r < R; ++r) {
+            float v, w;
+            const float d2 = closest_vw(qx[r], qy[r], qz[r], r0, r1, r2, v, w);
+            const bool lt = d2 < best[r];
+            best[r] = lt ? d2 : best[r];
+            bi[r] = lt ? jb + jj : bi[r];
+            wsum[r] = fmaf(r3.w, half_solid_angle(qx[r], qy[r], qz[r], r0, r3, r4), wsum[r]);
+          }
         }
       }
+#pragma unroll
+      for (int r = 0; r < R; ++r) w_flush(wsum[r], wacc[r]);
     }
   }
   const long long so = (long long)blockIdx.y * N;
@@ -287,7 +317,7 @@ __global__ __launch_bounds__(SD_THREADS) void sdf_kernel(const float* __restrict
   for (int r = 0; r < R; ++r) {
     const long long i = qbase + r * SD_THREADS + tid;
     if (i < pend) {
-      pw[so + i] = wsum[r];
+      pw[so + i] = wacc[r];
       if (!OCC) {
         pd[so + i] = best[r];
         pi[so + i] = bi[r];
@@ -302,7 +332,7 @@ constexpr float INV_2PI = 0.15915494309189535f;               // W = sum(Omega /
 
 __global__ void sdf_merge_kernel(const float* __restrict__ Q, const long long* __restrict__ qoff, const long long* __restrict__ toff,
                                  const float4* __restrict__ rec, const int* __restrict__ status, int B, long long N, int S,
-                                 const float* __restrict__ pd, const int* __restrict__ pi, const float* __restrict__ pw,
+                                 const float* __restrict__ pd, const int* __restrict__ pi, const long long* __restrict__ pw,
                                  float* __restrict__ Sd, int* __restrict__ I, float* __restrict__ C, float* __restrict__ W) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
@@ -315,15 +345,18 @@ __global__ void sdf_merge_kernel(const float* __restrict__ Q, const long long* _
     if (W) W[i] = 0.f;
     return;
   }
-  float best = pd[i], ws = pw[i];
+  float best = pd[i];
+  long long ws = 0;
+  bool bad = false;
+  w_add(pw[i], ws, bad);
   int bi = pi[i];
   for (int s = 1; s < S; ++s) {
     const float d = pd[(long long)s * N + i];
     const int k = pi[(long long)s * N + i];
     if (d < best) { best = d; bi = k; }
-    ws += pw[(long long)s * N + i];
+    w_add(pw[(long long)s * N + i], ws, bad);
   }
-  const float wn = ws * INV_2PI;
+  const float wn = w_value(ws, bad) * INV_2PI;
   Sd[i] = fabsf(wn) > 0.5f ? -sqrtf(best) : sqrtf(best);
   if (I) I[i] = bi;
   if (W) W[i] = wn;
@@ -338,13 +371,14 @@ __global__ void sdf_merge_kernel(const float* __restrict__ Q, const long long* _
   }
 }
 
-__global__ void occ_merge_kernel(const int* __restrict__ status, long long G3, long long N, int S, const float* __restrict__ pw,
+__global__ void occ_merge_kernel(const int* __restrict__ status, long long G3, long long N, int S, const long long* __restrict__ pw,
                                  unsigned char* __restrict__ occ) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  float ws = pw[i];
-  for (int s = 1; s < S; ++s) ws += pw[(long long)s * N + i];
-  occ[i] = (status[i / G3] == 0 && fabsf(ws * INV_2PI) > 0.5f) ? 1 : 0;
+  long long ws = 0;
+  bool bad = false;
+  for (int s = 0; s < S; ++s) w_add(pw[(long long)s * N + i], ws, bad);
+  occ[i] = (status[i / G3] == 0 && fabsf(w_value(ws, bad) * INV_2PI) > 0.5f) ? 1 : 0;
 }
 
 // ---- SDF_sampling's jitter --------------------------------------------------------------------------------------------------
@@ -371,7 +405,7 @@ size_t sdf_ws(int B, long long N, long long T, bool occ, int* splits) {
   const int R = occ ? SdR<true>::R : SdR<false>::R;
   const int S = sd_splits(B, N, T, R);
   if (splits) *splits = S;
-  size_t w = align256((size_t)(B + 1) * 8) + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16) + align256((size_t)S * N * 4);
+  size_t w = align256((size_t)(B + 1) * 8) + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16) + align256((size_t)S * N * 8);
   if (!occ) w += 2 * align256((size_t)S * N * 4);
   return w;
 }
@@ -380,7 +414,7 @@ size_t sdf_ws(int B, long long N, long long T, bool occ, int* splits) {
 
 extern "C" {
 
-// workspace: block offsets (B+1 int64) | face records (T x 80 B) | W partials (S*N f32) | full form: d2, idx partials (S*N each)
+// workspace: block offsets (B+1 int64) | face records (T x 80 B) | W partials (S*N int64) | full form: d2, idx partials (S*N each)
 size_t sfmi_mesh_sdf_workspace_bytes(int B, long long N, long long T) {
   if (B <= 0 || N < 0 || T < 0) return 0;
   const size_t a = sdf_ws(B, N, T, false, nullptr), b = sdf_ws(B, N, T, true, nullptr);
@@ -399,8 +433,8 @@ int sfmi_mesh_sdf_f32(const float* Q, const long long* qoff, const float* verts,
   char* ws = (char*)workspace;
   long long* block_off = (long long*)ws;
   float4* rec = (float4*)(ws + align256((size_t)(B + 1) * 8));
-  float* pw = (float*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
-  float* pd = (float*)((char*)pw + align256((size_t)splits * N * 4));
+  long long* pw = (long long*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
+  float* pd = (float*)((char*)pw + align256((size_t)splits * N * 8));
   int* pi = (int*)((char*)pd + align256((size_t)splits * N * 4));
   if (T > 0) hipLaunchKernelGGL(sdf_setup_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, st, verts, faces, voff, toff, B, T, rec);
   hipLaunchKernelGGL(sdf_status_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, st, toff, (const float4*)rec, status);
@@ -412,7 +446,7 @@ int sfmi_mesh_sdf_f32(const float* Q, const long long* qoff, const float* verts,
     hipLaunchKernelGGL(sdf_kernel<false>, grid, dim3(SD_THREADS), 0, st, Q, qoff, toff, (const float4*)rec, (const long long*)block_off, B, N,
                        lat, pd, pi, pw);
     hipLaunchKernelGGL(sdf_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, Q, qoff, toff, (const float4*)rec,
-                       (const int*)status, B, N, splits, (const float*)pd, (const int*)pi, (const float*)pw, S, I, C, W);
+                       (const int*)status, B, N, splits, (const float*)pd, (const int*)pi, (const long long*)pw, S, I, C, W);
   }
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -428,7 +462,7 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
   sdf_ws(B, N, T, true, &splits);
   char* ws = (char*)workspace;
   float4* rec = (float4*)(ws + align256((size_t)(B + 1) * 8));
-  float* pw = (float*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
+  long long* pw = (long long*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
   Lattice lat;
   lat.G = G;
   for (int a = 0; a < 3; ++a) {
@@ -442,8 +476,8 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
   const dim3 grid((unsigned)(cdiv(G3, QB) * B), (unsigned)splits);
   hipLaunchKernelGGL(sdf_kernel<true>, grid, dim3(SD_THREADS), 0, st, (const float*)nullptr, (const long long*)nullptr, toff,
                      (const float4*)rec, (const long long*)nullptr, B, N, lat, (float*)nullptr, (int*)nullptr, pw);
-  hipLaunchKernelGGL(occ_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, (const int*)status, G3, N, splits, (const float*)pw,
-                     occ);
+  hipLaunchKernelGGL(occ_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, (const int*)status, G3, N, splits,
+                     (const long long*)pw, occ);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

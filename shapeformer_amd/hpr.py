@@ -85,7 +85,8 @@ def constraint_order_dev(x, o, c):
 def hidden_point_mask_dev(points, cams, off=None, param=np.pi, _evals=None, _index_order=False):
     """Which points each camera sees.  points: (B,N,3), or ragged (N,3) with (B+1,) exclusive offsets `off` (None: one shape), f32 or
     f64 HIP tensor; cams: (B,3) camera positions (numpy or tensor; used in f64).  -> visible uint8 (B,N) / (N,), count (B,) int32,
-    status (B,) int32 on the device.  A non-HIP tensor raises SfmiError before any launch."""
+    status (B,) int32 on the device (include/sfmi.h; an empty shape has count 0).  A shape's mask depends on that shape and its camera
+    alone.  A non-HIP tensor raises SfmiError before any launch."""
     x, o, c, shape = _prepare(points, cams, off, "hidden_point_mask_dev")
     dev, B, N = x.device, len(o) - 1, x.shape[0]
     lib = L.lib()
@@ -127,7 +128,8 @@ def sample_cameras(B, radius=10, seed=0, shape0=0):
 
 
 def resample_visible_dev(x, o, visible, count, context_N, noise=0., seed=0, shape0=0):
-    """x (N,3) flat device tensor, o host offsets, visible (N,) uint8, count (B,) int32 -> (B, context_N, 3) f32 (csrc/hpr.hip)."""
+    """x (N,3) flat device tensor, o host offsets, visible (N,) uint8, count (B,) int32 -> (B, context_N, 3) f32 (csrc/hpr.hip).
+    A shape without points gives NaN rows."""
     dev, B, N = x.device, len(o) - 1, x.shape[0]
     if context_N < 0 or noise < 0:
         raise L.SfmiError("virtual_scan_dev: context_N and noise must be >= 0")
@@ -145,7 +147,8 @@ def virtual_scan_dev(X, context_N, radius=10, noise=0., seed=0, cams=None, off=N
     """VirtualScanSelector on the device: X (B,N,3) (or ragged (N,3) + off) HIP tensor -> Xct (B, context_N, 3) f32 on the device, the
     cameras (B,3) f64 numpy, count (B,) int32 visible points per shape.  cams=None: sample_cameras(B, radius, seed, shape0).
     Row k of shape b is a uniformly drawn visible point of shape b (all points when two or fewer are visible, as the reference falls
-    back), plus `noise` * normal jitter clipped to [-1, 1] when noise > 0.  Shape b is seeded by (seed, shape0 + b) only."""
+    back), plus `noise` * normal jitter clipped to [-1, 1] when noise > 0.  Shape b is seeded by (seed, shape0 + b) only, so shape b of a
+    batch equals a single-shape call with shape0 + b.  A shape without points has count 0 and NaN rows."""
     x, o, _, _ = _prepare(X, np.zeros((X.shape[0] if X.dim() == 3 else (1 if off is None else len(off) - 1), 3)), off, "virtual_scan_dev")
     B = len(o) - 1
     c = sample_cameras(B, radius, seed, shape0) if cams is None else _cams(cams, B, "virtual_scan_dev")

@@ -37,7 +37,9 @@ def signed_distance_dev(queries, verts, faces, qoff=None, voff=None, toff=None, 
 
     queries (N,3), verts (V,3) f32 and faces (T,3) int HIP tensors; qoff / voff / toff (B+1,) exclusive offsets (None: one shape).
     -> S (N,) f32 signed distance (negative inside), I (N,) int32 closest face local to the shape, C (N,3) f32 closest point
-    (, W (N,) f32 winding number), status (B,) int32.  A shape with queries but no faces raises SfmiError."""
+    (, W (N,) f32 winding number), status (B,) int32: 0 ok, 1 the shape has no faces, 2 a face index outside the shape (its queries get
+    S = NaN, I = -1, C = NaN, W = 0).  A shape with queries but no faces raises SfmiError; a shape with neither is admitted and gets
+    status 1.  Bit-identical from run to run; a shape's results, W included, depend on that shape alone (include/sfmi.h)."""
     if not isinstance(queries, torch.Tensor) or queries.dim() != 2 or queries.shape[1] != 3:
         raise L.SfmiError("signed_distance_dev: queries must be an (N,3) torch tensor")
     vf, ff, vo, to = mesh_args(verts, faces, voff, toff, "signed_distance_dev")
@@ -63,7 +65,8 @@ def signed_distance_dev(queries, verts, faces, qoff=None, voff=None, toff=None, 
 
 def mesh_occupancy_dev(verts, faces, voff, toff, grid_dim=64, bbox=((-1.0,) * 3, (1.0,) * 3), return_status=False):
     """Inside test (|W| > 0.5) of every point of the makeGrid(bbox, [grid_dim]*3, mode="on", indexing="ij") lattice, generated in
-    the kernel (no G^3 query array).  -> (B, G, G, G) uint8 in data.make_grid's order (first axis slowest) (, status (B,))."""
+    the kernel (no G^3 query array).  -> (B, G, G, G) uint8 in data.make_grid's order (first axis slowest) (, status (B,)).
+    A shape without faces raises SfmiError.  A shape's lattice depends on that shape alone."""
     vf, ff, vo, to = mesh_args(verts, faces, voff, toff, "mesh_occupancy_dev")
     if (np.diff(to) == 0).any():
         raise L.SfmiError("mesh_occupancy_dev: a shape has no faces")

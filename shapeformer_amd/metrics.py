@@ -216,7 +216,8 @@ def sample_mesh_dev(verts, faces, voff, toff, n, seed=0, return_face=False):
     faces (T,3) int32 local per shape, host voff / toff (B+1,)).  Face by binary search of a counter-hash uniform of (seed, k)
     in the shape's f64 area CDF; barycentric weights 1-sqrt(u), sqrt(u)(1-v), sqrt(u) v (geoutil.sampleMesh).  Sample k of a
     shape depends on (seed, k) and that mesh only, so a batch equals per-shape calls.  Does not touch any global RNG.
-    -> points (B*n,3) f32, status (B,) int32 (1: zero / non-finite total area, its points NaN) (, face (B*n,) int32 local)."""
+    -> points (B*n,3) f32, status (B,) int32 (1: zero / non-finite total area, its points NaN) (, face (B*n,) int32 local).
+    A shape without faces raises SfmiError."""
     if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
         raise L.SfmiError("sample_mesh_dev: verts / faces must be torch tensors on the HIP device")
     if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:

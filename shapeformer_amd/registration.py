@@ -204,7 +204,7 @@ def evaluate_registration_dev(source, target, s_off=None, t_off=None, max_dist=N
     """Open3D's evaluate_registration for a batch of pairs under the given poses (None: identity): exactly icp_dev(max_iter=0).
     -> fitness (B,) f64 = inliers / source points, rmse (B,) f64 over the inliers, idx (N,) int32 the nearest target point of every
     transformed source point (local to its set), d2 (N,) f32 - the bits of metrics.nn_dist on the transformed cloud.  A pair with a
-    non-finite coordinate or pose keeps idx = -1, d2 = +inf."""
+    non-finite coordinate or pose keeps idx = -1, d2 = +inf.  An empty pair has fitness 0 and rmse 0."""
     st = _Icp("evaluate_registration_dev", source, target, s_off, t_off, max_dist, "point", None, pose, "pose")
     st.iterate(0, True)
     return st.fitness, st.rmse, st.idx, st.d2
@@ -750,8 +750,8 @@ def information_matrix_dev(source, target, s_off=None, t_off=None, max_dist=None
     correspondences of evaluate_registration_dev, and over its inliers info = sum G^T G with G = [-[q]x | I], q the target point - the
     point metric's J^T J of icp_step_dev with q in place of the moved source point.  max_dist may differ from pair to pair.
     -> info (B,6,6) f64 symmetric, count (B,) int32 (= info[:,5,5]), fitness (B,) f64, rmse (B,) f64; with `details` also flag (B,) int32:
-    1 for a pair with a non-finite coordinate or pose (info 0, count 0).  f64 sums in icp_dev's fixed order: a batch equals per-pair calls
-    bit for bit."""
+    1 for a pair with a non-finite coordinate or pose (info 0, count 0).  An empty pair has info 0, count 0 and flag 0.  f64 sums in
+    icp_dev's fixed order: a batch equals per-pair calls bit for bit."""
     st = _Icp("information_matrix_dev", source, target, s_off, t_off, max_dist, "point", None, pose, "pose")
     st.iterate(0, True)
     info, count, flag = _information(st)
@@ -868,8 +868,9 @@ def pose_graph_optimize_dev(nodes, src, tgt, transforms, infos, uncertain=None, 
     nodes (S,4,4) / (S,3,4) / (S,12) f64: the starting poses, scan frame -> frame of the graph's node 0 (which is held fixed); src, tgt
     (E,) integers: node indices local to the edge's graph; transforms (E,4,4): p_tgt = T p_src; infos (E,6,6) f64 information matrices;
     uncertain (E,): loop closures, which the line process may switch off; alive (E,): None = all.  n_off / e_off: (Bg+1,) offsets of
-    the graphs' nodes and edges (None: one graph); at most 32 nodes and 496 edges per graph.  transforms and infos are HIP tensors;
-    the rest may be host arrays.  mu: the line-process weight, one number, one per graph or a (Bg,) device tensor; <= 0: off.
+    the graphs' nodes and edges (None: one graph); between 1 and 32 nodes and at most 496 edges per graph: a graph without nodes raises
+    SfmiError (node 0 is the frame of the result), one node without edges comes back as given (0 iterations).  transforms and infos
+    are HIP tensors; the rest may be host arrays.  mu: the line-process weight, one number, one per graph or a (Bg,) device tensor; <= 0: off.
     The residual, the Jacobians, the line process and the loop are include/sfmi.h's (numpy: tests/posegraph_ref.py).
     -> poses (S,4,4) f64, l (E,) f64 the line-process weights under them (1 for certain edges), cost (Bg,), iterations (Bg,), status
     (Bg,) int32 (the module's table), all on the device; with `details` a dict(H, g, delta, lam) of the last solve follows.  A graph's

@@ -95,7 +95,7 @@ def test_exclude_self_skips_by_index_not_by_distance(dev):
 
 # ---- 3. the split path
 
-@pytest.mark.parametrize("k", [16, 64])
+@pytest.mark.parametrize("k", [8, 16, 32, 64])                           # every instance of knn_merge_kernel<K>
 def test_split_path(dev, split_case, k):
     p, q = split_case
     lib = L.lib()
@@ -132,6 +132,27 @@ def test_split_path_ties_and_exclude_self(dev):
     d2, idx = _np(*scan.knn_dev(qt, qt, 8, exclude_self=True))
     assert np.array_equal(idx[:, 0], (np.arange(40000) + 20000) % 40000) and np.all(d2[:, 0] == 0)
     R.check_order(d2, idx)
+
+
+@pytest.fixture(scope="module")
+def doubled():
+    """the 40000-point duplicated cloud of test_split_path_ties_and_exclude_self"""
+    return np.tile((np.random.RandomState(4).rand(20000, 3) - 0.5).astype(np.float32), (2, 1))
+
+
+@pytest.mark.parametrize("k", [16, 32, 64])
+def test_split_path_exclude_self(dev, doubled, k):
+    """exclude_self under a split for the other three merge instances: by the plan in knn.hip the 40000 x 40000 search is cut into
+    16, 7 and 5 chunks for K = 16, 32 and 64, so a point's duplicate lies in another chunk than the point"""
+    q = doubled
+    assert L.lib().sfmi_knn_workspace_bytes(1, 40000, 40000, k) > 40000 * k * 8              # this shape takes partial lists
+    qt = _t(q, dev)
+    d2, idx = _np(*scan.knn_dev(qt, qt, k, exclude_self=True))
+    assert np.array_equal(idx[:, 0], (np.arange(40000) + 20000) % 40000) and np.all(d2[:, 0] == 0)
+    assert np.array_equal(idx[:, 2], (idx[:, 1] + 20000) % 40000)        # the next neighbour's two copies, the lower index first
+    assert np.all(idx[:, 1] < 20000) and np.all(d2[:, 1] == d2[:, 2])
+    R.check_order(d2, idx)
+    R.check_ranks(d2, idx, q, q, k, exclude_self=True)
 
 
 # ---- 4. anchors inside the project
