@@ -1,6 +1,7 @@
-"""Shared pieces of the mesh tools, host side (the device side is csrc/sfmi_ragged.h).
+"""Shared pieces of the mesh and scan tools, host side (the device side is csrc/sfmi_ragged.h).
 
-Argument handling and small tensor idioms of metrics / meshsdf / hpr / iso_sparse / simplify / components / morph / make_dataset.
+Argument handling and small tensor idioms of metrics / meshsdf / hpr / iso_sparse / simplify / components / morph / make_dataset and of
+scan / poisson / registration.
 
 A ragged batch is B sets stored back to back with (B+1,) exclusive offsets: off[0] = 0, nondecreasing, off[B] = the row count; None
 means one set.  Every check here runs on the host and raises SfmiError before the library is loaded, so a refused call launches
@@ -39,10 +40,23 @@ def check_count(v, what, name, lo=1):
     return int(v)
 
 
+def check_number(v, what, name, lo, hi, lo_open=False, hi_open=False, allow_inf=False):
+    """-> float(v) for an int or a float, not a bool and not NaN, between lo and hi (each end closed unless *_open).  hi = inf: no upper
+    bound, and +inf itself passes only with allow_inf."""
+    inf = float("inf")
+    ok = not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+    if ok:
+        x = float(v)
+        ok = (x > lo if lo_open else x >= lo) and (x < hi if hi_open else x <= hi) and (allow_inf or x != inf)
+    if not ok:
+        want = (f"a {'' if allow_inf else 'finite '}number {'>' if lo_open else '>='} {lo:g}" if hi == inf else
+                f"a number in {'(' if lo_open else '['}{lo:g}, {hi:g}{')' if hi_open else ']'}")
+        raise L.SfmiError(f"{what}: {name} must be {want}, got {v!r}")
+    return x
+
+
 def check_nonneg(v, what, name):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < float("inf"):
-        raise L.SfmiError(f"{what}: {name} must be a finite number >= 0, got {v!r}")
-    return float(v)
+    return check_number(v, what, name, 0, float("inf"))
 
 
 def on_device(what, *tensors):
@@ -75,6 +89,34 @@ def point_sets(points, off, what):
     return x, host_offsets(off, x.shape[0], f"{what} offsets"), None
 
 
+def pair_offsets(a_off, n, b_off, m, what, names=("source", "target")):
+    """the offsets of two clouds of n and m rows that are cut into the same number of sets -> two host offset arrays of equal length.
+    names: what the caller calls the two clouds; their initials name the offsets (s_off / t_off, p_off / q_off)"""
+    ao, bo = host_offsets(a_off, n, f"{what} {names[0][0]}_off"), host_offsets(b_off, m, f"{what} {names[1][0]}_off")
+    if len(ao) != len(bo):
+        raise L.SfmiError(f"{what}: {names[0]} has {len(ao) - 1} sets, {names[1]} has {len(bo) - 1}")
+    return ao, bo
+
+
+def pair_sets(a, b, a_off, b_off, what, names=("source", "target"), max_sets=65535):
+    """Set i of a against set i of b: (N,3) / (M,3) clouds with offsets (pair_offsets), or (B,N,3) / (B,M,3) batches of equal B with both
+    offsets None -> (a as (N,3), b as (M,3), host offsets of a, of b, (B,N) or None).  max_sets: the launch bounds of the registration
+    kernels, at most that many pairs (a grid's y limit) and every set below 2^31 points; None: neither bound."""
+    a, b = points_arg(a, f"{what} {names[0]}"), points_arg(b, f"{what} {names[1]}")
+    shape = None
+    if a.dim() == 3 or b.dim() == 3:
+        if a.dim() != b.dim() or a.shape[0] != b.shape[0] or a_off is not None or b_off is not None:
+            raise L.SfmiError(f"{what}: a batched (B,N,3) {names[0]} needs a (B,M,3) {names[1]} of the same B and no offsets; "
+                              f"an (N,3) {names[0]} needs an (M,3) {names[1]}")
+        shape = tuple(a.shape[:2])
+        ao, bo = (np.arange(shape[0] + 1, dtype=np.int64) * x.shape[1] for x in (a, b))
+    else:
+        ao, bo = pair_offsets(a_off, a.shape[0], b_off, b.shape[0], what, names)
+    if max_sets is not None and (len(ao) - 1 > max_sets or (np.diff(ao) >= 2 ** 31).any() or (np.diff(bo) >= 2 ** 31).any()):
+        raise L.SfmiError(f"{what}: at most {max_sets} pairs, every set below 2^31 points")
+    return a.reshape(-1, 3), b.reshape(-1, 3), ao, bo, shape
+
+
 def mesh_args(verts, faces, voff, toff, what, index32=False, empty_ok=False, flatten_offsets=False):
     """A ragged batch of indexed meshes -> (verts f32 contiguous, faces int32 contiguous, host voff, host toff) after the host checks:
     tensors, (V,3) / (T,3), integer faces, offsets (host_offsets), equal shape counts, and the size bound - with index32 the whole batch
@@ -99,6 +141,11 @@ def mesh_args(verts, faces, voff, toff, what, index32=False, empty_ok=False, fla
 
 
 # ---- host arrays -> device tensors -----------------------------------------------------------------------------------------
+
+def offsets_dev(o, dev):
+    """host offsets -> (B+1,) int64 on dev"""
+    return torch.from_numpy(np.asarray(o, np.int64)).to(dev)
+
 
 def i32_dev(a, dev):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.int32))).to(dev)
@@ -135,6 +182,12 @@ def excl(x):
 def excl_at(incl, off):
     """exclusive prefix at the (B+1) offsets `off` of an inclusive prefix sum (its total at off[B])"""
     return torch.cat([incl.new_zeros(1), incl])[off.long()]
+
+
+def nonfinite_sets(x, od):
+    """x (N,C) rows cut by the offsets od (B+1,) on x's device -> (B,) int32: 1 for a set with a row that is not finite"""
+    z = excl_at(torch.cumsum((~torch.isfinite(x).all(1)).to(torch.int32), 0, dtype=torch.int32), od)
+    return ((z[1:] - z[:-1]) > 0).to(torch.int32)
 
 
 def runs(keys, n):

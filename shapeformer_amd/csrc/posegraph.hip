@@ -3,9 +3,11 @@
 // edges).  The reference has no such step: its real-scan datasets serve one cloud in one frame.  DESIGN.md §5.20; the contract is
 // stated in include/sfmi.h and restated in numpy in tests/posegraph_ref.py.
 //
-// 1. pg_info_kernel / pg_info_reduce_kernel: register.hip's accumulate / update pair for Lambda = sum G^T G, G = [-[q]x | I], over
-//    the inliers of correspondences the caller already has.  Ten f64 sums per pair (six quadratic entries, sum q, count), in §5.18's
-//    order: a lane's 4 points ascending, wave_sum_f64, the 4 waves in order, the chunk partials in ascending order by one wave per pair.
+// 1. pg_info_kernel / pg_info_reduce_kernel: Lambda = sum G^T G, G = [-[q]x | I], over the inliers (sfmi_inlier) of correspondences the
+//    caller already has.  Ten f64 sums per pair (six quadratic entries, sum q, count) through the code register.hip's accumulate /
+//    update pair runs, so in §5.18's order bit for bit (tests/test_search_shared_gpu.py): a lane's 4 points ascending, then
+//    sfmi_ragged.h's sfmi_chunk_partial (wave_sum_f64, the 4 waves in order) and, by one wave per pair, sfmi_chunk_total (the chunk
+//    partials in ascending order).  The finite checks are sfmi_pairs_finite and sfmi_pose_finite.
 // 2. pg_optimize_kernel: one workgroup per graph runs the whole Levenberg-Marquardt loop.  Per outer iteration: one lane per edge
 //    evaluates the residual, its Jacobian and the edge's 6 x 6 block M = l J^T Lambda J and b = l J^T Lambda r (J_tgt = -J_src, so one
 //    block serves the four places an edge touches); one lane per pair of free nodes adds the blocks of its edges in ascending edge
@@ -23,10 +25,6 @@
 
 namespace {
 
-constexpr int PI_THREADS = 256;
-constexpr int PI_WAVES = PI_THREADS / 64;
-constexpr int PI_R = 4;                          // points per lane
-constexpr int PI_CHUNK = PI_THREADS * PI_R;      // source points per partial: register.hip's IA_CHUNK
 constexpr int PI_NS = 10;                        // qy^2+qz^2 | -qx qy | -qx qz | qx^2+qz^2 | -qy qz | qx^2+qy^2 | qx | qy | qz | count
 
 constexpr int PG_THREADS = 256;
@@ -39,50 +37,28 @@ constexpr double PG_LAMBDA_MIN = 1e-12, PG_LAMBDA_MAX = 1e12;
 
 // ---- the information matrix ---------------------------------------------------------------------------------------------------------
 
-// grid (chunks of 256 x 4 items, pairs): bad[b] |= 1 when a source or target coordinate of the pair is not finite
-__global__ __launch_bounds__(256) void pg_check_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
-                                                       const long long* __restrict__ soff, const long long* __restrict__ toff,
-                                                       int* __restrict__ bad) {
-  const int b = blockIdx.y;
-  const long long s0 = soff[b], n = soff[b + 1] - s0, t0 = toff[b], m = toff[b + 1] - t0;
-  bool x = false;
-  for (int r = 0; r < 4; ++r) {
-    const long long i = ((long long)blockIdx.x * 4 + r) * 256 + threadIdx.x;
-    if (i < n) x |= !sfmi_finite3(src + 3 * (s0 + i));
-    if (i < m) x |= !sfmi_finite3(tgt + 3 * (t0 + i));
-  }
-  if (__any(x) && (threadIdx.x & 63) == 0) atomicOr(bad + b, 1);
-}
-
-__device__ __forceinline__ bool pg_pose_finite(const double* __restrict__ T) {
-  bool ok = true;
-  for (int e = 0; e < 12; ++e) ok = ok && isfinite(T[e]);
-  return ok;
-}
-
 // grid (source chunks, pairs): part[(b * gridDim.x + chunk) * 10 + e]
-__global__ __launch_bounds__(PI_THREADS) void pg_info_kernel(const float* __restrict__ Q, const long long* __restrict__ poff,
-                                                             const long long* __restrict__ qoff, const double* __restrict__ pose,
-                                                             const int* __restrict__ bad, const int* __restrict__ idx,
-                                                             const float* __restrict__ d2, const float* __restrict__ maxd2v,
-                                                             double* __restrict__ part) {
-  __shared__ double red[PI_WAVES][PI_NS];
+__global__ __launch_bounds__(SFMI_CHUNK_THREADS) void pg_info_kernel(
+    const float* __restrict__ Q, const long long* __restrict__ poff, const long long* __restrict__ qoff, const double* __restrict__ pose,
+    const int* __restrict__ bad, const int* __restrict__ idx, const float* __restrict__ d2, const float* __restrict__ maxd2v,
+    double* __restrict__ part) {
+  __shared__ double red[SFMI_CHUNK_THREADS / 64][PI_NS];
   const int b = blockIdx.y, tid = threadIdx.x;
-  if (bad[b] != 0 || !pg_pose_finite(pose + 12 * b)) return;  // block-uniform, before any barrier: the reduce writes zeros
+  if (bad[b] != 0 || !sfmi_pose_finite(pose + 12 * b)) return;  // block-uniform, before any barrier: the reduce writes zeros
   const long long p0 = poff[b], n = poff[b + 1] - p0;
-  if ((long long)blockIdx.x * PI_CHUNK >= n) return;           // block-uniform
+  if ((long long)blockIdx.x * SFMI_CHUNK >= n) return;         // block-uniform
   const long long q0 = qoff[b], m = qoff[b + 1] - q0;
   const float maxd2 = maxd2v[b];
   double acc[PI_NS];
 #pragma unroll
   for (int e = 0; e < PI_NS; ++e) acc[e] = 0.0;
 #pragma unroll
-  for (int r = 0; r < PI_R; ++r) {                             // a lane's points in ascending order
-    const long long i = (long long)blockIdx.x * PI_CHUNK + r * PI_THREADS + tid;
+  for (int r = 0; r < SFMI_CHUNK_R; ++r) {                     // a lane's points in ascending order
+    const long long i = (long long)blockIdx.x * SFMI_CHUNK + r * SFMI_CHUNK_THREADS + tid;
     if (i < n) {
       const int j = idx[p0 + i];
       const float d = d2[p0 + i];
-      if (j >= 0 && j < m && d <= maxd2) {                     // the index is checked before the point is read
+      if (sfmi_inlier(j, m, d, maxd2)) {                       // the index is checked before the point is read
         const float* q = Q + 3 * (q0 + j);
         const double ax = (double)q[0], ay = (double)q[1], az = (double)q[2];
         acc[0] += ay * ay + az * az;  acc[1] += -(ax * ay);  acc[2] += -(ax * az);
@@ -92,18 +68,7 @@ __global__ __launch_bounds__(PI_THREADS) void pg_info_kernel(const float* __rest
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < PI_NS; ++e) {
-    const double v = wave_sum_f64(acc[e]);
-    if ((tid & 63) == 0) red[tid >> 6][e] = v;
-  }
-  __syncthreads();
-  if (tid < PI_NS) {
-    double s = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < PI_WAVES; ++w) s += red[w][tid];       // the waves in order
-    part[((long long)b * gridDim.x + blockIdx.x) * PI_NS + tid] = s;
-  }
+  sfmi_chunk_partial(acc, red, part + ((long long)b * gridDim.x + blockIdx.x) * PI_NS);
 }
 
 // one wave per pair: lane e adds entry e of the chunk partials in ascending chunk order; lane 0 writes the 6 x 6 matrix
@@ -112,14 +77,9 @@ __global__ __launch_bounds__(64) void pg_info_reduce_kernel(const long long* __r
                                                             double* __restrict__ info, int* __restrict__ count, int* __restrict__ flag) {
   __shared__ double s[PI_NS];
   const int b = blockIdx.x, lane = threadIdx.x;
-  const bool ok = bad[b] == 0 && pg_pose_finite(pose + 12 * b);
+  const bool ok = bad[b] == 0 && sfmi_pose_finite(pose + 12 * b);
   const long long n = poff[b + 1] - poff[b];
-  const int nc = ok ? (int)cdiv(n, PI_CHUNK) : 0;
-  if (lane < PI_NS) {
-    double v = 0.0;
-    for (int c = 0; c < nc && c < chunks; ++c) v += part[((long long)b * chunks + c) * PI_NS + lane];
-    s[lane] = v;
-  }
+  if (lane < PI_NS) s[lane] = sfmi_chunk_total<PI_NS>(part, b, chunks, ok ? (int)cdiv(n, SFMI_CHUNK) : 0);
   __syncthreads();
   if (lane != 0) return;
   double* L = info + 36ll * b;
@@ -262,12 +222,6 @@ __device__ __forceinline__ double pg_edge(const double* xs, const double* xt, co
     }
   }
   return th;
-}
-
-__device__ __forceinline__ double pg_wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // the words every lane reads after a barrier
@@ -442,7 +396,7 @@ __global__ __launch_bounds__(PG_THREADS) void pg_optimize_kernel(PgArgs a) {
         if (tid < 64) {
           double m = 0.0;
           for (int i = tid; i < n; i += 64) m = fmax(m, Hg[i * (i + 1) / 2 + i]);
-          m = pg_wave_max_f64(m);
+          m = wave_max_f64(m);
           if (tid == 0) sVal[PG_V_LAM] = 1e-5 * m;
         }
         __syncthreads();
@@ -557,7 +511,7 @@ __global__ __launch_bounds__(PG_THREADS) void pg_optimize_kernel(PgArgs a) {
 
 extern "C" {
 
-int sfmi_pg_chunk(void) { return PI_CHUNK; }
+int sfmi_pg_chunk(void) { return SFMI_CHUNK; }
 int sfmi_pg_max_nodes(void) { return PG_MAX_NODES; }
 int sfmi_pg_max_edges(void) { return PG_MAX_EDGES; }
 
@@ -568,13 +522,11 @@ int sfmi_pg_information_f32(const float* src, const float* tgt, const long long*
       !pose || !maxd2 || !bad || !part || !info || !count || !flag || (N > 0 && (!src || !idx || !d2)) || (M > 0 && !tgt))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st) != hipSuccess) return SFMI_ELAUNCH;
-  const long long most = max_n > max_m ? max_n : max_m;
-  if (most > 0) hipLaunchKernelGGL(pg_check_kernel, dim3((unsigned)cdiv(most, 1024), (unsigned)B), dim3(256), 0, st, src, tgt, soff, toff, bad);
-  const int chunks = (int)(max_n > 0 ? cdiv(max_n, PI_CHUNK) : 1);
+  if (!sfmi_pairs_finite<false>(src, tgt, nullptr, soff, toff, nullptr, B, max_n, max_m, bad, st)) return SFMI_ELAUNCH;
+  const int chunks = (int)(max_n > 0 ? cdiv(max_n, SFMI_CHUNK) : 1);
   if (N > 0 && M > 0)
-    hipLaunchKernelGGL(pg_info_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(PI_THREADS), 0, st, tgt, soff, toff, pose, (const int*)bad, idx,
-                       d2, maxd2, part);
+    hipLaunchKernelGGL(pg_info_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(SFMI_CHUNK_THREADS), 0, st, tgt, soff, toff, pose,
+                       (const int*)bad, idx, d2, maxd2, part);
   hipLaunchKernelGGL(pg_info_reduce_kernel, dim3((unsigned)B), dim3(64), 0, st, soff, pose, (const int*)bad, (const double*)part,
                      (N > 0 && M > 0) ? chunks : 0, info, count, flag);
   SFMI_CHECK_LAUNCH();

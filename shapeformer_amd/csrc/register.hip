@@ -10,10 +10,11 @@
 //    When there are too few query blocks the target is cut into S chunks (grid.y) and the shared merge, skipping frozen pairs, merges
 //    them in ascending chunk order.
 // 2. icp_accumulate_kernel: grid (source chunks of 1024 points, pairs).  A lane gathers q (and n) of its 4 points, ascending, into
-//    29 f64 accumulators (the 21 upper entries of A = sum J^T J, the 6 of sum J^T r, sum d2, count); wave_sum_f64; the 4 waves in
-//    order; one partial per chunk.  Chunks start at the set's first point: a pair's sums do not depend on the batch around it.
-// 3. icp_update_kernel: one wave per pair.  Lane e adds entry e of the chunk partials in ascending chunk order; lane 0 takes the
-//    statistics, tests convergence, solves A xi = g by Cholesky, and writes the pose and the state.
+//    29 f64 accumulators (the 21 upper entries of A = sum J^T J, the 6 of sum J^T r, sum d2, count); sfmi_ragged.h's
+//    sfmi_chunk_partial ends the chunk: wave_sum_f64, the 4 waves in order, one partial per chunk.  Chunks start at the set's first
+//    point: a pair's sums do not depend on the batch around it.
+// 3. icp_update_kernel: one wave per pair.  Lane e adds entry e of the chunk partials in ascending chunk order (sfmi_chunk_total);
+//    lane 0 takes the statistics, tests convergence, solves A xi = g by Cholesky, and writes the pose and the state.
 // A pair that has ended (state != 0) is frozen: its workgroups leave at once (block-uniform exits, before any barrier) and none of
 // its outputs changes again, so the result does not depend on how often the host looks at the states.
 //
@@ -30,37 +31,13 @@ constexpr int IC_THREADS = SFMI_SCAN_TILE;
 constexpr int IC_R = 8;                          // queries per lane
 constexpr int IC_QB = IC_THREADS * IC_R;         // queries per workgroup
 constexpr int IC_TARGET_BLOCKS = 2048;           // 256 CUs x 8 workgroups
-constexpr int IA_THREADS = 256;
-constexpr int IA_WAVES = IA_THREADS / 64;
-constexpr int IA_R = 4;                          // points per lane
-constexpr int IA_CHUNK = IA_THREADS * IA_R;      // source points per partial
 constexpr int IC_NS = 29;                        // A (21, upper, row-major) | J^T r (6) | sum d2 | count
 constexpr int IC_SD2 = 27, IC_CNT = 28;
-constexpr int ICP_POINT = 0, ICP_PLANE = 1;
+constexpr int ICP_POINT = 0, ICP_PLANE = SFMI_METRIC_PLANE;
 
 inline int ic_splits(int B, long long N, long long M) { return sfmi_splits(B, N, M, IC_TARGET_BLOCKS, IC_QB); }
 
-// ---- start of a call ----------------------------------------------------------------------------------------------------------------
-
-// grid (chunks of 256 x 4 items, pairs): bad[b] |= 1 when a source, target or normal coordinate of the pair is not finite
-__global__ __launch_bounds__(256) void icp_check_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
-                                                        const float* __restrict__ nrm, const long long* __restrict__ soff,
-                                                        const long long* __restrict__ toff, const int* __restrict__ metric,
-                                                        int* __restrict__ bad) {
-  const int b = blockIdx.y;
-  const bool plane = metric[b] == ICP_PLANE;
-  const long long s0 = soff[b], n = soff[b + 1] - s0, t0 = toff[b], m = toff[b + 1] - t0;
-  bool x = false;
-  for (int r = 0; r < 4; ++r) {
-    const long long i = ((long long)blockIdx.x * 4 + r) * 256 + threadIdx.x;
-    if (i < n) x |= !sfmi_finite3(src + 3 * (s0 + i));
-    if (i < m) {
-      x |= !sfmi_finite3(tgt + 3 * (t0 + i));
-      if (plane) x |= !sfmi_finite3(nrm + 3 * (t0 + i));
-    }
-  }
-  if (__any(x) && (threadIdx.x & 63) == 0) atomicOr(bad + b, 1);
-}
+// ---- start of a call (the finite check of the pairs is sfmi_ragged.h's sfmi_pairs_finite) -------------------------------------------
 
 // one lane per pair: the state of iteration 0, and (lane 0) which query blocks belong to which pair
 __global__ void icp_begin_kernel(const long long* __restrict__ soff, const double* __restrict__ pose, const int* __restrict__ bad,
@@ -69,8 +46,7 @@ __global__ void icp_begin_kernel(const long long* __restrict__ soff, const doubl
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b == 0) sfmi_block_offsets(soff, block_off, B, IC_QB);
   if (b >= B) return;
-  bool ok = bad[b] == 0;
-  for (int e = 0; e < 12; ++e) ok = ok && isfinite(pose[12 * b + e]);
+  const bool ok = bad[b] == 0 && sfmi_pose_finite(pose + 12 * b);
   state[b] = ok ? 0 : 1;
   status[b] = ok ? 1 : 4;
   iterations[b] = 0;
@@ -136,17 +112,15 @@ __device__ __forceinline__ void ia_add(double (&acc)[IC_NS], double ax, double a
 }
 
 // grid (source chunks, pairs): part[(b * gridDim.x + chunk) * 29 + e].  metric[b] and maxd2[b] are the pair's: workgroup-uniform
-__global__ __launch_bounds__(IA_THREADS) void icp_accumulate_kernel(const float* __restrict__ P, const float* __restrict__ Q,
-                                                                    const float* __restrict__ Nrm, const long long* __restrict__ poff,
-                                                                    const long long* __restrict__ qoff, const double* __restrict__ pose,
-                                                                    const int* __restrict__ state, const int* __restrict__ idx,
-                                                                    const float* __restrict__ d2, const int* __restrict__ metric,
-                                                                    const float* __restrict__ maxd2v, double* __restrict__ part) {
-  __shared__ double red[IA_WAVES][IC_NS];
+__global__ __launch_bounds__(SFMI_CHUNK_THREADS) void icp_accumulate_kernel(
+    const float* __restrict__ P, const float* __restrict__ Q, const float* __restrict__ Nrm, const long long* __restrict__ poff,
+    const long long* __restrict__ qoff, const double* __restrict__ pose, const int* __restrict__ state, const int* __restrict__ idx,
+    const float* __restrict__ d2, const int* __restrict__ metric, const float* __restrict__ maxd2v, double* __restrict__ part) {
+  __shared__ double red[SFMI_CHUNK_THREADS / 64][IC_NS];
   const int b = blockIdx.y, tid = threadIdx.x;
   if (state[b] != 0) return;                                   // a frozen pair: block-uniform, before any barrier
   const long long p0 = poff[b], n = poff[b + 1] - p0;
-  if ((long long)blockIdx.x * IA_CHUNK >= n) return;           // block-uniform
+  if ((long long)blockIdx.x * SFMI_CHUNK >= n) return;         // block-uniform
   const long long q0 = qoff[b], m = qoff[b + 1] - q0;
   const double* T = pose + 12 * b;
   const bool plane = metric[b] == ICP_PLANE;
@@ -155,12 +129,12 @@ __global__ __launch_bounds__(IA_THREADS) void icp_accumulate_kernel(const float*
 #pragma unroll
   for (int e = 0; e < IC_NS; ++e) acc[e] = 0.0;
 #pragma unroll
-  for (int r = 0; r < IA_R; ++r) {                             // a lane's points in ascending order
-    const long long i = (long long)blockIdx.x * IA_CHUNK + r * IA_THREADS + tid;
+  for (int r = 0; r < SFMI_CHUNK_R; ++r) {                     // a lane's points in ascending order
+    const long long i = (long long)blockIdx.x * SFMI_CHUNK + r * SFMI_CHUNK_THREADS + tid;
     if (i < n) {
       const int j = idx[p0 + i];
       const float d = d2[p0 + i];
-      if (j >= 0 && j < m && d <= maxd2) {                     // the index is checked before the point is read
+      if (sfmi_inlier(j, m, d, maxd2)) {                       // the index is checked before the point is read
         const double x = (double)P[3 * (p0 + i)], y = (double)P[3 * (p0 + i) + 1], z = (double)P[3 * (p0 + i) + 2];
         const double ax = (double)sfmi_pose_row(T, x, y, z), ay = (double)sfmi_pose_row(T + 4, x, y, z),
                      az = (double)sfmi_pose_row(T + 8, x, y, z);
@@ -176,18 +150,7 @@ __global__ __launch_bounds__(IA_THREADS) void icp_accumulate_kernel(const float*
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < IC_NS; ++e) {
-    const double v = wave_sum_f64(acc[e]);
-    if ((tid & 63) == 0) red[tid >> 6][e] = v;
-  }
-  __syncthreads();
-  if (tid < IC_NS) {
-    double s = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < IA_WAVES; ++w) s += red[w][tid];       // the waves in order
-    part[((long long)b * gridDim.x + blockIdx.x) * IC_NS + tid] = s;
-  }
+  sfmi_chunk_partial(acc, red, part + ((long long)b * gridDim.x + blockIdx.x) * IC_NS);
 }
 
 // ---- the step -----------------------------------------------------------------------------------------------------------------------
@@ -234,10 +197,8 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const long long* __restr
   if (state[b] != 0) return;                                   // frozen: the whole wave leaves
   const long long n = poff[b + 1] - poff[b];
   const int metric = metricv[b];
-  const int nc = (int)cdiv(n, IA_CHUNK);                       // <= chunks
   if (lane < IC_NS) {
-    double v = 0.0;
-    for (int c = 0; c < nc && c < chunks; ++c) v += part[((long long)b * chunks + c) * IC_NS + lane];   // ascending chunk order
+    const double v = sfmi_chunk_total<IC_NS>(part, b, chunks, (int)cdiv(n, SFMI_CHUNK));   // ascending chunk order
     s[lane] = v;
     sums[(long long)b * IC_NS + lane] = v;
   }
@@ -316,7 +277,7 @@ __global__ void icp_transform_kernel(const float* __restrict__ P, const long lon
 extern "C" {
 
 int sfmi_icp_query_block(void) { return IC_QB; }
-int sfmi_icp_chunk(void) { return IA_CHUNK; }
+int sfmi_icp_chunk(void) { return SFMI_CHUNK; }
 int sfmi_icp_splits(int B, long long N, long long M) { return (B <= 0 || N < 0 || M < 0) ? 0 : ic_splits(B, N, M); }
 
 int sfmi_icp_transform_f32(const float* P, const long long* off, const double* pose, int B, long long N, float* out, void* stream) {
@@ -335,10 +296,7 @@ int sfmi_icp_begin_f32(const float* src, const float* tgt, const float* nrm, con
       !pose || !metric || !bad || !block_off || !state || !status || !iterations || !fitness || !rmse || (N > 0 && !src) || (M > 0 && !tgt))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st) != hipSuccess) return SFMI_ELAUNCH;
-  const long long most = max_n > max_m ? max_n : max_m;
-  if (most > 0)
-    hipLaunchKernelGGL(icp_check_kernel, dim3((unsigned)cdiv(most, 1024), (unsigned)B), dim3(256), 0, st, src, tgt, nrm, soff, toff, metric, bad);
+  if (!sfmi_pairs_finite<true>(src, tgt, nrm, soff, toff, metric, B, max_n, max_m, bad, st)) return SFMI_ELAUNCH;
   hipLaunchKernelGGL(icp_begin_kernel, dim3(blocks256(B)), dim3(256), 0, st, soff, pose, (const int*)bad, B, block_off, state, status,
                      iterations, fitness, rmse);
   SFMI_CHECK_LAUNCH();
@@ -357,7 +315,7 @@ int sfmi_icp_iterate_f32(const float* src, const float* tgt, const float* nrm, c
   hipStream_t st = (hipStream_t)stream;
   const int S = ic_splits(B, N, M);
   if (N > 0 && S > 1 && (!part_d2 || !part_idx)) return SFMI_EINVAL;
-  const int chunks = (int)(max_n > 0 ? cdiv(max_n, IA_CHUNK) : 1);
+  const int chunks = (int)(max_n > 0 ? cdiv(max_n, SFMI_CHUNK) : 1);
   if (N > 0) {
     const dim3 grid((unsigned)sfmi_qblocks(B, N, IC_QB), (unsigned)S);
     if (S == 1) {
@@ -369,7 +327,7 @@ int sfmi_icp_iterate_f32(const float* src, const float* tgt, const float* nrm, c
       sfmi_nn_merge<true, true>(part_d2, part_idx, soff, state, B, S, N, d2, idx, st);   // a frozen pair's (idx, d2) stay
     }
     const dim3 agrid((unsigned)chunks, (unsigned)B);
-    hipLaunchKernelGGL(icp_accumulate_kernel, agrid, dim3(IA_THREADS), 0, st, src, tgt, nrm, soff, toff, (const double*)pose,
+    hipLaunchKernelGGL(icp_accumulate_kernel, agrid, dim3(SFMI_CHUNK_THREADS), 0, st, src, tgt, nrm, soff, toff, (const double*)pose,
                        (const int*)state, (const int*)idx, (const float*)d2, metric, maxd2, part);
   }
   hipLaunchKernelGGL(icp_update_kernel, dim3((unsigned)B), dim3(64), 0, st, soff, (const double*)part, chunks, metric, k, last, rel_fitness,

@@ -1,5 +1,5 @@
 // Shared pieces of the mesh and scan tools: what csrc/pointdist.hip, meshsdf.hip, hpr.hip, iso_sparse.hip, simplify.hip,
-// components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip, global_register.hip and tangent.hip need
+// components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip, global_register.hip, posegraph.hip and tangent.hip need
 // for ragged batches (the split nearest-neighbour search of the scan tools is sfmi_search.h, which includes this file).  A ragged batch
 // is B sets stored back to back with (B+1) nondecreasing offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b
 // with off[b] <= x < off[b+1].  Everything here is inlined into its caller.  A caller's `#pragma clang fp contract(off)` comes after
@@ -90,8 +90,8 @@ __device__ __forceinline__ double wave_max_f64(double v) {
 
 // the sum over a workgroup of WAVES waves (a power of two; 16 in orient_kernel, rf_kernel and greg_refit_kernel) in every lane:
 // wave_sum_f64, then the WAVES wave sums through the same xor tree.  red: WAVES doubles of LDS; every lane of the workgroup calls.
-// NOT the order of poisson.hip's cg_block_sum ((r0 + r1) + (r2 + r3)) nor of icp_accumulate_kernel (the waves in order): each of the
-// three is a different f64 rounding fixed by its numpy restatement, so those two stay where they are.
+// NOT the order of poisson.hip's cg_block_sum ((r0 + r1) + (r2 + r3)) nor of sfmi_chunk_partial below (the waves in order): each of
+// the three is a different f64 rounding fixed by its numpy restatement, so the three stay three.
 template <int WAVES>
 __device__ __forceinline__ double sfmi_block_sum_f64(double v, double* red) {
   v = wave_sum_f64(v);
@@ -171,6 +171,85 @@ __device__ __forceinline__ bool sfmi_centroid_f64(const float* __restrict__ Pb, 
 __device__ __forceinline__ float sfmi_pose_row(const double* __restrict__ T, double x, double y, double z) {
 #pragma clang fp contract(off)
   return (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+}
+
+__device__ __forceinline__ bool sfmi_pose_finite(const double* __restrict__ T) {
+  bool ok = true;
+  for (int e = 0; e < 12; ++e) ok = ok && isfinite(T[e]);
+  return ok;
+}
+
+// is correspondence (j, d) of a pair whose target set has m points an inlier?  The index is tested here, before the caller reads the
+// point it names.
+__device__ __forceinline__ bool sfmi_inlier(int j, long long m, float d, float maxd2) { return j >= 0 && j < m && d <= maxd2; }
+
+// ---- the chunked f64 sums of register.hip (29 entries per pair) and posegraph.hip (10): DESIGN.md §5.18's order -------------------------
+// A workgroup of 4 waves takes a chunk of 1024 source points, 4 per lane, counted from the pair's first point, so a pair's sums do not
+// depend on the batch around it.  sfmi_icp_chunk() and sfmi_pg_chunk() report this size: the host sizes `part` by it.
+constexpr int SFMI_CHUNK_THREADS = 256;
+constexpr int SFMI_CHUNK_R = 4;                  // points per lane, taken in ascending order
+constexpr int SFMI_CHUNK = SFMI_CHUNK_THREADS * SFMI_CHUNK_R;
+constexpr int SFMI_METRIC_PLANE = 1;             // include/sfmi.h's metric code of point-to-plane ICP
+
+// the end of a chunk: wave_sum_f64 per entry, lane 0 of each wave into red, the WAVES waves added in order by lanes < NS, which store
+// the chunk's partial out[e].  Sums only: nothing here contracts.  Every lane of the workgroup calls (one barrier).
+template <int NS, int WAVES>
+__device__ __forceinline__ void sfmi_chunk_partial(const double (&acc)[NS], double (&red)[WAVES][NS], double* __restrict__ out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < NS; ++e) {
+    const double v = wave_sum_f64(acc[e]);
+    if ((tid & 63) == 0) red[tid >> 6][e] = v;
+  }
+  __syncthreads();
+  if (tid < NS) {
+    double s = red[0][tid];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) s += red[w][tid];          // the waves in order
+    out[tid] = s;
+  }
+}
+
+// entry threadIdx.x (< NS) of pair b: its chunk partials added in ascending chunk order.  nc: the pair's own chunks (<= chunks, the
+// row length of part)
+template <int NS>
+__device__ __forceinline__ double sfmi_chunk_total(const double* __restrict__ part, int b, int chunks, int nc) {
+  double v = 0.0;
+  for (int c = 0; c < nc && c < chunks; ++c) v += part[((long long)b * chunks + c) * NS + threadIdx.x];
+  return v;
+}
+
+// grid (chunks of 256 x 4 items, pairs): bad[b] |= 1 when a source or target coordinate of the pair is not finite; with NORMALS also
+// a target normal of a pair whose metric[b] is the plane metric (without, nrm and metric are not read)
+template <bool NORMALS>
+static __global__ __launch_bounds__(SFMI_CHUNK_THREADS) void sfmi_pairs_finite_kernel(
+    const float* __restrict__ src, const float* __restrict__ tgt, const float* __restrict__ nrm, const long long* __restrict__ soff,
+    const long long* __restrict__ toff, const int* __restrict__ metric, int* __restrict__ bad) {
+  const int b = blockIdx.y;
+  const bool plane = NORMALS && metric[b] == SFMI_METRIC_PLANE;
+  const long long s0 = soff[b], n = soff[b + 1] - s0, t0 = toff[b], m = toff[b + 1] - t0;
+  bool x = false;
+  for (int r = 0; r < SFMI_CHUNK_R; ++r) {
+    const long long i = ((long long)blockIdx.x * SFMI_CHUNK_R + r) * SFMI_CHUNK_THREADS + threadIdx.x;
+    if (i < n) x |= !sfmi_finite3(src + 3 * (s0 + i));
+    if (i < m) {
+      x |= !sfmi_finite3(tgt + 3 * (t0 + i));
+      if (plane) x |= !sfmi_finite3(nrm + 3 * (t0 + i));
+    }
+  }
+  if (__any(x) && (threadIdx.x & 63) == 0) atomicOr(bad + b, 1);
+}
+
+// bad[0 .. B) <- 0, then the kernel above over the largest set of the batch.  false: the memset was refused
+template <bool NORMALS>
+inline bool sfmi_pairs_finite(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
+                              const int* metric, int B, long long max_n, long long max_m, int* bad, hipStream_t st) {
+  if (hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st) != hipSuccess) return false;
+  const long long most = max_n > max_m ? max_n : max_m;
+  if (most > 0)
+    hipLaunchKernelGGL(sfmi_pairs_finite_kernel<NORMALS>, dim3((unsigned)((most + SFMI_CHUNK - 1) / SFMI_CHUNK), (unsigned)B),
+                       dim3(SFMI_CHUNK_THREADS), 0, st, src, tgt, nrm, soff, toff, metric, bad);
+  return true;
 }
 
 // ---- RANSAC over hypotheses (segment.hip's planes, global_register.hip's poses): integer counts, so the result is a function of the input

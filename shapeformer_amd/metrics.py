@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import f32_dev, host_offsets, on_device, points_arg
+from ._ragged import f32_dev, host_offsets, offsets_dev, on_device, pair_sets, points_arg
 
 
 # ---- nearest neighbours over ragged sets (the argument checks are _ragged.py's: DESIGN.md §5.5a) ----------------------------
@@ -35,7 +35,7 @@ def _launch_nn(pf, qf, po, qo, want_index):
     idx = torch.empty(N, device=dev, dtype=torch.int32) if want_index else None
     if N == 0:
         return d2, idx
-    pod, qod = torch.from_numpy(po).to(dev), torch.from_numpy(qo).to(dev)
+    pod, qod = offsets_dev(po, dev), offsets_dev(qo, dev)
     ws = torch.empty(max(int(lib.sfmi_nn_dist_workspace_bytes(B, N, M)), 1), device=dev, dtype=torch.uint8)
     L.check(lib.sfmi_nn_dist_f32(L.ptr(pf), L.ptr(qf), L.ptr(pod), L.ptr(qod), B, N, M, L.ptr(d2), L.ptr(idx), L.ptr(ws),
                                  L.stream_ptr()), "sfmi_nn_dist_f32")
@@ -49,27 +49,14 @@ def nn_dist(p, q, p_off=None, q_off=None, return_index=False):
     batches (set b of p against set b of q; offsets must then be None).  -> d2 (N,) f32 (or (B,N)) and, with return_index, the
     int32 index of that nearest point local to its set of q: the lowest index among equal f32 distances.  Bit-identical from
     run to run.  A set of q with no points while its set of p has some raises SfmiError."""
-    p, q = points_arg(p, "nn_dist p"), points_arg(q, "nn_dist q")
-    batched = p.dim() == 3
-    if batched:
-        if q.dim() != 3 or q.shape[0] != p.shape[0] or p_off is not None or q_off is not None:
-            raise L.SfmiError("nn_dist: batched (B,N,3) inputs need a (B,M,3) q of the same B and no offsets")
-        B, n, m = p.shape[0], p.shape[1], q.shape[1]
-        po, qo = np.arange(B + 1, dtype=np.int64) * n, np.arange(B + 1, dtype=np.int64) * m
-    else:
-        if q.dim() != 2:
-            raise L.SfmiError("nn_dist: (N,3) p needs an (M,3) q")
-        po, qo = host_offsets(p_off, p.shape[0], "nn_dist p_off"), host_offsets(q_off, q.shape[0], "nn_dist q_off")
-        if len(po) != len(qo):
-            raise L.SfmiError(f"nn_dist: p has {len(po) - 1} sets, q has {len(qo) - 1}")
+    p, q, po, qo, shape = pair_sets(p, q, p_off, q_off, "nn_dist", ("p", "q"), None)
     if ((np.diff(qo) == 0) & (np.diff(po) > 0)).any():
         raise L.SfmiError("nn_dist: a reference set is empty while its query set is not")
     on_device("nn_dist", p, q)
-    pf, qf = p.reshape(-1, 3).float().contiguous(), q.reshape(-1, 3).float().contiguous()
-    d2, idx = _launch_nn(pf, qf, po, qo, return_index)
-    if batched:
-        d2 = d2.reshape(p.shape[0], p.shape[1])
-        idx = idx.reshape(p.shape[0], p.shape[1]) if idx is not None else None
+    d2, idx = _launch_nn(p.float().contiguous(), q.float().contiguous(), po, qo, return_index)
+    if shape:
+        d2 = d2.reshape(shape)
+        idx = idx.reshape(shape) if idx is not None else None
     return (d2, idx) if return_index else d2
 
 
@@ -236,7 +223,7 @@ def sample_mesh_dev(verts, faces, voff, toff, n, seed=0, return_face=False):
     out = torch.empty(B * n, 3, device=dev, dtype=torch.float32)
     face = torch.empty(B * n, device=dev, dtype=torch.int32) if return_face else None
     status = torch.empty(B, device=dev, dtype=torch.int32)
-    vod, tod = torch.from_numpy(vo).to(dev), torch.from_numpy(to).to(dev)
+    vod, tod = offsets_dev(vo, dev), offsets_dev(to, dev)
     ws = torch.empty(int(lib.sfmi_mesh_sample_workspace_bytes(B, T)), device=dev, dtype=torch.uint8)
     L.check(lib.sfmi_mesh_sample_f32(L.ptr(vf), L.ptr(ff), L.ptr(vod), L.ptr(tod), B, T, n, int(seed) & (2 ** 64 - 1), L.ptr(ws),
                                      L.ptr(out), L.ptr(face), L.ptr(status), L.stream_ptr()), "sfmi_mesh_sample_f32")

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import host_offsets, on_device, point_sets, points_arg
+from ._ragged import host_offsets, offsets_dev, on_device, point_sets, points_arg
 
 MIN_GRID, MAX_GRID = 5, 513
 DEFAULT_BBOX = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
@@ -123,7 +123,7 @@ def _splat(xf, nf, o, R, box):
     """checked, contiguous f32 device arrays -> Vx, Vy, Vz, W, outside"""
     lib, st, dev = L.lib(), L.stream_ptr, xf.device
     B, N, C = len(o) - 1, xf.shape[0], R - 1
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     f32 = dict(device=dev, dtype=torch.float32)
     Vx, Vy, Vz = torch.empty(B, C, R, R, **f32), torch.empty(B, R, C, R, **f32), torch.empty(B, R, R, C, **f32)
     W = torch.empty(B, R, R, R, **f32)
@@ -224,7 +224,7 @@ def poisson_solve_dev(rhs, tol=1e-4, max_iter=None, check_every=16):
 def _sample(lat, xf, o, box):
     B, R, N = lat.shape[0], lat.shape[1], xf.shape[0]
     out = torch.empty(N, device=lat.device, dtype=torch.float32)
-    od = torch.from_numpy(np.asarray(o, np.int64)).to(lat.device)
+    od = offsets_dev(o, lat.device)
     L.check(L.lib().sfmi_poisson_sample_f32(L.ptr(lat), L.ptr(xf), L.ptr(od), B, N, R, L.ptr(box), L.ptr(out), L.stream_ptr()),
             "sfmi_poisson_sample_f32")
     return out
@@ -255,7 +255,7 @@ def _field(xf, nf, o, R, box, tol, max_iter):
     del Vx, Vy, Vz
     chi, iters, res = _solve(rhs, tol, max_iter, 16)
     iso = torch.empty(B, device=dev, dtype=torch.float64)
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     L.check(lib.sfmi_poisson_iso_f32(L.ptr(chi), L.ptr(xf), L.ptr(od), B, N, R, L.ptr(box), L.ptr(iso), L.ptr(chi), L.stream_ptr()),
             "sfmi_poisson_iso_f32")
     return chi, W, dict(iterations=iters, residual=res, iso=iso, outside=outside)
@@ -298,7 +298,7 @@ def _trim(verts, faces, vo, to, density, q):
     for b in range(B):
         if vo[b + 1] > vo[b]:
             thr[b] = _np_quantile(torch.sort(d64[int(vo[b]):int(vo[b + 1])]).values, q)
-    vod, tod = torch.from_numpy(np.asarray(vo, np.int64)).to(dev), torch.from_numpy(np.asarray(to, np.int64)).to(dev)
+    vod, tod = offsets_dev(vo, dev), offsets_dev(to, dev)
     vshape = torch.repeat_interleave(torch.arange(B, device=dev), vod[1:] - vod[:-1], output_size=verts.shape[0])
     fshape = torch.repeat_interleave(torch.arange(B, device=dev), tod[1:] - tod[:-1], output_size=faces.shape[0])
     keep = d64 >= thr[vshape]

@@ -56,16 +56,21 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import check_count, check_nonneg, excl_at, host_offsets, i32_dev, on_device, point_sets, points_arg, set_ids
+from ._ragged import (check_count, check_nonneg, check_number, excl_at, host_offsets, i32_dev, nonfinite_sets, offsets_dev, on_device,
+                      pair_offsets, pair_sets, point_sets, points_arg, set_ids)
 
 METRICS = ("point", "plane")
 N_SUMS = 29
 
 
+def _identity_poses(B):
+    return np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float64), (B, 1))
+
+
 def _pose_arg(pose, B, what, name="pose"):
     """None (identity), (B,4,4), (B,3,4), (B,12) or, for one pair, (4,4) / (3,4) / (12,) -> (B,12) f64 numpy or torch tensor"""
     if pose is None:
-        return np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float64), (B, 1))
+        return _identity_poses(B)
     p = pose.detach().to(torch.float64) if isinstance(pose, torch.Tensor) else np.asarray(pose, np.float64)
     if B == 1 and tuple(p.shape) in ((4, 4), (3, 4), (12,)):
         p = p[None]
@@ -103,9 +108,11 @@ def _per_pair(v, B, what, name, conv, expect):
 
 
 def _check_tol(v, what, name):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not float(v) >= 0:
-        raise L.SfmiError(f"{what}: {name} must be a number >= 0, got {v!r}")
-    return float(v)
+    return check_number(v, what, name, 0, float("inf"), allow_inf=True)
+
+
+def _check_unit(v, what, name):
+    return check_number(v, what, name, 0, 1)
 
 
 def transform_points_dev(points, off=None, pose=None):
@@ -120,7 +127,7 @@ def transform_points_dev(points, off=None, pose=None):
     xf = x.float().contiguous()
     out = torch.empty_like(xf)
     if B > 0 and N > 0:
-        pd, od = _pose_dev(p, dev), torch.from_numpy(o).to(dev)
+        pd, od = _pose_dev(p, dev), offsets_dev(o, dev)
         L.check(L.lib().sfmi_icp_transform_f32(L.ptr(xf), L.ptr(od), L.ptr(pd), B, N, L.ptr(out), L.stream_ptr()), "sfmi_icp_transform_f32")
     return out.reshape(*shape, 3) if shape else out
 
@@ -129,22 +136,10 @@ class _Icp:
     """The device state of one call: validated arguments, the pose and the per-pair outputs; `iterate` runs one iteration."""
 
     def __init__(self, what, source, target, s_off, t_off, max_dist, metric, target_normals, init, pose_name="init"):
-        s, t = points_arg(source, f"{what} source"), points_arg(target, f"{what} target")
-        if s.dim() == 3 or t.dim() == 3:
-            if s.dim() != 3 or t.dim() != 3 or s.shape[0] != t.shape[0] or s_off is not None or t_off is not None:
-                raise L.SfmiError(f"{what}: batched (B,N,3) sources need a (B,M,3) target of the same B and no offsets")
-            B = s.shape[0]
-            so, to = np.arange(B + 1, dtype=np.int64) * s.shape[1], np.arange(B + 1, dtype=np.int64) * t.shape[1]
-        else:
-            so, to = host_offsets(s_off, s.shape[0], f"{what} s_off"), host_offsets(t_off, t.shape[0], f"{what} t_off")
-            if len(so) != len(to):
-                raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+        s, t, so, to, _ = pair_sets(source, target, s_off, t_off, what)
         B = len(so) - 1
         if B < 1:
             raise L.SfmiError(f"{what}: expected at least one pair")
-        if B > 65535 or (np.diff(so) >= 2 ** 31).any() or (np.diff(to) >= 2 ** 31).any():
-            raise L.SfmiError(f"{what}: at most 65535 pairs, every set below 2^31 points")
-        s, t = s.reshape(-1, 3), t.reshape(-1, 3)
         metrics = _per_pair(metric, B, what, "metric", lambda m: m if isinstance(m, str) and m in METRICS else None,
                             f"one of {METRICS}")
         dists = _per_pair(max_dist, B, what, "max_dist", lambda v: check_nonneg(v, what, "max_dist"), "a finite number >= 0")
@@ -164,7 +159,7 @@ class _Icp:
         self.max_n, self.max_m = int(np.diff(so).max()), int(np.diff(to).max())
         self.src, self.tgt = s.float().contiguous(), t.float().contiguous()
         self.nrm = n.float().contiguous() if n is not None else None
-        self.sod, self.tod = torch.from_numpy(so).to(dev), torch.from_numpy(to).to(dev)
+        self.sod, self.tod = offsets_dev(so, dev), offsets_dev(to, dev)
         self.pose = _pose_dev(p, dev)
         lib = self.lib = L.lib()
         i32 = dict(device=dev, dtype=torch.int32)
@@ -262,8 +257,7 @@ def icp_multiscale_dev(source, target, s_off=None, t_off=None, voxels=(0.04, 0.0
         check_nonneg(m, what, "max_dists")
     s, so, _ = point_sets(source, s_off, f"{what} source")
     t, to, _ = point_sets(target, t_off, f"{what} target")
-    if len(so) != len(to):
-        raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+    pair_offsets(so, s.shape[0], to, t.shape[0], what)
     pose = _pose_arg(init, len(so) - 1, what, "init")
     on_device(what, s, t)
     out = None
@@ -286,9 +280,7 @@ def _radius_arg(radius, what, name="radius"):
     """None, or a finite number > 0 -> (use_radius, f32(radius^2)) rounded as radius_outlier_mask_dev rounds its radius"""
     if radius is None:
         return 0, 0.0
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not 0 < float(radius) < float("inf"):
-        raise L.SfmiError(f"{what}: {name} must be None or a finite number > 0, got {radius!r}")
-    return 1, float(np.float32(float(radius) ** 2))
+    return 1, float(np.float32(check_number(radius, what, name, 0, float("inf"), lo_open=True) ** 2))
 
 
 def _normals_arg(normals, x, what):
@@ -301,7 +293,7 @@ def _fpfh_stage2(o, idx, d2, spfh, m, k, use, r2, dev):
     B, N = len(o) - 1, idx.shape[0]
     out = torch.empty(N, FPFH_BINS, device=dev, dtype=torch.float32)
     if N:
-        od = torch.from_numpy(o).to(dev)
+        od = offsets_dev(o, dev)
         L.check(L.lib().sfmi_fpfh_features_f32(L.ptr(od), L.ptr(idx), L.ptr(d2), L.ptr(spfh), L.ptr(m), B, N, k, use, r2, L.ptr(out),
                                                L.stream_ptr()), "sfmi_fpfh_features_f32")
     return out
@@ -314,7 +306,7 @@ def _fpfh_from_knn(xf, nf, o, idx, d2, k, use, r2):
     spfh = torch.empty(N, FPFH_BINS, device=dev, dtype=torch.int32)
     m = torch.empty(N, device=dev, dtype=torch.int32)
     if N:
-        od = torch.from_numpy(o).to(dev)
+        od = offsets_dev(o, dev)
         L.check(L.lib().sfmi_fpfh_spfh_f32(L.ptr(xf), L.ptr(nf), L.ptr(od), L.ptr(idx), L.ptr(d2), B, N, k, use, r2, L.ptr(spfh), L.ptr(m),
                                            L.stream_ptr()), "sfmi_fpfh_spfh_f32")
     return _fpfh_stage2(o, idx, d2, spfh, m, k, use, r2, dev), spfh, m
@@ -378,7 +370,7 @@ def _feature_nn(fa, fb, ao, bo, splits, q):
     S = splits if splits else int(lib.sfmi_fpfh_nn_splits(B, N, M, q))
     pd = torch.empty(S * N, device=dev, dtype=torch.float32) if S > 1 else None
     pi = torch.empty(S * N, device=dev, dtype=torch.int32) if S > 1 else None
-    aod, bod, kod = (torch.from_numpy(v).to(dev) for v in (ao, bo, block_off))
+    aod, bod, kod = (offsets_dev(v, dev) for v in (ao, bo, block_off))
     L.check(lib.sfmi_fpfh_nn_f32(L.ptr(fa), L.ptr(fb), L.ptr(aod), L.ptr(bod), L.ptr(kod), B, N, M, int(block_off[-1]), S, q, L.ptr(idx),
                                  L.ptr(d2), L.ptr(pd), L.ptr(pi), L.stream_ptr()), "sfmi_fpfh_nn_f32")
     return idx, d2
@@ -394,9 +386,7 @@ def match_features_dev(fs, ft, s_off=None, t_off=None, mutual=True, splits=None,
     the result does not depend on them."""
     what = "match_features_dev"
     fs, ft = _features_arg(fs, what, "fs"), _features_arg(ft, what, "ft")
-    so, to = host_offsets(s_off, fs.shape[0], f"{what} s_off"), host_offsets(t_off, ft.shape[0], f"{what} t_off")
-    if len(so) != len(to):
-        raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+    so, to = pair_offsets(s_off, fs.shape[0], t_off, ft.shape[0], what)
     if len(so) - 1 > 65535 or (np.diff(so) >= 2 ** 31).any() or (np.diff(to) >= 2 ** 31).any():
         raise L.SfmiError(f"{what}: at most 65535 pairs, every set below 2^31 rows")
     if splits is not None and (isinstance(splits, bool) or not isinstance(splits, (int, np.integer)) or not 1 <= int(splits) <= 64):
@@ -408,7 +398,7 @@ def match_features_dev(fs, ft, s_off=None, t_off=None, mutual=True, splits=None,
     fs, ft = fs.float().contiguous(), ft.float().contiguous()
     idx, d2 = _feature_nn(fs, ft, so, to, S, q)
     N = fs.shape[0]
-    sod, tod = torch.from_numpy(so).to(dev), torch.from_numpy(to).to(dev)
+    sod, tod = offsets_dev(so, dev), offsets_dev(to, dev)
     sid = set_ids(so, dev)
     local = torch.arange(N, device=dev) - sod[sid]
     keep = idx >= 0
@@ -433,19 +423,10 @@ class _Greg:
     """The validated arguments of one RANSAC call on the device"""
 
     def __init__(self, what, source, target, s_off, t_off, corr, c_off):
-        s, t = points_arg(source, f"{what} source"), points_arg(target, f"{what} target")
-        if s.dim() == 3 or t.dim() == 3:
-            if s.dim() != 3 or t.dim() != 3 or s.shape[0] != t.shape[0] or s_off is not None or t_off is not None:
-                raise L.SfmiError(f"{what}: batched (B,N,3) sources need a (B,M,3) target of the same B and no offsets")
-            B = s.shape[0]
-            so, to = np.arange(B + 1, dtype=np.int64) * s.shape[1], np.arange(B + 1, dtype=np.int64) * t.shape[1]
-        else:
-            so, to = host_offsets(s_off, s.shape[0], f"{what} s_off"), host_offsets(t_off, t.shape[0], f"{what} t_off")
-            if len(so) != len(to):
-                raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+        s, t, so, to, _ = pair_sets(source, target, s_off, t_off, what)
         B = len(so) - 1
-        if B < 1 or B > 65535 or (np.diff(so) >= 2 ** 31).any() or (np.diff(to) >= 2 ** 31).any():
-            raise L.SfmiError(f"{what}: between 1 and 65535 pairs, every set below 2^31 points")
+        if B < 1:
+            raise L.SfmiError(f"{what}: expected at least one pair")
         if not isinstance(corr, torch.Tensor) or corr.dim() != 2 or corr.shape[1] != 2 or corr.dtype.is_floating_point or corr.dtype == torch.bool:
             raise L.SfmiError(f"{what}: corr must be a (C,2) integer tensor of (source index, target index)")
         co = host_offsets(c_off, corr.shape[0], f"{what} c_off")
@@ -454,23 +435,19 @@ class _Greg:
         if corr.shape[0] and (s.numel() == 0 or t.numel() == 0):
             raise L.SfmiError(f"{what}: corr names points of empty clouds")
         self.B, self.so, self.to, self.co = B, so, to, co
-        self.s, self.t, self.corr = s.reshape(-1, 3), t.reshape(-1, 3), corr
+        self.s, self.t, self.corr = s, t, corr
 
     def to_device(self, what, *more):
         dev = self.dev = on_device(what, self.s, self.t, self.corr, *more)
         self.s, self.t = self.s.float().contiguous(), self.t.float().contiguous()
         self.corr = self.corr.to(torch.int32).contiguous()
-        self.sod, self.tod, self.cod = (torch.from_numpy(v).to(dev) for v in (self.so, self.to, self.co))
+        self.sod, self.tod, self.cod = (offsets_dev(v, dev) for v in (self.so, self.to, self.co))
         self.max_c = int(np.diff(self.co).max())
         return dev
 
     def bad_pairs(self):
         """(B,) int32: a coordinate of the pair is not finite"""
-        out = torch.zeros(self.B, device=self.dev, dtype=torch.int32)
-        for x, od in ((self.s, self.sod), (self.t, self.tod)):
-            z = excl_at(torch.cumsum((~torch.isfinite(x).all(1)).to(torch.int32), 0, dtype=torch.int32), od)
-            out |= ((z[1:] - z[:-1]) > 0).to(torch.int32)
-        return out
+        return nonfinite_sets(self.s, self.sod) | nonfinite_sets(self.t, self.tod)
 
     def poses(self, trd, similarity):
         H = trd.shape[1]
@@ -518,12 +495,6 @@ def _triples_dev(tr, dev):
     return (tr if isinstance(tr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tr)).to(dev)).to(torch.int32).contiguous()
 
 
-def _check_similarity(v, what):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) <= 1:
-        raise L.SfmiError(f"{what}: similarity must be a number in [0, 1], got {v!r}")
-    return float(v)
-
-
 def _maxd2(max_dist, what):
     return float(np.float32(check_nonneg(max_dist, what, "max_dist") ** 2))
 
@@ -534,7 +505,7 @@ def hypothesis_poses_dev(source, target, s_off=None, t_off=None, corr=None, c_of
     what = "hypothesis_poses_dev"
     a = _Greg(what, source, target, s_off, t_off, corr, c_off)
     tr = _triples_arg(triples, a.B, what)
-    sim = _check_similarity(similarity, what)
+    sim = _check_unit(similarity, what, "similarity")
     dev = a.to_device(what, *([tr] if isinstance(tr, torch.Tensor) else []))
     return a.poses(_triples_dev(tr, dev), sim)
 
@@ -557,7 +528,7 @@ def score_poses_dev(source, target, s_off=None, t_off=None, corr=None, c_off=Non
 
 def _ransac(what, a, max_dist, hypotheses, seed, triples, similarity, refit, extra_bad=None):
     maxd2 = _maxd2(max_dist, what)
-    sim = _check_similarity(similarity, what)
+    sim = _check_unit(similarity, what, "similarity")
     tr = (correspondence_hypotheses(np.diff(a.co), check_count(hypotheses, what, "hypotheses"), seed) if triples is None
           else _triples_arg(triples, a.B, what))
     dev = a.to_device(what, *([tr] if isinstance(tr, torch.Tensor) else []))
@@ -605,7 +576,7 @@ def _oriented_normals(x, o, k, viewpoint):
         return estimate_normals_dev(x, o, k, viewpoint)[0]
     n = estimate_normals_dev(x, o, k)[0].contiguous()
     if x.shape[0]:
-        od = torch.from_numpy(o).to(x.device)
+        od = offsets_dev(o, x.device)
         L.check(L.lib().sfmi_fpfh_orient_f32(L.ptr(x), L.ptr(od), len(o) - 1, x.shape[0], L.ptr(n), L.stream_ptr()), "sfmi_fpfh_orient_f32")
     return n
 
@@ -621,8 +592,7 @@ def global_registration_dev(source, target, s_off=None, t_off=None, voxel=None, 
     what = "global_registration_dev"
     s, so, _ = point_sets(source, s_off, f"{what} source")
     t, to, _ = point_sets(target, t_off, f"{what} target")
-    if len(so) != len(to):
-        raise L.SfmiError(f"{what}: source has {len(so) - 1} sets, target has {len(to) - 1}")
+    pair_offsets(so, s.shape[0], to, t.shape[0], what)
     if not 1 <= len(so) - 1 <= 65535:
         raise L.SfmiError(f"{what}: between 1 and 65535 pairs")
     if voxel is not None:
@@ -653,10 +623,7 @@ def global_registration_dev(source, target, s_off=None, t_off=None, voxel=None, 
     corr, co, _, _ = match_features_dev(fs, ft, so, to, mutual)
     a = _Greg(what, s, t, so, to, corr, co)
     a.to_device(what)
-    extra = torch.zeros(a.B, device=a.dev, dtype=torch.int32)
-    for v, od in ((ns, a.sod), (fs, a.sod), (nt, a.tod), (ft, a.tod)):
-        z = excl_at(torch.cumsum((~torch.isfinite(v).all(1)).to(torch.int32), 0, dtype=torch.int32), od)
-        extra |= ((z[1:] - z[:-1]) > 0).to(torch.int32)
+    extra = nonfinite_sets(ns, a.sod) | nonfinite_sets(fs, a.sod) | nonfinite_sets(nt, a.tod) | nonfinite_sets(ft, a.tod)
     return _ransac(what, a, max_dist, ransac.get("hypotheses", 4096), ransac.get("seed", 0), ransac.get("triples"),
                    ransac.get("similarity", 0.9), ransac.get("refit", True), extra)[0]
 
@@ -674,31 +641,18 @@ def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, multiway=No
     multiway: a dict of multiway_registration_dev's arguments (max_dists, pairs, global_init, ICP options ...): the poses come from the
     pose graph over all pairs instead of the star onto scan 0, for captures in which not every scan overlaps scan 0; every other
     registration argument then goes into that dict.  None: the star."""
-    from .scan import voxel_downsample_dev
+    from .scan import _check_voxel, voxel_downsample_dev
     what = "merge_scans_dev"
     if multiway is not None and (not isinstance(multiway, dict) or global_init is not None or icp):
         raise L.SfmiError(f"{what}: multiway must be a dict of multiway_registration_dev arguments; global_init and the ICP options go inside it")
     if global_init is not None and (not isinstance(global_init, dict) or "init" in icp):
         raise L.SfmiError(f"{what}: global_init must be a dict of global_registration_dev arguments and replaces init")
-    if voxel is not None and not (isinstance(voxel, (int, float, np.integer, np.floating)) and not isinstance(voxel, bool) and 0 < float(voxel) < float("inf")):
-        raise L.SfmiError(f"{what}: voxel must be a finite number > 0, got {voxel!r}")
-    if isinstance(clouds, (list, tuple)):
-        if offs is not None or not clouds:
-            raise L.SfmiError(f"{what}: a non-empty list of clouds takes no offsets")
-        parts = [points_arg(c, what) for c in clouds]
-        if any(c.dim() != 2 for c in parts):
-            raise L.SfmiError(f"{what}: every cloud must be (n,3)")
-        o = np.concatenate([[0], np.cumsum([c.shape[0] for c in parts])]).astype(np.int64)
-        on_device(what, *parts)
-        x = torch.cat([c.float() for c in parts]).contiguous()
-    else:
-        x = points_arg(clouds, what)
-        if x.dim() != 2:
-            raise L.SfmiError(f"{what}: expected a list of (n,3) clouds or (N,3) points with offsets")
-        o = host_offsets(offs, x.shape[0], f"{what} offs")
-        on_device(what, x)
-        x = x.float().contiguous()
-    S, dev = len(o) - 1, x.device
+    if voxel is not None:
+        voxel = _check_voxel(voxel, what)
+    parts, o = _scans_arg(clouds, offs, what)
+    dev = on_device(what, *parts)
+    x = (torch.cat([c.float() for c in parts]) if len(parts) > 1 else parts[0].float()).contiguous()
+    S = len(o) - 1
     poses = torch.eye(4, device=dev, dtype=torch.float64).repeat(S, 1, 1)
     status = np.zeros(S, np.int32)
     first = x[:int(o[1])]
@@ -722,7 +676,7 @@ def merge_scans_dev(clouds, offs=None, voxel=None, global_init=None, multiway=No
     else:
         merged = first
     if voxel is not None and merged.shape[0]:
-        merged = voxel_downsample_dev(merged, None, float(voxel))[0]
+        merged = voxel_downsample_dev(merged, None, voxel)[0]
     return merged, poses, status
 
 
@@ -779,12 +733,6 @@ def _edge_flags(v, E, what, name, default):
     return (a != 0).astype(np.int32)
 
 
-def _check_unit(v, what, name):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) <= 1:
-        raise L.SfmiError(f"{what}: {name} must be a number in [0, 1], got {v!r}")
-    return float(v)
-
-
 class _Graph:
     """The validated arguments of one optimiser call: a ragged batch of pose graphs"""
 
@@ -829,7 +777,7 @@ class _Graph:
         self.Lam = f64(self.Lam).reshape(self.E, 36).contiguous()
         self.unc, self.alive = i32(self.unc), i32(self.alive)
         self.src, self.tgt = i32_dev(self.srch, dev), i32_dev(self.tgth, dev)
-        self.nod, self.eod = torch.from_numpy(self.no).to(dev), torch.from_numpy(self.eo).to(dev)
+        self.nod, self.eod = offsets_dev(self.no, dev), offsets_dev(self.eo, dev)
         return dev
 
     def run(self, X, alive, mu, max_iter, tol):
@@ -856,9 +804,7 @@ class _Graph:
 
 def _graph_opts(what, max_iter, tol):
     max_iter = check_count(max_iter, what, "max_iter", 0)
-    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not 0 <= float(tol) < float("inf"):
-        raise L.SfmiError(f"{what}: tol must be a finite number >= 0, got {tol!r}")
-    return max_iter, float(tol)
+    return max_iter, check_nonneg(tol, what, "tol")
 
 
 def pose_graph_optimize_dev(nodes, src, tgt, transforms, infos, uncertain=None, alive=None, n_off=None, e_off=None, mu=0.0, max_iter=100,
@@ -941,7 +887,7 @@ def _walk(S, edges, T):
         A = a.reshape(3, 4)
         return np.concatenate([A[:, :3].T, -(A[:, :3].T @ A[:, 3])[:, None]], 1).reshape(12)
 
-    X = np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float64), (S, 1))
+    X = _identity_poses(S)
     seen, queue = np.zeros(S, bool), [0]
     seen[0] = True
     while queue:

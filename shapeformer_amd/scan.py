@@ -37,8 +37,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._ragged import (check_count, check_nonneg, excl_at, host_offsets, on_device, point_sets, points_arg, run_starts, set_ids,
-                      sorted_runs)
+from ._ragged import (check_count, check_nonneg, check_number, excl_at, offsets_dev, on_device, pair_sets, point_sets, points_arg,
+                      run_starts, set_ids, sorted_runs)
 
 MAX_K = 64
 
@@ -58,7 +58,7 @@ def _launch_knn(pf, qf, po, qo, k, exclude_self):
     idx = torch.empty(N, k, device=dev, dtype=torch.int32)
     if N == 0:
         return d2, idx
-    pod, qod = torch.from_numpy(po).to(dev), torch.from_numpy(qo).to(dev)
+    pod, qod = offsets_dev(po, dev), offsets_dev(qo, dev)
     ws = torch.empty(max(int(lib.sfmi_knn_workspace_bytes(B, N, M, k)), 1), device=dev, dtype=torch.uint8)
     L.check(lib.sfmi_knn_f32(L.ptr(pf), L.ptr(qf), L.ptr(pod), L.ptr(qod), B, N, M, k, int(bool(exclude_self)), L.ptr(d2), L.ptr(idx),
                              L.ptr(ws), L.stream_ptr()), "sfmi_knn_f32")
@@ -77,19 +77,7 @@ def knn_dev(p, q, k, p_off=None, q_off=None, exclude_self=False):
     A set of q that is empty while its set of p is not raises SfmiError.  Bit-identical from run to run; with exclude_self=False
     column 0 equals metrics.nn_dist(..., return_index=True) bit for bit."""
     k = _check_k(k, "knn_dev")
-    p, q = points_arg(p, "knn_dev p"), points_arg(q, "knn_dev q")
-    batched = p.dim() == 3
-    if batched:
-        if q.dim() != 3 or q.shape[0] != p.shape[0] or p_off is not None or q_off is not None:
-            raise L.SfmiError("knn_dev: batched (B,N,3) inputs need a (B,M,3) q of the same B and no offsets")
-        B, n, m = p.shape[0], p.shape[1], q.shape[1]
-        po, qo = np.arange(B + 1, dtype=np.int64) * n, np.arange(B + 1, dtype=np.int64) * m
-    else:
-        if q.dim() != 2:
-            raise L.SfmiError("knn_dev: (N,3) p needs an (M,3) q")
-        po, qo = host_offsets(p_off, p.shape[0], "knn_dev p_off"), host_offsets(q_off, q.shape[0], "knn_dev q_off")
-        if len(po) != len(qo):
-            raise L.SfmiError(f"knn_dev: p has {len(po) - 1} sets, q has {len(qo) - 1}")
+    p, q, po, qo, shape = pair_sets(p, q, p_off, q_off, "knn_dev", ("p", "q"), None)
     if exclude_self and not np.array_equal(po, qo):
         raise L.SfmiError("knn_dev: exclude_self needs p and q to be the same sets (equal sizes and offsets)")
     if ((np.diff(qo) == 0) & (np.diff(po) > 0)).any():
@@ -97,11 +85,8 @@ def knn_dev(p, q, k, p_off=None, q_off=None, exclude_self=False):
     if (np.diff(qo) >= 2 ** 31).any():
         raise L.SfmiError("knn_dev: a reference set has 2^31 points or more")
     on_device("knn_dev", p, q)
-    pf, qf = p.reshape(-1, 3).float().contiguous(), q.reshape(-1, 3).float().contiguous()
-    d2, idx = _launch_knn(pf, qf, po, qo, k, exclude_self)
-    if batched:
-        d2, idx = d2.reshape(p.shape[0], p.shape[1], k), idx.reshape(p.shape[0], p.shape[1], k)
-    return d2, idx
+    d2, idx = _launch_knn(p.float().contiguous(), q.float().contiguous(), po, qo, k, exclude_self)
+    return (d2.reshape(*shape, k), idx.reshape(*shape, k)) if shape else (d2, idx)
 
 
 def _self_knn(points, off, k, what, exclude_self=True):
@@ -131,7 +116,7 @@ def knn_mean_dist_dev(points, off, k):
 
 def _counts(keep, o):
     """per-set sums of a (N,) uint8 mask -> (B,) int32 on the device"""
-    z = excl_at(torch.cumsum(keep, 0, dtype=torch.int32), torch.from_numpy(o).to(keep.device))
+    z = excl_at(torch.cumsum(keep, 0, dtype=torch.int32), offsets_dev(o, keep.device))
     return (z[1:] - z[:-1]).to(torch.int32)
 
 
@@ -187,7 +172,7 @@ def estimate_normals_dev(points, off=None, k=16, viewpoint=None, orient=None):
     _, idx = _launch_knn(xf, xf, o, o, k, False)
     normal = torch.empty(N, 3, device=dev, dtype=torch.float32)
     variation = torch.empty(N, device=dev, dtype=torch.float32)
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     vd = torch.from_numpy(view).to(dev) if view is not None else None
     L.check(L.lib().sfmi_knn_normals_f32(L.ptr(xf), L.ptr(od), L.ptr(idx), B, N, k, L.ptr(vd), L.ptr(normal), L.ptr(variation),
                                          L.stream_ptr()), "sfmi_knn_normals_f32")
@@ -225,7 +210,7 @@ def _orient_launch(what, xf, nf, o, idx, vd):
     rounds = torch.zeros(B, device=dev, dtype=torch.int32)
     if N and B:
         lib = L.lib()
-        od = torch.from_numpy(o).to(dev)
+        od = offsets_dev(o, dev)
         status = torch.empty(B, device=dev, dtype=torch.int32)
         ws = torch.empty(max(int(lib.sfmi_tangent_workspace_bytes(B, N)), 256), device=dev, dtype=torch.uint8)
         L.check(lib.sfmi_tangent_forest_f32(L.ptr(nf), L.ptr(od), L.ptr(idx), B, N, k, _max_n(o), L.ptr(component), L.ptr(tree),
@@ -293,7 +278,7 @@ def orient_normals_dev(points, normals, off=None, k=16, idx=None, anchor="outwar
         return out
     N = xf.shape[0]
     if N:
-        local = torch.arange(N, device=dev) - torch.from_numpy(o).to(dev)[set_ids(o, dev)]
+        local = torch.arange(N, device=dev) - offsets_dev(o, dev)[set_ids(o, dev)]
         r["n_components"] = _counts((r["component"].long() == local).to(torch.uint8), o)
     else:
         r["n_components"] = torch.zeros(B, device=dev, dtype=torch.int32)
@@ -399,7 +384,7 @@ def farthest_point_sample_dev(points, off=None, n=None, start=None, valid=None):
     lib = L.lib()
     xf = _aligned16(x.float().contiguous())
     vd = valid.reshape(-1).contiguous() if valid is not None else None
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     sd = torch.from_numpy(st).to(dev) if st is not None else None
     ws = torch.empty(max(int(lib.sfmi_fps_workspace_bytes(B, N, n)), 16), device=dev, dtype=torch.uint8)
     L.check(lib.sfmi_fps_f32(L.ptr(xf), L.ptr(od), L.ptr(vd), L.ptr(sd), B, N, n, L.ptr(idx), L.ptr(d2), L.ptr(count), L.ptr(status),
@@ -408,9 +393,7 @@ def farthest_point_sample_dev(points, off=None, n=None, start=None, valid=None):
 
 
 def _check_voxel(voxel, what):
-    if isinstance(voxel, bool) or not isinstance(voxel, (int, float, np.integer, np.floating)) or not 0 < float(voxel) < float("inf"):
-        raise L.SfmiError(f"{what}: voxel must be a finite number > 0, got {voxel!r}")
-    return float(voxel)
+    return check_number(voxel, what, "voxel", 0, float("inf"), lo_open=True)
 
 
 def voxel_downsample_dev(points, off=None, voxel=None, pick="centroid"):
@@ -441,7 +424,7 @@ def voxel_downsample_dev(points, off=None, voxel=None, pick="centroid"):
                 torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.int32))
     lib = L.lib()
     xf = x.float().contiguous()
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     lo = torch.empty(B, 3, device=dev, dtype=torch.int32)
     keys = torch.empty(N, device=dev, dtype=torch.int64)
     status = torch.empty(1, device=dev, dtype=torch.int32)
@@ -565,7 +548,7 @@ def segment_plane_dev(points, off=None, threshold=0.01, hypotheses=1024, seed=0,
     dev = on_device(what, x, *([tr] if isinstance(tr, torch.Tensor) else []))
     xf = x.float().contiguous()
     trd = (tr if isinstance(tr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tr)).to(dev)).to(torch.int32).contiguous()
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     upd = torch.from_numpy(upa).to(dev) if upa is not None else None
     count = torch.empty(B, H, device=dev, dtype=torch.int32)
     best = torch.empty(B, device=dev, dtype=torch.int32)
@@ -604,7 +587,7 @@ def refit_plane_dev(points, off=None, plane=None, threshold=0.01, up=None):
     upa = _up_arg(up, B, what)
     dev = on_device(what, x)
     xf, seed = x.float().contiguous(), seed.to(dev).contiguous()
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     upd = torch.from_numpy(upa).to(dev) if upa is not None else None
     out = torch.empty(B, 4, device=dev, dtype=torch.float64)
     inlier = torch.empty(N, device=dev, dtype=torch.uint8)
@@ -660,7 +643,7 @@ def _cluster_roots(xf, o, r2):
     dev = xf.device
     root = torch.empty(xf.shape[0], device=dev, dtype=torch.int32)
     if xf.shape[0]:
-        od = torch.from_numpy(o).to(dev)
+        od = offsets_dev(o, dev)
         L.check(L.lib().sfmi_cluster_f32(L.ptr(xf), L.ptr(od), len(o) - 1, xf.shape[0], _max_n(o), r2, L.ptr(root), L.stream_ptr()),
                 "sfmi_cluster_f32")
     return root
@@ -692,7 +675,7 @@ def euclidean_clusters_dev(points, off=None, radius=None, min_points=1, return_r
     if N == 0:
         out = (root.clone(), torch.empty(0, device=dev, dtype=torch.int32), np.zeros(B + 1, np.int64))
         return out + (root,) if return_root else out
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     sid = set_ids(o, dev)
     g = root.long() + od[sid]                                                   # the root as a batch index
     size_at = torch.bincount(g, minlength=N)                                    # at a root: its cluster's size; elsewhere 0
@@ -858,7 +841,7 @@ def clean_cloud_dev(X, k=16, std_ratio=2.0, out_N=None, seed=0, voxel=None, resa
     dev = xf.device
     if B == 0 or xf.shape[0] == 0:
         return torch.zeros(B, n_out, 3, device=dev, dtype=torch.float32), count
-    od = torch.from_numpy(o).to(dev)
+    od = offsets_dev(o, dev)
     few = torch.repeat_interleave(count <= 2, od[1:] - od[:-1], output_size=xf.shape[0])        # the fallback: all the cloud's points
     idx, _, got, _ = farthest_point_sample_dev(xf, o, n_out, valid=keep | few.to(torch.uint8))
     r = torch.arange(n_out, device=dev)[None, :] % got.clamp(min=1).long()[:, None]

@@ -149,6 +149,130 @@ def test_point_sets(no_library):
         R.point_sets(p.reshape(15, 3), [0, 5, 10], "f")
 
 
+# ---- pairs of clouds
+
+def test_pair_sets_accepts(no_library):
+    g = torch.Generator().manual_seed(1)
+    a, b = torch.randn(7, 3, generator=g), torch.randn(9, 3, generator=g)
+    fa, fb, ao, bo, shape = R.pair_sets(a, b, [0, 3, 3, 7], torch.tensor([0, 4, 9, 9]), "f")          # flat clouds with offsets
+    assert fa.data_ptr() == a.data_ptr() and torch.equal(fa, a) and torch.equal(fb, b) and shape is None    # views, not copies
+    assert ao.dtype == bo.dtype == np.int64 and ao.tolist() == [0, 3, 3, 7] and bo.tolist() == [0, 4, 9, 9]
+    fa, fb, ao, bo, shape = R.pair_sets(a, b, None, None, "f")                                        # no offsets: one pair
+    assert ao.tolist() == [0, 7] and bo.tolist() == [0, 9] and shape is None
+    pa, pb = torch.randn(2, 5, 3, generator=g), torch.randn(2, 4, 3, generator=g)                     # two batches of equal B
+    fa, fb, ao, bo, shape = R.pair_sets(pa, pb, None, None, "f")
+    assert shape == (2, 5) and torch.equal(fa, pa.reshape(10, 3)) and torch.equal(fb, pb.reshape(8, 3))
+    assert ao.dtype == bo.dtype == np.int64 and ao.tolist() == [0, 5, 10] and bo.tolist() == [0, 4, 8]
+    fa, fb, ao, bo, shape = R.pair_sets(pa[:, :0], pb, None, None, "f")                               # empty sets
+    assert fa.shape == (0, 3) and ao.tolist() == [0, 0, 0] and shape == (2, 0)
+    ao, bo = R.pair_offsets([0, 2, 7], 7, np.array([0, 9, 9]), 9, "f", ("p", "q"))
+    assert ao.dtype == bo.dtype == np.int64 and ao.tolist() == [0, 2, 7] and bo.tolist() == [0, 9, 9]
+    assert [o.tolist() for o in R.pair_offsets(None, 7, None, 9, "f")] == [[0, 7], [0, 9]]
+
+
+def test_pair_sets_refuses(no_library):
+    a, b = torch.zeros(7, 3), torch.zeros(9, 3)
+    pa, pb = torch.zeros(2, 5, 3), torch.zeros(2, 4, 3)
+    for x, y, xo, yo in ((pa, b, None, None), (a, pb, None, None), (a, pb, None, [0, 4, 8]),      # mixed dimensions
+                         (pa, torch.zeros(3, 4, 3), None, None),                                  # unequal B
+                         (pa, pb, [0, 5, 10], None), (pa, pb, None, [0, 4, 8])):                  # offsets with batches
+        with pytest.raises(SfmiError, match=r"same B and no offsets.*\(N,3\) left needs an \(M,3\) right"):
+            R.pair_sets(x, y, xo, yo, "f", ("left", "right"))
+    with pytest.raises(SfmiError, match="^the_call: left has 2 sets, right has 1$"):                  # the caller's names
+        R.pair_sets(a, b, [0, 3, 7], None, "the_call", ("left", "right"))
+    with pytest.raises(SfmiError, match="source has 1 sets, target has 3"):
+        R.pair_sets(a, b, None, [0, 4, 4, 9], "f")
+    with pytest.raises(SfmiError, match="p has 1 sets, q has 2"):
+        R.pair_offsets(None, 7, [0, 4, 9], 9, "f", ("p", "q"))
+    with pytest.raises(SfmiError, match="f l_off.*end at 7"):                                         # the offsets are named by initials
+        R.pair_sets(a, b, [0, 3, 6], [0, 4, 9], "f", ("left", "right"))
+    with pytest.raises(SfmiError, match="f r_off.*integer"):
+        R.pair_sets(a, b, [0, 3, 7], [0.0, 4.0, 9.0], "f", ("left", "right"))
+    for bad, word in ((np.zeros((5, 3)), "torch tensor"), (torch.zeros(5, 2), r"\(N,3\)")):
+        with pytest.raises(SfmiError, match="f left.*" + word):
+            R.pair_sets(bad, b, None, None, "f", ("left", "right"))
+        with pytest.raises(SfmiError, match="f right.*" + word):
+            R.pair_sets(a, bad, None, None, "f", ("left", "right"))
+
+
+def test_pair_sets_bounds(no_library):
+    a, b = torch.zeros(4, 3), torch.zeros(4, 3)
+    assert R.pair_sets(a, b, [0, 1, 2, 4], [0, 2, 3, 4], "f", max_sets=3)[2].tolist() == [0, 1, 2, 4]
+    with pytest.raises(SfmiError, match="at most 2 pairs"):
+        R.pair_sets(a, b, [0, 1, 2, 4], [0, 2, 3, 4], "f", max_sets=2)
+    with pytest.raises(SfmiError, match="at most 2 pairs"):
+        R.pair_sets(torch.zeros(3, 2, 3), torch.zeros(3, 1, 3), None, None, "f", max_sets=2)
+    many = np.arange(65537 + 1)
+    row = torch.zeros(1, 3)
+    with pytest.raises(SfmiError, match="at most 65535 pairs"):                                       # the default: a grid's y limit
+        R.pair_sets(row.expand(65537, 3), row.expand(65537, 3), many, many, "f")
+    assert len(R.pair_sets(row.expand(65535, 3), row.expand(65535, 3), many[:65536], many[:65536], "f")[2]) == 65536
+    assert len(R.pair_sets(row.expand(65537, 3), row.expand(65537, 3), many, many, "f", max_sets=None)[2]) == 65538
+    # views: the sizes without the memory
+    with pytest.raises(SfmiError, match=r"below 2\^31 points"):
+        R.pair_sets(row.expand(2 ** 31, 3), row, None, None, "f")
+    with pytest.raises(SfmiError, match=r"below 2\^31 points"):
+        R.pair_sets(row, row.expand(2 ** 31 + 1, 3), [0, 0, 1], [0, 2 ** 31, 2 ** 31 + 1], "f")
+    assert R.pair_sets(row.expand(2 ** 31, 3), row, None, None, "f", max_sets=None)[2].tolist() == [0, 2 ** 31]
+
+
+# ---- numbers
+
+def test_check_number(no_library):
+    inf = float("inf")
+    assert R.check_number(2, "f", "x", 0, 5) == 2.0 and isinstance(R.check_number(2, "f", "x", 0, 5), float)
+    assert R.check_number(np.float32(0.5), "f", "x", 0, 1) == 0.5 and R.check_number(np.int64(1), "f", "x", 0, 1) == 1.0
+    for v in (True, False, "1", None, [1.0], np.array([1.0]), torch.tensor(1.0), 1j, float("nan"), np.float64("nan")):
+        with pytest.raises(SfmiError, match=r"^the_call: the_x must be a number in \[0, 5\], got "):
+            R.check_number(v, "the_call", "the_x", 0, 5)
+    for v in (-1e-300, -1, 5.000001, 6, inf, -inf):                                                   # both bounds
+        with pytest.raises(SfmiError, match="x must be"):
+            R.check_number(v, "f", "x", 0, 5)
+    # closed ends take the bound itself, open ends do not; the text says which
+    assert R.check_number(0, "f", "x", 0, 5) == 0.0 and R.check_number(5.0, "f", "x", 0, 5) == 5.0
+    with pytest.raises(SfmiError, match=r"in \(0, 5\]"):
+        R.check_number(0, "f", "x", 0, 5, lo_open=True)
+    with pytest.raises(SfmiError, match=r"in \[0, 5\)"):
+        R.check_number(5, "f", "x", 0, 5, hi_open=True)
+    assert R.check_number(5, "f", "x", 0, 5, lo_open=True) == 5.0 and R.check_number(0, "f", "x", 0, 5, hi_open=True) == 0.0
+    assert R.check_number(1e-300, "f", "x", 0, 5, lo_open=True, hi_open=True) == 1e-300
+    # no upper bound: +inf only with allow_inf, NaN never
+    assert R.check_number(1e308, "f", "x", 0, inf) == 1e308
+    with pytest.raises(SfmiError, match="x must be a finite number >= 0, got inf"):
+        R.check_number(inf, "f", "x", 0, inf)
+    with pytest.raises(SfmiError, match="x must be a finite number > 0, got 0"):
+        R.check_number(0, "f", "x", 0, inf, lo_open=True)
+    assert R.check_number(inf, "f", "x", 0, inf, allow_inf=True) == inf
+    for v in (float("nan"), -1, -inf, True):
+        with pytest.raises(SfmiError, match="x must be a number >= 0, got"):
+            R.check_number(v, "f", "x", 0, inf, allow_inf=True)
+    with pytest.raises(SfmiError, match="got inf"):                                                   # a finite hi keeps +inf out either way
+        R.check_number(inf, "f", "x", 0, 5, allow_inf=True)
+    assert R.check_nonneg(0, "f", "x") == 0.0
+    for v in (inf, -1e-9, True, float("nan")):
+        with pytest.raises(SfmiError, match="x must be a finite number >= 0"):
+            R.check_nonneg(v, "f", "x")
+
+
+# ---- which sets hold a row that is not finite
+
+def test_nonfinite_sets():
+    x = torch.zeros(7, 3)
+    od = R.offsets_dev(np.array([0, 3, 3, 7]), "cpu")                                                 # three sets, the middle one empty
+    assert od.dtype == torch.int64 and od.tolist() == [0, 3, 3, 7]
+    out = R.nonfinite_sets(x, od)
+    assert out.dtype == torch.int32 and out.tolist() == [0, 0, 0]
+    x[1, 2] = float("nan")
+    assert R.nonfinite_sets(x, od).tolist() == [1, 0, 0]
+    x[6, 0] = float("-inf")
+    assert R.nonfinite_sets(x, od).tolist() == [1, 0, 1]
+    x[1, 2] = 0.0
+    assert R.nonfinite_sets(x, od).tolist() == [0, 0, 1]
+    assert R.nonfinite_sets(x[:, :1], od).tolist() == [0, 0, 1]                                       # rows of any width
+    assert R.nonfinite_sets(x, R.offsets_dev([0, 7], "cpu")).tolist() == [1]
+    assert R.nonfinite_sets(x[:0], R.offsets_dev([0, 0], "cpu")).tolist() == [0]
+
+
 # ---- prefix sums and runs, against numpy
 
 @pytest.mark.parametrize("counts", [[], [0], [3], [0, 0, 0], [2, 0, 5, 1, 0, 0, 7], list(range(40))])

@@ -51,3 +51,36 @@ def test_one_set_of_bits_from_the_three_searches(dev, tgt_sizes, split):
     for b, (j, i) in enumerate(tie):
         assert i_nn[i] == j and d_nn[i] == 0.0                                # not the copy in the last slot
     assert (i_nn[:2049] < tgt_sizes[0]).all() and (i_nn >= 0).all() and np.isfinite(d_nn).all()
+
+
+PAIR_SIZES = (2049, 1024, 1, 0, 8)
+
+
+def test_information_matrix_and_icp_step_give_one_set_of_bits(dev):
+    """information_matrix_dev and icp_step_dev add their f64 sums with one piece of code (csrc/sfmi_ragged.h: sfmi_chunk_partial,
+    sfmi_chunk_total): a lane's 4 points ascending, the wave butterfly, the 4 waves in order, the chunk partials in
+    ascending order.  Five pairs: 3 chunks of 1024 source points, exactly one chunk, a single point, an empty pair (a chunk grid row
+    with nothing to do) and a pair with a NaN.  Each target is a copy of its source and the poses are the identity, so the moved point
+    is the f32 source exactly and every inlier has a = q: the point metric's J^T J of icp_step_dev (with a) and the information
+    matrix (with q) are sums of the same terms, and the 21 upper entries must agree bit for bit.  Every fourth source point of the
+    two large pairs is moved 10 units away and is no inlier, so lanes with nothing to add sit between lanes that add."""
+    so = _off(PAIR_SIZES)
+    N = int(so[-1])
+    src = np.random.RandomState(28).uniform(-0.8, 0.8, (N, 3)).astype(np.float32)
+    assert (src != 0).all()
+    tgt = src.copy()
+    for b in (0, 1):
+        src[so[b]:so[b + 1]:4, 0] += 10.0
+    tgt[so[4] + 3, 1] = np.nan
+    s, t = torch.from_numpy(src).to(dev), torch.from_numpy(tgt).to(dev)
+    _, _, sums, _, _, status = registration.icp_step_dev(s, t, so, so, 0.1)
+    info, count, _, _, flag = registration.information_matrix_dev(s, t, so, so, 0.1, details=True)
+    sums, status, info, count, flag = (x.cpu().numpy() for x in (sums, status, info, count, flag))
+    assert sums.dtype == info.dtype == np.float64 and sums.shape == (5, 29) and info.shape == (5, 6, 6)
+    iu = np.triu_indices(6)
+    for b in range(4):
+        assert np.array_equal(info[b][iu], sums[b, :21]), b
+        assert count[b] == sums[b, 28], b
+    assert count[:4].tolist() == [2049 - 513, 1024 - 256, 1, 0] and flag[:4].tolist() == [0, 0, 0, 0]
+    assert status[4] == 4 and flag[4] == 1
+    assert not info[4].any() and count[4] == 0
