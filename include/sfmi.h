@@ -1107,6 +1107,46 @@ int sfmi_tangent_forest_f32(const float* normal, const long long* off, const int
 int sfmi_tangent_apply_f32(const float* P, const float* normal, const long long* off, const int* component, const unsigned char* parity,
                            const double* viewpoint, int B, long long N, int* votes, float* out, void* workspace, void* stream);
 
+/* ---- Earth mover's distance between clouds of equal size: a deterministic auction (csrc/emd.hip).  Bertsekas' forward
+ *      auction in its Jacobi form with epsilon scaling, stated as a pure function of the inputs and restated in numpy in
+ *      tests/emd_ref.py.  The reference has no such metric: it scores completions with Chamfer distance only.
+ * Two collections of ragged sets: A (NA,3) f32 with aoff (SA+1) int64 [device], B (NB,3) f32 with boff (SB+1).  P pairs: pa / pb (P)
+ * int32 [device] index the collections (no point is copied per pair); poff (P+1) int64 [device] cuts the ragged outputs, with
+ * poff[p+1] - poff[p] = n_p = |A_pa| = |B_pb|, N = poff[P], 0 <= n_p <= max_n <= sfmi_emd_max_points() = 8192.
+ * Cost: c_ij = (double) sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))), (dx, dy, dz) = a_i - b_j in f32.
+ * Scale: lo / hi = the f32 minimum / maximum of each coordinate over the pair's two clouds; e = (double) hi - (double) lo; diag =
+ * sqrt((ex ex + ey ey) + ez ez) in f64, every operation rounded on its own.  eps_final = eps_rel diag, 1e-9 <= eps_rel <= 1.
+ * Phases: eps_0 = max(diag / 2, eps_final), eps_{k+1} = max(eps_k / 4, eps_final); the phase run at eps_final is the last.  Prices
+ * are f64, start at 0 and are kept from phase to phase; every assignment is cleared when a phase starts.
+ * Round: every unassigned i bids against the prices of the round's start: v_j = (-c_ij) - price_j; j1 = arg max v, the lowest j among
+ * equals; v2 = max v over j != j1 (n = 1: v2 = v1); bid = (price_j1 + (v1 - v2)) + eps.  Each object takes its largest bid, the lowest
+ * i among equals: the bid becomes its price, its previous owner is unassigned, the bidder owns it.  A phase ends when nobody is
+ * unassigned.  Both selections are maxima under a strict total order, so the result does not depend on how the work is split over
+ * lanes, waves, launches (chunk_rounds) or batches, bit for bit.
+ * Outputs: assign (N) int32 local to the set, a bijection; emd (P) f64 = S / n with S the sum of c[i, assign[i]] in this order: lane t
+ * of 1024 adds i = t, t + 1024, ... ascending, the 64 lanes of a wave through the xor butterfly (32, 16, .., 1), the 16 wave sums through
+ * the same butterfly (8, 4, 2, 1); rounds (P) int32 the total over the phases; eps_final (P) f64; price (N) f64 the final prices;
+ * status (P) int32: 0 done; 1 max_rounds reached (emd NaN, assign -1 where unassigned); 2 a coordinate that is not finite, or diag >=
+ * 2^63 (emd NaN, assign -1, price NaN); 3 sizes or indices the host wrapper refuses (|A| != |B|, n > max_n, an index outside its
+ * collection: emd and eps_final NaN, rounds 0, nothing else is written).  n = 0: emd NaN, status 0.  diag = 0: the identity, emd 0, status 0.
+ * Guarantee (Bertsekas, epsilon-complementary slackness): emd_opt <= emd <= emd_opt + eps_final.
+ * max_rounds <= 0: sfmi_emd_default_cap(n) = 320 n + 256 per pair.  chunk_rounds <= 0: sfmi_emd_default_chunk().  A launch runs at most
+ * chunk_rounds rounds per pair; finished pairs are frozen; the call reads one counter of unfinished pairs per launch (it synchronises
+ * the stream) and relaunches.  One workgroup per pair: pairs up to sfmi_emd_resident_max() = 2048 points keep their whole state in LDS,
+ * larger ones keep the bid slots in LDS and the rest in the workspace.  Integer atomics in LDS only.
+ * ticks (P,2) int64 or NULL: a timing for tools/kbench_emd.py and no part of the result: ticks of the device's 100 MHz clock that the
+ * pair's workgroup spent in rounds with fewer than 16 bidders, and in all rounds.
+ * workspace: sfmi_emd_workspace_bytes(P, N) bytes, 0 for arguments the call refuses. */
+int sfmi_emd_resident_max(void);
+int sfmi_emd_max_points(void);
+int sfmi_emd_default_cap(int n);
+int sfmi_emd_default_chunk(void);
+size_t sfmi_emd_workspace_bytes(int P, long long N);
+int sfmi_emd_f32(const float* A, const long long* aoff, int SA, const float* B, const long long* boff, int SB, const int* pa, const int* pb,
+                 const long long* poff, int P, long long N, int max_n, double eps_rel, int max_rounds, int chunk_rounds, int* assign,
+                 double* emd, int* rounds, int* status, double* eps_final, double* price, long long* ticks, void* workspace,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

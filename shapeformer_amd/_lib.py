@@ -277,6 +277,13 @@ PROTOTYPES = {
     "sfmi_tangent_workspace_bytes": (sz, [i32, i64]),
     "sfmi_tangent_forest_f32": (i32, [c_ptr] * 3 + [i32, i64, i32, i64] + [c_ptr] * 7),
     "sfmi_tangent_apply_f32": (i32, [c_ptr] * 6 + [i32, i64] + [c_ptr] * 4),
+    # earth mover's distance: the deterministic auction (csrc/emd.hip)
+    "sfmi_emd_resident_max": (i32, []),
+    "sfmi_emd_max_points": (i32, []),
+    "sfmi_emd_default_cap": (i32, [i32]),
+    "sfmi_emd_default_chunk": (i32, []),
+    "sfmi_emd_workspace_bytes": (sz, [i32, i64]),
+    "sfmi_emd_f32": (i32, [c_ptr, c_ptr, i32, c_ptr, c_ptr, i32, c_ptr, c_ptr, c_ptr, i32, i64, i32, C.c_double, i32, i32] + [c_ptr] * 9),
 }
 
 
