@@ -158,6 +158,13 @@ def f32_dev(x, dev=None):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32))).to(dev or torch.device("cuda"))
 
 
+def workspace(nbytes, dev):
+    """-> the uint8 buffer a `void* workspace` argument points at: what the tool's sfmi_*_workspace_bytes reported, at least 256 bytes
+    (never an empty tensor, whose pointer is null).  Every tool allocates through here, called as `_ragged.workspace`, so a test can
+    put guard bands around every workspace by replacing this one function."""
+    return torch.empty(max(int(nbytes), 256), device=dev, dtype=torch.uint8)
+
+
 def batch_meshes(meshes, dev):
     """[(verts (n_i,3), faces (t_i,3)) numpy, indices local] -> verts f32, faces int32 on dev, host voff, toff (B+1,)"""
     verts = torch.from_numpy(np.concatenate([v for v, _ in meshes]).astype(np.float32)).to(dev)

@@ -69,9 +69,13 @@ struct EmdArgs {
   int* owner; int* list; unsigned long long* mybid; float* bx; float* by; float* bz;
 };
 
-inline size_t emd_ws_bytes(int P, long long N) {
+// workspace: per-pair state (P) | the unfinished counter (one int) | owner, list (N int32 each) | bids (N u64) | the streaming form's
+// copy of B as three arrays (N f32 each).  Fills the workspace members of a
+inline void emd_ws(SfmiCarver& c, int P, long long N, EmdArgs& a) {
   const size_t n = (size_t)N;
-  return align256(sizeof(EmdState) * (size_t)P) + 256 + 2 * align256(4 * n) + align256(8 * n) + 3 * align256(4 * n);
+  a.state = c.take<EmdState>((size_t)P); a.unfinished = c.take<int>(1);
+  a.owner = c.take<int>(n); a.list = c.take<int>(n); a.mybid = c.take<unsigned long long>(n);
+  a.bx = c.take<float>(n); a.by = c.take<float>(n); a.bz = c.take<float>(n);
 }
 
 __device__ __forceinline__ double emd_cost(float ax, float ay, float az, float x, float y, float z) {
@@ -413,7 +417,10 @@ int sfmi_emd_default_chunk(void) { return EMD_CHUNK_DEFAULT; }
 
 size_t sfmi_emd_workspace_bytes(int P, long long N) {
   if (P <= 0 || N < 0 || N >= (1ll << 40)) return 0;
-  return emd_ws_bytes(P, N);
+  SfmiCarver c{nullptr};
+  EmdArgs a;
+  emd_ws(c, P, N, a);
+  return c.bytes();
 }
 
 int sfmi_emd_f32(const float* A, const long long* aoff, int SA, const float* B, const long long* boff, int SB, const int* pa, const int* pb,
@@ -433,20 +440,12 @@ int sfmi_emd_f32(const float* A, const long long* aoff, int SA, const float* B, 
                                                        EMD_STREAM_BYTES * EMD_N_MAX);
   if (attr_r != hipSuccess || attr_s != hipSuccess) return SFMI_ELDS;
 
-  const size_t n = (size_t)N;
-  char* w = (char*)workspace;
   EmdArgs a;
   a.A = A; a.aoff = aoff; a.SA = SA; a.B = B; a.boff = boff; a.SB = SB; a.pa = pa; a.pb = pb; a.poff = poff;
   a.max_n = max_n; a.max_rounds = max_rounds; a.chunk_rounds = chunk_rounds; a.eps_rel = eps_rel;
   a.assign = assign; a.emd = emd; a.rounds = rounds; a.status = status; a.eps_final = eps_final; a.price = price; a.ticks = ticks;
-  a.state = (EmdState*)w; w += align256(sizeof(EmdState) * (size_t)P);
-  a.unfinished = (int*)w; w += 256;
-  a.owner = (int*)w; w += align256(4 * n);
-  a.list = (int*)w; w += align256(4 * n);
-  a.mybid = (unsigned long long*)w; w += align256(8 * n);
-  a.bx = (float*)w; w += align256(4 * n);
-  a.by = (float*)w; w += align256(4 * n);
-  a.bz = (float*)w;
+  SfmiCarver carver{(char*)workspace};
+  emd_ws(carver, P, N, a);
 
   const int res_n = max_n < EMD_N_RES ? max_n : EMD_N_RES;
   const size_t lds_r = (size_t)EMD_RES_BYTES * (size_t)((res_n + 1) & ~1), lds_s = (size_t)EMD_STREAM_BYTES * (size_t)((max_n + 1) & ~1);

@@ -369,14 +369,21 @@ __global__ void hpr_resample_kernel(const T* __restrict__ X, const unsigned char
   }
 }
 
+struct HprWs { double *fx, *fy, *fz, *R; int* orig; };
+
+// workspace: flipped x | y | z (N f64 each, in constraint order) | R (B f64) | the point of each slot (N int32)
+HprWs hpr_ws(SfmiCarver& c, int B, long long N) {
+  const size_t n = (size_t)(N > 0 ? N : 1);
+  return {c.take<double>(n), c.take<double>(n), c.take<double>(n), c.take<double>((size_t)B), c.take<int>(n)};   // in this order
+}
+
 }  // namespace
 
 extern "C" {
 
-// workspace: flipped x | y | z (N f64 each, in constraint order) | R (B f64) | the point of each slot (N int32)
 size_t sfmi_hpr_workspace_bytes(int B, long long N) {
   if (B <= 0 || N < 0) return 0;
-  return 3 * align256((size_t)(N > 0 ? N : 1) * 8) + align256((size_t)B * 8) + align256((size_t)(N > 0 ? N : 1) * 4);
+  return sfmi_ws_bytes(hpr_ws, B, N);
 }
 
 int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const double* cam, const int* order, int B, long long N, double param,
@@ -384,10 +391,8 @@ int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const doub
   if (B <= 0 || N < 0 || N >= (1ll << 31) || !off || !cam || !count || !status || !workspace) return SFMI_EINVAL;
   if (N > 0 && (!X || !visible)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const size_t comp = align256((size_t)(N > 0 ? N : 1) * 8);
-  char* ws = (char*)workspace;
-  double *fx = (double*)ws, *fy = (double*)(ws + comp), *fz = (double*)(ws + 2 * comp), *R = (double*)(ws + 3 * comp);
-  int* orig = (int*)(ws + 3 * comp + align256((size_t)B * 8));
+  SfmiCarver carver{(char*)workspace};
+  const auto [fx, fy, fz, R, orig] = hpr_ws(carver, B, N);
   if (N > 0 && order) (void)hipMemsetAsync(visible, 0, (size_t)N, st);     // an `order` that is no permutation leaves no byte unwritten
   const double scale = pow(10.0, param);
   const unsigned fb = (unsigned)cdiv(N, 256), vb = (unsigned)cdiv(N, HV_WAVES);

@@ -316,18 +316,26 @@ __global__ void knn_normals_kernel(const float* __restrict__ P, const long long*
   variation[i] = (float)(lam / (a00 + a11 + a22));
 }
 
+struct KnnWs { int K, S; long long* block_off; float* pd; int* pi; };   // the instance that serves k, its split; pd, pi: S > 1 only
+
+// workspace: block offsets (B+1 int64) | S > 1: partial d2 (S*K*N f32) | partial idx (S*K*N int32), K the instance that serves k
+KnnWs knn_ws(SfmiCarver& c, int B, long long N, long long M, int k) {
+  const int K = knn_instance(k);
+  KnnWs w{K, knn_splits(B, N, M, K), c.take<long long>((size_t)(B + 1)), nullptr, nullptr};
+  if (w.S > 1) {
+    w.pd = c.take<float>((size_t)w.S * w.K * N);
+    w.pi = c.take<int>((size_t)w.S * w.K * N);
+  }
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
 
-// workspace: block offsets (B+1 int64) | S > 1: partial d2 (S*K*N f32) | partial idx (S*K*N int32), K the instance that serves k
 size_t sfmi_knn_workspace_bytes(int B, long long N, long long M, int k) {
   if (B <= 0 || N < 0 || M < 0 || k < 1 || k > KNN_MAX_K) return 0;
-  const int K = knn_instance(k);
-  const int S = knn_splits(B, N, M, K);
-  size_t w = align256((size_t)(B + 1) * 8);
-  if (S > 1) w += 2 * align256((size_t)S * K * N * 4);
-  return w;
+  return sfmi_ws_bytes(knn_ws, B, N, M, k);
 }
 
 int sfmi_knn_f32(const float* P, const float* Q, const long long* poff, const long long* qoff, int B, long long N, long long M, int k,
@@ -337,16 +345,13 @@ int sfmi_knn_f32(const float* P, const float* Q, const long long* poff, const lo
   if (N == 0) return SFMI_OK;
   if (!P || !Q || !d2 || !idx) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int K = knn_instance(k);
-  const int S = knn_splits(B, N, M, K);
-  long long* block_off = (long long*)workspace;
-  float* pd = (float*)((char*)workspace + align256((size_t)(B + 1) * 8));
-  int* pi = (int*)((char*)pd + align256((size_t)S * K * N * 4));
+  SfmiCarver carver{(char*)workspace};
+  const KnnWs w = knn_ws(carver, B, N, M, k);
   const bool ex = exclude_self != 0;
-  if (K == 8) knn_launch<8, 4, 0>(P, Q, poff, qoff, block_off, B, N, k, S, ex, d2, idx, pd, pi, st);
-  else if (K == 16) knn_launch<16, 2, 0>(P, Q, poff, qoff, block_off, B, N, k, S, ex, d2, idx, pd, pi, st);
-  else if (K == 32) knn_launch<32, 1, 8>(P, Q, poff, qoff, block_off, B, N, k, S, ex, d2, idx, pd, pi, st);
-  else knn_launch<64, 1, 8>(P, Q, poff, qoff, block_off, B, N, k, S, ex, d2, idx, pd, pi, st);
+  if (w.K == 8) knn_launch<8, 4, 0>(P, Q, poff, qoff, w.block_off, B, N, k, w.S, ex, d2, idx, w.pd, w.pi, st);
+  else if (w.K == 16) knn_launch<16, 2, 0>(P, Q, poff, qoff, w.block_off, B, N, k, w.S, ex, d2, idx, w.pd, w.pi, st);
+  else if (w.K == 32) knn_launch<32, 1, 8>(P, Q, poff, qoff, w.block_off, B, N, k, w.S, ex, d2, idx, w.pd, w.pi, st);
+  else knn_launch<64, 1, 8>(P, Q, poff, qoff, w.block_off, B, N, k, w.S, ex, d2, idx, w.pd, w.pi, st);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

@@ -11,7 +11,7 @@
 //           table (mc_table.h, built by shapeformer_amd/mc_tables.py).
 // Output order is deterministic: vertices by (grid point, axis), triangles by (cell, table order).
 // HBM-bound integer/byte work: ~9 reads of the grid (L2-resident 8 MB per 128^3 shape) + one int per edge and cell.
-#include "sfmi_common.h"
+#include "sfmi_ragged.h"   // SfmiCarver: DESIGN.md §5.5a
 #include "mc_table.h"
 
 namespace {
@@ -195,33 +195,31 @@ int run_scan(F f, long long n, int* bsum, int* out, long long per_shape, int nsh
   return nblk;
 }
 
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
+struct McWs { int *vid, *toff, *bs0, *bs1; };
+
+// workspace: vid int[B*3*Q^3] | toff int[B*Q^3] | block sums of the two scans (nb ints each)
+McWs mc_ws(SfmiCarver& c, int B, int Q) {
+  const size_t n3 = (size_t)Q * Q * Q * B;
+  const size_t nb = (3 * n3 + SCAN_BLK - 1) / SCAN_BLK + 2;
+  return {c.take<int>(3 * n3), c.take<int>(n3), c.take<int>(nb), c.take<int>(nb)};   // in this order
+}
 
 }  // namespace
 
 extern "C" {
 
-// workspace: vid int[B*3*Q^3] | toff int[B*Q^3] | block sums
-size_t sfmi_mc_workspace_bytes(int B, int Q) {
-  const size_t n3 = (size_t)Q * Q * Q * B;
-  const size_t nb = (3 * n3 + SCAN_BLK - 1) / SCAN_BLK + 2;
-  return al(3 * n3 * 4) + al(n3 * 4) + al(nb * 4) * 2;
-}
+size_t sfmi_mc_workspace_bytes(int B, int Q) { return sfmi_ws_bytes(mc_ws, B, Q); }
 
 // pass 1: offsets (device, 2*(B+1) ints) = vertex offsets [B+1] then triangle offsets [B+1] (exclusive, per shape)
 int sfmi_mc_count_f32(const float* occ, float iso, int B, int Q, void* workspace, int* offsets, void* stream) {
   if (!occ || !workspace || !offsets || B <= 0 || Q < 2 || (long long)B * Q * Q * Q * 3 >= (1ll << 31)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const size_t n3 = (size_t)Q * Q * Q * B;
-  char* w = (char*)workspace;
-  int* vid = (int*)w;
-  int* toff = (int*)(w + al(3 * n3 * 4));
-  const size_t nb = (3 * n3 + SCAN_BLK - 1) / SCAN_BLK + 2;
-  int* bs0 = (int*)(w + al(3 * n3 * 4) + al(n3 * 4));
-  int* bs1 = (int*)((char*)bs0 + al(nb * 4));
+  SfmiCarver c{(char*)workspace};
+  const McWs w = mc_ws(c, B, Q);
   McGrid g{occ, iso, B, Q};
-  run_scan(EdgeCount{g}, (long long)3 * n3, bs0, vid, (long long)3 * Q * Q * Q, B, offsets, st);
-  run_scan(TriCount{g}, (long long)n3, bs1, toff, (long long)Q * Q * Q, B, offsets + B + 1, st);
+  run_scan(EdgeCount{g}, (long long)3 * n3, w.bs0, w.vid, (long long)3 * Q * Q * Q, B, offsets, st);
+  run_scan(TriCount{g}, (long long)n3, w.bs1, w.toff, (long long)Q * Q * Q, B, offsets + B + 1, st);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
@@ -233,13 +231,13 @@ int sfmi_mc_emit_f32(const float* occ, float iso, int B, int Q, const void* work
   if (!occ || !workspace || !offsets || !verts || !faces || B <= 0 || Q < 2) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const size_t n3 = (size_t)Q * Q * Q * B;
-  const char* w = (const char*)workspace;
-  const int* vid = (const int*)w;
-  const int* toff = (const int*)(w + al(3 * n3 * 4));
+  SfmiCarver c{(char*)const_cast<void*>(workspace)};           // read only: the kernels below take const pointers
+  const McWs w = mc_ws(c, B, Q);
   McGrid g{occ, iso, B, Q};
   McBox box{{lo0, lo1, lo2}, {hi0, hi1, hi2}};
-  hipLaunchKernelGGL(mc_verts_kernel, dim3((unsigned)((3 * n3 + 255) / 256)), dim3(256), 0, st, g, vid, offsets, box, verts);
-  hipLaunchKernelGGL(mc_faces_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, g, vid, toff, offsets, faces);
+  hipLaunchKernelGGL(mc_verts_kernel, dim3((unsigned)((3 * n3 + 255) / 256)), dim3(256), 0, st, g, (const int*)w.vid, offsets, box, verts);
+  hipLaunchKernelGGL(mc_faces_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, g, (const int*)w.vid, (const int*)w.toff,
+                     offsets, faces);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

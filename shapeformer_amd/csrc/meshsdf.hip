@@ -401,12 +401,19 @@ __global__ void sdf_jitter_kernel(const float* __restrict__ X, int B, long long 
   out[g] = fminf(fmaxf(x, -0.99f), 0.99f);
 }
 
-size_t sdf_ws(int B, long long N, long long T, bool occ, int* splits) {
-  const int R = occ ? SdR<true>::R : SdR<false>::R;
-  const int S = sd_splits(B, N, T, R);
-  if (splits) *splits = S;
-  size_t w = align256((size_t)(B + 1) * 8) + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16) + align256((size_t)S * N * 8);
-  if (!occ) w += 2 * align256((size_t)S * N * 4);
+struct SdWs { int splits; long long* block_off; float4* rec; long long* pw; float* pd; int* pi; };   // pd, pi: full form only
+
+// workspace: block offsets (B+1 int64) | face records (T x 80 B) | W partials (S*N int64) | full form: d2, idx partials (S*N each)
+// occ: the occupancy form, whose sections are the first three of the full form at the same offsets (its S differs)
+SdWs sdf_ws(SfmiCarver& c, int B, long long N, long long T, bool occ) {
+  const int S = sd_splits(B, N, T, occ ? SdR<true>::R : SdR<false>::R);
+  const size_t sn = (size_t)S * N;
+  SdWs w{S, c.take<long long>((size_t)(B + 1)), c.take<float4>((size_t)(T > 0 ? T : 1) * SD_REC), c.take<long long>(sn), nullptr,
+         nullptr};
+  if (!occ) {
+    w.pd = c.take<float>(sn);
+    w.pi = c.take<int>(sn);
+  }
   return w;
 }
 
@@ -414,11 +421,10 @@ size_t sdf_ws(int B, long long N, long long T, bool occ, int* splits) {
 
 extern "C" {
 
-// workspace: block offsets (B+1 int64) | face records (T x 80 B) | W partials (S*N int64) | full form: d2, idx partials (S*N each)
 size_t sfmi_mesh_sdf_workspace_bytes(int B, long long N, long long T) {
   if (B <= 0 || N < 0 || T < 0) return 0;
-  const size_t a = sdf_ws(B, N, T, false, nullptr), b = sdf_ws(B, N, T, true, nullptr);
-  return a > b ? a : b;
+  const size_t full = sfmi_ws_bytes(sdf_ws, B, N, T, false), occ = sfmi_ws_bytes(sdf_ws, B, N, T, true);
+  return full > occ ? full : occ;                              // the caller's buffer serves either form
 }
 
 int sfmi_mesh_sdf_f32(const float* Q, const long long* qoff, const float* verts, const int* faces, const long long* voff,
@@ -428,25 +434,19 @@ int sfmi_mesh_sdf_f32(const float* Q, const long long* qoff, const float* verts,
   if (T > 0 && (!verts || !faces)) return SFMI_EINVAL;
   if (N > 0 && (!Q || !S)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  int splits;
-  sdf_ws(B, N, T, false, &splits);
-  char* ws = (char*)workspace;
-  long long* block_off = (long long*)ws;
-  float4* rec = (float4*)(ws + align256((size_t)(B + 1) * 8));
-  long long* pw = (long long*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
-  float* pd = (float*)((char*)pw + align256((size_t)splits * N * 8));
-  int* pi = (int*)((char*)pd + align256((size_t)splits * N * 4));
-  if (T > 0) hipLaunchKernelGGL(sdf_setup_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, st, verts, faces, voff, toff, B, T, rec);
-  hipLaunchKernelGGL(sdf_status_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, st, toff, (const float4*)rec, status);
+  SfmiCarver carver{(char*)workspace};
+  const SdWs w = sdf_ws(carver, B, N, T, false);
+  if (T > 0) hipLaunchKernelGGL(sdf_setup_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, st, verts, faces, voff, toff, B, T, w.rec);
+  hipLaunchKernelGGL(sdf_status_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, st, toff, (const float4*)w.rec, status);
   if (N > 0) {
     constexpr int QB = SD_THREADS * SdR<false>::R;
-    hipLaunchKernelGGL(sdf_block_offsets_kernel, dim3(1), dim3(64), 0, st, qoff, block_off, B, QB);
-    const dim3 grid((unsigned)sd_qblocks(B, N, SdR<false>::R), (unsigned)splits);
+    hipLaunchKernelGGL(sdf_block_offsets_kernel, dim3(1), dim3(64), 0, st, qoff, w.block_off, B, QB);
+    const dim3 grid((unsigned)sd_qblocks(B, N, SdR<false>::R), (unsigned)w.splits);
     Lattice lat{};
-    hipLaunchKernelGGL(sdf_kernel<false>, grid, dim3(SD_THREADS), 0, st, Q, qoff, toff, (const float4*)rec, (const long long*)block_off, B, N,
-                       lat, pd, pi, pw);
-    hipLaunchKernelGGL(sdf_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, Q, qoff, toff, (const float4*)rec,
-                       (const int*)status, B, N, splits, (const float*)pd, (const int*)pi, (const long long*)pw, S, I, C, W);
+    hipLaunchKernelGGL(sdf_kernel<false>, grid, dim3(SD_THREADS), 0, st, Q, qoff, toff, (const float4*)w.rec,
+                       (const long long*)w.block_off, B, N, lat, w.pd, w.pi, w.pw);
+    hipLaunchKernelGGL(sdf_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, Q, qoff, toff, (const float4*)w.rec,
+                       (const int*)status, B, N, w.splits, (const float*)w.pd, (const int*)w.pi, (const long long*)w.pw, S, I, C, W);
   }
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -458,11 +458,8 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
   if (T > 0 && (!verts || !faces)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const long long G3 = (long long)G * G * G, N = (long long)B * G3;
-  int splits;
-  sdf_ws(B, N, T, true, &splits);
-  char* ws = (char*)workspace;
-  float4* rec = (float4*)(ws + align256((size_t)(B + 1) * 8));
-  long long* pw = (long long*)((char*)rec + align256((size_t)(T > 0 ? T : 1) * SD_REC * 16));
+  SfmiCarver carver{(char*)workspace};
+  const SdWs w = sdf_ws(carver, B, N, T, true);
   Lattice lat;
   lat.G = G;
   for (int a = 0; a < 3; ++a) {
@@ -470,14 +467,14 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
     lat.hi[a] = hi[a];
     lat.step[a] = G > 1 ? (hi[a] - lo[a]) / (double)(G - 1) : 0.0;
   }
-  if (T > 0) hipLaunchKernelGGL(sdf_setup_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, st, verts, faces, voff, toff, B, T, rec);
-  hipLaunchKernelGGL(sdf_status_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, st, toff, (const float4*)rec, status);
+  if (T > 0) hipLaunchKernelGGL(sdf_setup_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, st, verts, faces, voff, toff, B, T, w.rec);
+  hipLaunchKernelGGL(sdf_status_kernel, dim3((unsigned)B), dim3(ST_THREADS), 0, st, toff, (const float4*)w.rec, status);
   constexpr int QB = SD_THREADS * SdR<true>::R;
-  const dim3 grid((unsigned)(cdiv(G3, QB) * B), (unsigned)splits);
+  const dim3 grid((unsigned)(cdiv(G3, QB) * B), (unsigned)w.splits);
   hipLaunchKernelGGL(sdf_kernel<true>, grid, dim3(SD_THREADS), 0, st, (const float*)nullptr, (const long long*)nullptr, toff,
-                     (const float4*)rec, (const long long*)nullptr, B, N, lat, (float*)nullptr, (int*)nullptr, pw);
-  hipLaunchKernelGGL(occ_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, (const int*)status, G3, N, splits,
-                     (const long long*)pw, occ);
+                     (const float4*)w.rec, (const long long*)nullptr, B, N, lat, (float*)nullptr, (int*)nullptr, w.pw);
+  hipLaunchKernelGGL(occ_merge_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, (const int*)status, G3, N, w.splits,
+                     (const long long*)w.pw, occ);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

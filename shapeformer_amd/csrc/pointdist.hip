@@ -140,17 +140,25 @@ __global__ void mesh_sample_kernel(const float* __restrict__ verts, const int* _
   if (face_out) face_out[g] = (int)lo;
 }
 
+struct NnWs { int S; long long* block_off; float* pd; int* pi; };   // pd, pi: S > 1 only
+
+// workspace: block offsets (B+1 int64) | S > 1: partial d2 (S*N f32) | partial idx (S*N int32)
+NnWs nn_ws(SfmiCarver& c, int B, long long N, long long M) {
+  NnWs w{nn_splits(B, N, M), c.take<long long>((size_t)(B + 1)), nullptr, nullptr};
+  if (w.S > 1) {
+    w.pd = c.take<float>((size_t)w.S * N);
+    w.pi = c.take<int>((size_t)w.S * N);
+  }
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
 
-// workspace: block offsets (B+1 int64) | S > 1: partial d2 (S*N f32) | partial idx (S*N int32)
 size_t sfmi_nn_dist_workspace_bytes(int B, long long N, long long M) {
   if (B <= 0 || N < 0 || M < 0) return 0;
-  const int S = nn_splits(B, N, M);
-  size_t w = align256((size_t)(B + 1) * 8);
-  if (S > 1) w += 2 * align256((size_t)S * N * 4);
-  return w;
+  return sfmi_ws_bytes(nn_ws, B, N, M);
 }
 
 int sfmi_nn_dist_f32(const float* P, const float* Q, const long long* poff, const long long* qoff, int B, long long N, long long M,
@@ -159,18 +167,16 @@ int sfmi_nn_dist_f32(const float* P, const float* Q, const long long* poff, cons
   if (N == 0) return SFMI_OK;
   if (!P || !Q || !d2) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int S = nn_splits(B, N, M);
-  long long* block_off = (long long*)workspace;
-  hipLaunchKernelGGL(sfmi_block_offsets_kernel<NN_QB>, dim3(1), dim3(64), 0, st, poff, block_off, B);
-  const dim3 grid((unsigned)sfmi_qblocks(B, N, NN_QB), (unsigned)S);
-  if (S == 1) {
-    hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)block_off, B, N, d2, idx);
+  SfmiCarver carver{(char*)workspace};
+  const NnWs w = nn_ws(carver, B, N, M);
+  hipLaunchKernelGGL(sfmi_block_offsets_kernel<NN_QB>, dim3(1), dim3(64), 0, st, poff, w.block_off, B);
+  const dim3 grid((unsigned)sfmi_qblocks(B, N, NN_QB), (unsigned)w.S);
+  if (w.S == 1) {
+    hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)w.block_off, B, N, d2, idx);
   } else {
-    float* pd = (float*)((char*)workspace + align256((size_t)(B + 1) * 8));
-    int* pi = (int*)((char*)pd + align256((size_t)S * N * 4));
-    hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)block_off, B, N, pd, pi);
-    if (idx) sfmi_nn_merge<true, false>(pd, pi, nullptr, nullptr, B, S, N, d2, idx, st);
-    else sfmi_nn_merge<false, false>(pd, pi, nullptr, nullptr, B, S, N, d2, idx, st);
+    hipLaunchKernelGGL(nn_kernel, grid, dim3(NN_THREADS), 0, st, P, Q, poff, qoff, (const long long*)w.block_off, B, N, w.pd, w.pi);
+    if (idx) sfmi_nn_merge<true, false>(w.pd, w.pi, nullptr, nullptr, B, w.S, N, d2, idx, st);
+    else sfmi_nn_merge<false, false>(w.pd, w.pi, nullptr, nullptr, B, w.S, N, d2, idx, st);
   }
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

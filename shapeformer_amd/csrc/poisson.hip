@@ -187,10 +187,13 @@ inline int cg_span(int R) {
 struct CgLayout {
   long long n3;
   int ti, span, np_apply, np_elem, tiles;
-  size_t r, p, q, part_pq, part_rr, rr, bb, tol2, iter, done, bytes;
+  float *r, *p, *q;            // (B n3) each
+  double *part_pq, *part_rr;   // (B np_apply), (B np_elem)
+  double *rr, *bb, *tol2;      // (2 B), (B), one
+  int *iter, *done;            // (2 B) each
 };
 
-inline CgLayout cg_layout(int B, int R) {
+inline CgLayout cg_layout(SfmiCarver& c, int B, int R) {
   CgLayout l;
   l.n3 = (long long)R * R * R;
   l.ti = cg_ti(R);
@@ -198,19 +201,11 @@ inline CgLayout cg_layout(int B, int R) {
   l.tiles = (int)(cdiv(R, CG_TK) * cdiv(R, CG_TJ));
   l.np_apply = l.tiles * (int)cdiv(R, l.ti);
   l.np_elem = (int)cdiv(l.n3, l.span);
-  const size_t lat = align256((size_t)B * l.n3 * sizeof(float));
-  size_t o = 0;
-  l.r = o; o += lat;
-  l.p = o; o += lat;
-  l.q = o; o += lat;
-  l.part_pq = o; o += align256((size_t)B * l.np_apply * sizeof(double));
-  l.part_rr = o; o += align256((size_t)B * l.np_elem * sizeof(double));
-  l.rr = o; o += align256((size_t)2 * B * sizeof(double));
-  l.bb = o; o += align256((size_t)B * sizeof(double));
-  l.tol2 = o; o += 256;
-  l.iter = o; o += align256((size_t)2 * B * sizeof(int));
-  l.done = o; o += align256((size_t)2 * B * sizeof(int));
-  l.bytes = o;
+  const size_t lat = (size_t)B * l.n3;
+  l.r = c.take<float>(lat); l.p = c.take<float>(lat); l.q = c.take<float>(lat);
+  l.part_pq = c.take<double>((size_t)B * l.np_apply); l.part_rr = c.take<double>((size_t)B * l.np_elem);
+  l.rr = c.take<double>((size_t)2 * B); l.bb = c.take<double>((size_t)B); l.tol2 = c.take<double>(1);
+  l.iter = c.take<int>((size_t)2 * B); l.done = c.take<int>((size_t)2 * B);
   return l;
 }
 
@@ -507,31 +502,30 @@ int sfmi_poisson_rhs_f32(const float* Vx, const float* Vy, const float* Vz, int 
 
 size_t sfmi_poisson_cg_workspace_bytes(int B, int R) {
   if (!p_dims_ok(B, R)) return 0;
-  return cg_layout(B, R).bytes;
+  return sfmi_ws_bytes(cg_layout, B, R);
 }
 
 int sfmi_poisson_cg_init_f32(const float* rhs, int B, int R, double tol, float* x, void* workspace, void* stream) {
   if (!p_dims_ok(B, R) || !(tol > 0.0) || !rhs || !x || !workspace) return SFMI_EINVAL;
-  const CgLayout l = cg_layout(B, R);
-  char* ws = (char*)workspace;
+  SfmiCarver c{(char*)workspace};
+  const CgLayout l = cg_layout(c, B, R);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cg_init_kernel, dim3((unsigned)l.np_elem, (unsigned)B), dim3(CG_THREADS), 0, st, rhs, x, (float*)(ws + l.r),
-                     (float*)(ws + l.p), l.n3, l.span, (double*)(ws + l.part_rr));
-  hipLaunchKernelGGL(cg_init_state_kernel, dim3((unsigned)B), dim3(CG_THREADS), 0, st, (const double*)(ws + l.part_rr), l.np_elem, tol,
-                     (double*)(ws + l.rr), (double*)(ws + l.bb), (double*)(ws + l.tol2), (int*)(ws + l.iter), (int*)(ws + l.done));
+  hipLaunchKernelGGL(cg_init_kernel, dim3((unsigned)l.np_elem, (unsigned)B), dim3(CG_THREADS), 0, st, rhs, x, l.r, l.p, l.n3, l.span,
+                     l.part_rr);
+  hipLaunchKernelGGL(cg_init_state_kernel, dim3((unsigned)B), dim3(CG_THREADS), 0, st, (const double*)l.part_rr, l.np_elem, tol, l.rr,
+                     l.bb, l.tol2, l.iter, l.done);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
 
 int sfmi_poisson_cg_steps_f32(int B, int R, int n, long long it0, float* x, void* workspace, void* stream) {
   if (!p_dims_ok(B, R) || n < 0 || it0 < 0 || !x || !workspace) return SFMI_EINVAL;
-  const CgLayout l = cg_layout(B, R);
-  char* ws = (char*)workspace;
+  SfmiCarver c{(char*)workspace};
+  const CgLayout l = cg_layout(c, B, R);
   hipStream_t st = (hipStream_t)stream;
-  float *r = (float*)(ws + l.r), *p = (float*)(ws + l.p), *q = (float*)(ws + l.q);
-  double *ppq = (double*)(ws + l.part_pq), *prr = (double*)(ws + l.part_rr), *rr = (double*)(ws + l.rr), *bb = (double*)(ws + l.bb);
-  double* tol2 = (double*)(ws + l.tol2);
-  int *iter = (int*)(ws + l.iter), *done = (int*)(ws + l.done);
+  float *r = l.r, *p = l.p, *q = l.q;
+  double *ppq = l.part_pq, *prr = l.part_rr, *rr = l.rr, *bb = l.bb, *tol2 = l.tol2;
+  int *iter = l.iter, *done = l.done;
   const dim3 ga((unsigned)l.tiles, (unsigned)cdiv(R, l.ti), (unsigned)B), ge((unsigned)l.np_elem, (unsigned)B);
   for (int t = 0; t < n; ++t) {
     const int cur = (int)((it0 + t) & 1), nxt = cur ^ 1;
@@ -548,12 +542,11 @@ int sfmi_poisson_cg_steps_f32(int B, int R, int n, long long it0, float* x, void
 
 int sfmi_poisson_cg_read_i32(int B, int R, long long it, const void* workspace, int* iterations, double* residual, int* done, void* stream) {
   if (!p_dims_ok(B, R) || it < 0 || !workspace || !iterations || !residual || !done) return SFMI_EINVAL;
-  const CgLayout l = cg_layout(B, R);
-  const char* ws = (const char*)workspace;
+  SfmiCarver c{(char*)const_cast<void*>(workspace)};           // read only: the kernel below takes const pointers
+  const CgLayout l = cg_layout(c, B, R);
   const int cur = (int)(it & 1);
-  hipLaunchKernelGGL(cg_read_kernel, dim3(blocks256(B)), dim3(256), 0, (hipStream_t)stream, (const double*)(ws + l.rr) + cur * B,
-                     (const double*)(ws + l.bb), (const int*)(ws + l.iter) + cur * B, (const int*)(ws + l.done) + cur * B, B, iterations,
-                     residual, done);
+  hipLaunchKernelGGL(cg_read_kernel, dim3(blocks256(B)), dim3(256), 0, (hipStream_t)stream, (const double*)l.rr + cur * B,
+                     (const double*)l.bb, (const int*)l.iter + cur * B, (const int*)l.done + cur * B, B, iterations, residual, done);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

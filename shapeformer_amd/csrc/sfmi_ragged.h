@@ -2,8 +2,9 @@
 // components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip, global_register.hip, posegraph.hip, tangent.hip and emd.hip need
 // for ragged batches (the split nearest-neighbour search of the scan tools is sfmi_search.h, which includes this file).  A ragged batch
 // is B sets stored back to back with (B+1) nondecreasing offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b
-// with off[b] <= x < off[b+1].  Everything here is inlined into its caller.  A caller's `#pragma clang fp contract(off)` comes after
-// this include, so it changes nothing in here.  Two functions below have a product feeding a sum: sfmi_pose_row, whose callers all
+// with off[b] <= x < off[b+1].  Everything here is inlined into its caller.  The host one-liners at the end hold SfmiCarver, through
+// which every tool with a `void* workspace` states that buffer's layout once, for its size function and its launchers.  A caller's
+// `#pragma clang fp contract(off)` comes after this include, so it changes nothing in here.  Two functions below have a product feeding a sum: sfmi_pose_row, whose callers all
 // compile without contraction, carries `#pragma clang fp contract(off)` in its body; jacobi_rot is compiled under the build's setting.
 #pragma once
 #include "sfmi_common.h"
@@ -308,6 +309,28 @@ __device__ __forceinline__ int sfmi_mesh_status(int flags) {
 // ---- host one-liners ----------------------------------------------------------------------------------------------------------------
 __host__ __device__ inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }                    // workspace sections start on 256 bytes
+
+// a `void* workspace` cut into sections, in the order they are taken.  A tool names its sections in ONE layout function that takes a
+// carver: over a null carver it only counts (sfmi_*_workspace_bytes returns bytes()), over the caller's buffer it hands the launcher the
+// same sections' pointers, so the size and the offsets cannot drift apart.  Host only.
+struct SfmiCarver {
+  char* base;                                                  // nullptr: count only, every take() is nullptr
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += align256(count * sizeof(T));
+    return p;
+  }
+  size_t bytes() const { return off; }
+};
+// what a layout function takes in all: it is run over a null carver.  args: the layout's arguments after the carver
+template <typename F, typename... A>
+inline size_t sfmi_ws_bytes(F layout, A... args) {
+  SfmiCarver c{nullptr};
+  layout(c, args...);
+  return c.bytes();
+}
 inline unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }         // workgroups of 256 threads over n items
 constexpr unsigned SFMI_MAX_GRID = 65535;                                              // the y and z limits of a grid
 inline unsigned sfmi_grid_cap(long long n) { return (unsigned)(n < 1 ? 1 : (n > SFMI_MAX_GRID ? SFMI_MAX_GRID : n)); }   // for grid-stride loops

@@ -58,26 +58,16 @@ struct TgState {
   int* flags;                  // (TG_MAX_ROUNDS + 2) flags[r] != 0: round r has work
 };
 
-inline size_t tg_ws_bytes(long long N) {
+// workspace of the forest: best_w, best_e (N u64 each) | label, parent, newroot, cmin (N int32 each) | par, hookflip, acc, alive
+// (N bytes each) | flags.  sfmi_tangent_apply_f32 reuses the buffer's start for B centroids (3 f64 each)
+inline TgState tg_ws(SfmiCarver& c, long long N) {
   const size_t n = (size_t)N;
-  return 4 * align256(4 * n) + 2 * align256(8 * n) + 4 * align256(n) + align256(4 * (TG_MAX_ROUNDS + 2));
-}
-
-inline TgState tg_carve(void* ws, long long N) {
-  const size_t n = (size_t)N;
-  char* p = (char*)ws;
   TgState s;
-  s.best_w = (unsigned long long*)p; p += align256(8 * n);
-  s.best_e = (unsigned long long*)p; p += align256(8 * n);
-  s.label = (int*)p; p += align256(4 * n);
-  s.parent = (int*)p; p += align256(4 * n);
-  s.newroot = (int*)p; p += align256(4 * n);
-  s.cmin = (int*)p; p += align256(4 * n);
-  s.par = (unsigned char*)p; p += align256(n);
-  s.hookflip = (unsigned char*)p; p += align256(n);
-  s.acc = (unsigned char*)p; p += align256(n);
-  s.alive = (unsigned char*)p; p += align256(n);
-  s.flags = (int*)p;
+  s.best_w = c.take<unsigned long long>(n); s.best_e = c.take<unsigned long long>(n);
+  s.label = c.take<int>(n); s.parent = c.take<int>(n); s.newroot = c.take<int>(n); s.cmin = c.take<int>(n);
+  s.par = c.take<unsigned char>(n); s.hookflip = c.take<unsigned char>(n); s.acc = c.take<unsigned char>(n);
+  s.alive = c.take<unsigned char>(n);
+  s.flags = c.take<int>(TG_MAX_ROUNDS + 2);
   return s;
 }
 
@@ -314,8 +304,8 @@ extern "C" {
 
 size_t sfmi_tangent_workspace_bytes(int B, long long N) {
   if (B <= 0 || N < 0 || N >= (1ll << 31)) return 0;
-  const size_t forest = tg_ws_bytes(N), anchor = align256(sizeof(double) * 3 * (size_t)B);
-  return forest > anchor ? forest : anchor;
+  const size_t forest = sfmi_ws_bytes(tg_ws, N), anchor = align256(sizeof(double) * 3 * (size_t)B);
+  return forest > anchor ? forest : anchor;                    // the caller's buffer serves the forest, then apply's centroids
 }
 
 int sfmi_tangent_forest_f32(const float* normal, const long long* off, const int* idx, int B, long long N, int k, long long max_n,
@@ -324,7 +314,8 @@ int sfmi_tangent_forest_f32(const float* normal, const long long* off, const int
     return SFMI_EINVAL;
   if (N > 0 && (!normal || !idx || !component || !tree || !parity || !workspace)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const TgState s = tg_carve(workspace, N);
+  SfmiCarver carver{(char*)workspace};
+  const TgState s = tg_ws(carver, N);
   const long long items = N > B ? (N > TG_MAX_ROUNDS + 2 ? N : TG_MAX_ROUNDS + 2) : (B > TG_MAX_ROUNDS + 2 ? B : TG_MAX_ROUNDS + 2);
   if (N == 0) {                                                // no workspace: rounds and status alone
     hipMemsetAsync(rounds, 0, sizeof(int) * (size_t)B, st);
@@ -358,8 +349,10 @@ int sfmi_tangent_apply_f32(const float* P, const float* normal, const long long*
   hipMemsetAsync(votes, 0, sizeof(int) * 2 * (size_t)N, st);
   const double* ref = viewpoint;
   if (!viewpoint) {
-    hipLaunchKernelGGL(tg_centroid_kernel, dim3((unsigned)B), dim3(TG_CEN_THREADS), 0, st, P, off, (double*)workspace);
-    ref = (const double*)workspace;
+    SfmiCarver carver{(char*)workspace};
+    double* cen = carver.take<double>(3 * (size_t)B);          // the `anchor` of sfmi_tangent_workspace_bytes
+    hipLaunchKernelGGL(tg_centroid_kernel, dim3((unsigned)B), dim3(TG_CEN_THREADS), 0, st, P, off, cen);
+    ref = cen;
   }
   hipLaunchKernelGGL(tg_vote_kernel, grid, block, 0, st, P, normal, off, component, parity, ref, viewpoint ? 0 : 1, B, N, votes);
   hipLaunchKernelGGL(tg_apply_kernel, grid, block, 0, st, (const unsigned*)normal, off, component, parity, votes, B, N, (unsigned*)out);

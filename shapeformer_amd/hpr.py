@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import on_device, point_sets
 
 
@@ -95,7 +96,7 @@ def hidden_point_mask_dev(points, cams, off=None, param=np.pi, _evals=None, _ind
     status = torch.empty(B, device=dev, dtype=torch.int32)
     od, cd = torch.from_numpy(o).to(dev), torch.from_numpy(c).to(dev)
     order = constraint_order_dev(x, o, c) if N > 0 and not _index_order else None   # None: index order (tools/kbench_hpr.py's A/B)
-    ws = torch.empty(max(int(lib.sfmi_hpr_workspace_bytes(B, N)), 1), device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_hpr_workspace_bytes(B, N), dev)
     if _evals is not None:
         _evals.append(torch.empty(N, 2, device=dev, dtype=torch.int32))
     L.check(lib.sfmi_hpr_visible(L.ptr(x), int(x.dtype == torch.float64), L.ptr(od), L.ptr(cd), L.ptr(order), B, N, float(param), L.ptr(vis),

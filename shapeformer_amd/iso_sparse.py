@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import excl_at
 
 
@@ -99,7 +100,7 @@ def extract_sparse_dev(field, B, coarse_Q, levels, thresh=0.5, margin=1, bbox=((
     nbytes = int(lib.sfmi_iso_sparse_workspace_bytes(B, Q))
     if nbytes == 0:
         raise L.SfmiError("sfmi_iso_sparse_workspace_bytes: invalid lattice")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(nbytes, dev)
     W = (Q ** 3 + 31) // 32
     lat = (B, Q0, nl, Q)
     pts, cel = _BitSet(ws, 0, nbytes // 4, B, W), _BitSet(ws, 1, nbytes // 4, B, W)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 
 
 def marching_cubes_dev(occ: torch.Tensor, thresh: float = 0.5, bbox=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))):
@@ -24,7 +25,7 @@ def marching_cubes_dev(occ: torch.Tensor, thresh: float = 0.5, bbox=((-1.0, -1.0
     occ = occ.contiguous().float()
     B, Q = occ.shape[0], occ.shape[1]
     assert occ.shape == (B, Q, Q, Q)
-    ws = torch.empty(lib.sfmi_mc_workspace_bytes(B, Q), device=occ.device, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_mc_workspace_bytes(B, Q), occ.device)
     offs = torch.zeros(2 * (B + 1), device=occ.device, dtype=torch.int32)
     L.check(lib.sfmi_mc_count_f32(L.ptr(occ), float(thresh), B, Q, L.ptr(ws), L.ptr(offs), L.stream_ptr()), "sfmi_mc_count_f32")
     o = offs.cpu().numpy()            # the one host sync: output sizes

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import batch_meshes, f32_dev, host_offsets, mesh_args, on_device
 from .metrics import sample_mesh_dev
 
@@ -29,7 +30,7 @@ STATUS_OK, STATUS_NO_FACES, STATUS_BAD_INDEX = 0, 1, 2
 
 
 def _workspace(B, N, T, dev):
-    return torch.empty(max(int(L.lib().sfmi_mesh_sdf_workspace_bytes(B, N, T)), 1), device=dev, dtype=torch.uint8)
+    return _ragged.workspace(L.lib().sfmi_mesh_sdf_workspace_bytes(B, N, T), dev)
 
 
 def signed_distance_dev(queries, verts, faces, qoff=None, voff=None, toff=None, return_winding=False):

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import check_count, check_number, f32_dev, host_offsets, i32_dev, offsets_dev, on_device, pair_sets, point_sets, points_arg
 
 
@@ -39,7 +40,7 @@ def _launch_nn(pf, qf, po, qo, want_index):
     if N == 0:
         return d2, idx
     pod, qod = offsets_dev(po, dev), offsets_dev(qo, dev)
-    ws = torch.empty(max(int(lib.sfmi_nn_dist_workspace_bytes(B, N, M)), 1), device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_nn_dist_workspace_bytes(B, N, M), dev)
     L.check(lib.sfmi_nn_dist_f32(L.ptr(pf), L.ptr(qf), L.ptr(pod), L.ptr(qod), B, N, M, L.ptr(d2), L.ptr(idx), L.ptr(ws),
                                  L.stream_ptr()), "sfmi_nn_dist_f32")
     return d2, idx
@@ -296,7 +297,7 @@ def emd_dev(a, b, a_off=None, b_off=None, pairs=None, eps_rel=1e-4, max_rounds=N
         af, bf = a.float().contiguous(), b.float().contiguous()
         aod, bod, pod = offsets_dev(ao, dev), offsets_dev(bo, dev), offsets_dev(po, dev)
         pad, pbd = i32_dev(pa, dev), i32_dev(pb, dev)
-        ws = torch.empty(int(lib.sfmi_emd_workspace_bytes(P, N)), device=dev, dtype=torch.uint8)
+        ws = _ragged.workspace(lib.sfmi_emd_workspace_bytes(P, N), dev)
         L.check(lib.sfmi_emd_f32(L.ptr(af), L.ptr(aod), SA, L.ptr(bf), L.ptr(bod), SB, L.ptr(pad), L.ptr(pbd), L.ptr(pod), P, N,
                                  int(na.max()), eps_rel, max_rounds, chunk_rounds, L.ptr(assign), L.ptr(emd_), L.ptr(rounds),
                                  L.ptr(status), L.ptr(eps_final), L.ptr(price), L.ptr(tk), L.ptr(ws), L.stream_ptr()), "sfmi_emd_f32")
@@ -458,7 +459,7 @@ def sample_mesh_dev(verts, faces, voff, toff, n, seed=0, return_face=False):
     face = torch.empty(B * n, device=dev, dtype=torch.int32) if return_face else None
     status = torch.empty(B, device=dev, dtype=torch.int32)
     vod, tod = offsets_dev(vo, dev), offsets_dev(to, dev)
-    ws = torch.empty(int(lib.sfmi_mesh_sample_workspace_bytes(B, T)), device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_mesh_sample_workspace_bytes(B, T), dev)
     L.check(lib.sfmi_mesh_sample_f32(L.ptr(vf), L.ptr(ff), L.ptr(vod), L.ptr(tod), B, T, n, int(seed) & (2 ** 64 - 1), L.ptr(ws),
                                      L.ptr(out), L.ptr(face), L.ptr(status), L.stream_ptr()), "sfmi_mesh_sample_f32")
     return (out, status, face) if return_face else (out, status)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import i32_dev, mesh_args, on_device, point_sets
 
 MAX_RADIUS = 16         # sfmi_morph_max_radius()
@@ -79,7 +80,7 @@ def _words(B, G, dev):
 
 
 def _workspace(B, G, r, dev):
-    return torch.empty(max(int(L.lib().sfmi_morph_workspace_bytes(B, G, r)), 1), device=dev, dtype=torch.uint8)
+    return _ragged.workspace(L.lib().sfmi_morph_workspace_bytes(B, G, r), dev)
 
 
 def _pack(v4, B, G):

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import host_offsets, offsets_dev, on_device, point_sets, points_arg
 
 MIN_GRID, MAX_GRID = 5, 513
@@ -188,7 +189,7 @@ def _solve(rhs, tol, max_iter, check_every):
     if max_iter is None:
         max_iter = 4 * R
     chi = torch.empty_like(rhs)
-    ws = torch.empty(int(lib.sfmi_poisson_cg_workspace_bytes(B, R)), device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_poisson_cg_workspace_bytes(B, R), dev)
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     done = torch.empty(B, device=dev, dtype=torch.int32)
     res = torch.empty(B, device=dev, dtype=torch.float64)

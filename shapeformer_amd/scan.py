@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _ragged
 from ._ragged import (check_count, check_nonneg, check_number, excl_at, offsets_dev, on_device, pair_sets, point_sets, points_arg,
                       run_starts, set_ids, sorted_runs)
 
@@ -59,7 +60,7 @@ def _launch_knn(pf, qf, po, qo, k, exclude_self):
     if N == 0:
         return d2, idx
     pod, qod = offsets_dev(po, dev), offsets_dev(qo, dev)
-    ws = torch.empty(max(int(lib.sfmi_knn_workspace_bytes(B, N, M, k)), 1), device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_knn_workspace_bytes(B, N, M, k), dev)
     L.check(lib.sfmi_knn_f32(L.ptr(pf), L.ptr(qf), L.ptr(pod), L.ptr(qod), B, N, M, k, int(bool(exclude_self)), L.ptr(d2), L.ptr(idx),
                              L.ptr(ws), L.stream_ptr()), "sfmi_knn_f32")
     return d2, idx
@@ -212,7 +213,7 @@ def _orient_launch(what, xf, nf, o, idx, vd):
         lib = L.lib()
         od = offsets_dev(o, dev)
         status = torch.empty(B, device=dev, dtype=torch.int32)
-        ws = torch.empty(max(int(lib.sfmi_tangent_workspace_bytes(B, N)), 256), device=dev, dtype=torch.uint8)
+        ws = _ragged.workspace(lib.sfmi_tangent_workspace_bytes(B, N), dev)
         L.check(lib.sfmi_tangent_forest_f32(L.ptr(nf), L.ptr(od), L.ptr(idx), B, N, k, _max_n(o), L.ptr(component), L.ptr(tree),
                                             L.ptr(parity), L.ptr(rounds), L.ptr(status), L.ptr(ws), L.stream_ptr()),
                 "sfmi_tangent_forest_f32")
@@ -386,7 +387,7 @@ def farthest_point_sample_dev(points, off=None, n=None, start=None, valid=None):
     vd = valid.reshape(-1).contiguous() if valid is not None else None
     od = offsets_dev(o, dev)
     sd = torch.from_numpy(st).to(dev) if st is not None else None
-    ws = torch.empty(max(int(lib.sfmi_fps_workspace_bytes(B, N, n)), 16), device=dev, dtype=torch.uint8)
+    ws = _ragged.workspace(lib.sfmi_fps_workspace_bytes(B, N, n), dev)
     L.check(lib.sfmi_fps_f32(L.ptr(xf), L.ptr(od), L.ptr(vd), L.ptr(sd), B, N, n, L.ptr(idx), L.ptr(d2), L.ptr(count), L.ptr(status),
                              L.ptr(ws), L.stream_ptr()), "sfmi_fps_f32")
     return idx, d2, count, status
