@@ -104,6 +104,7 @@ int sfmi_groupnorm_coeffs_f32(const float* x, const float* gamma, const float* b
                               double* partial, int B, int V, int C, int groups, float eps, void* stream);
 int sfmi_affine_cl_f32(const float* x, const float* scale, const float* shift, float* y, int B, long long V, int C, void* stream);
 int sfmi_maxpool2_cl_f32(const float* x, float* y, int B, int Do, int Ho, int Wo, int C, void* stream); /* unet3d.py:218-237 */
+/* D, H, W: the extents of skip and y, all even (low is read at d >> 1, h >> 1, w >> 1); Cs, Cu > 0, multiples of 4 */
 int sfmi_upcat_cl_f32(const float* skip, const float* low, float* y, int B, int D, int H, int W, int Cs, int Cu, void* stream); /* unet3d.py:268-293 */
 
 /* ---- Vector quantiser: quantizer.py:19-30 (get_code), :47-51 (distances + argmax) ----------------------------- */
@@ -453,14 +454,21 @@ int sfmi_upsample2_cl_f32(const float* x, float* y, int B, int D, int H, int W, 
 int sfmi_sumpool2_cl_f32(const float* dy, float* dx, int B, int Do, int Ho, int Wo, int Ctot, int c0, int Cs, void* stream);
 int sfmi_maxpool2_bwd_cl_f32(const float* x, const float* y, const float* dy, float* dx, int B, int Do, int Ho, int Wo, int C,
                              void* stream);
+/* 1 <= G <= 1024: the cell index x + G (y + G z) is an int32 */
 int sfmi_cells_f32(const float* cloud, int* cell, float* p_half, int B, int T, int G, void* stream);             /* common.py:260-321 */
 /* torch_scatter.scatter_max + gather (enc.py:95-112): keys (B,ncell,C) int32 pre-filled with 0x80 bytes */
 int sfmi_cell_max_f32(const float* net, const int* cell, int* keys, float* out, int B, int T, long long ncell, int C, int ldo, int co,
                       void* stream);
 int sfmi_cell_scatter_add_f32(const float* src, const int* cell, long long* acc, int* count, int B, int T, long long ncell, int C,
                               int lds, int cs, void* stream);
+/* backward of the local max pool: the gradient acc[b,cell,c] (2^-32 fixed point) of every (cell, channel) goes to exactly one point, the
+ * lowest-indexed of those whose value attains the cell's maximum (one of scatter_max's own outcomes; deterministic); every other point
+ * gets zero (accumulate: keeps its value).  _ws: win (B,ncell,C) int32 is the caller's scratch, contents on entry ignored (on return: the
+ * winner of every occupied (cell, channel)); the form without it takes that buffer from the device's stream-ordered pool for the call. */
 int sfmi_cell_max_bwd_f32(const float* net, const int* keys, const long long* acc, const int* cell, float* dnet, int B, int T,
                           long long ncell, int C, int ldd, int accumulate, void* stream);
+int sfmi_cell_max_bwd_ws_f32(const float* net, const int* keys, const long long* acc, const int* cell, int* win, float* dnet, int B, int T,
+                             long long ncell, int C, int ldd, int accumulate, void* stream);
 int sfmi_cell_mean_f32(const long long* acc, const int* count, float* grid, int B, long long ncell, int C, void* stream);  /* enc.py:66-75 */
 int sfmi_cell_mean_bwd_f32(const float* dgrid, const int* count, const int* cell, float* dc, int B, int T, long long ncell, int C,
                            void* stream);

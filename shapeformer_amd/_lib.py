@@ -40,6 +40,7 @@ PROTOTYPES = {
     "sfmi_cell_max_f32": (i32, [c_ptr] * 4 + [i32, i32, i64, i32, i32, i32, c_ptr]),
     "sfmi_cell_scatter_add_f32": (i32, [c_ptr] * 4 + [i32, i32, i64, i32, i32, i32, c_ptr]),
     "sfmi_cell_max_bwd_f32": (i32, [c_ptr] * 5 + [i32, i32, i64, i32, i32, i32, c_ptr]),
+    "sfmi_cell_max_bwd_ws_f32": (i32, [c_ptr] * 6 + [i32, i32, i64, i32, i32, i32, c_ptr]),
     "sfmi_cell_mean_f32": (i32, [c_ptr] * 3 + [i32, i64, i32, c_ptr]),
     "sfmi_cell_mean_bwd_f32": (i32, [c_ptr] * 4 + [i32, i32, i64, i32, c_ptr]),
     "sfmi_trilinear_cl_f32": (i32, [c_ptr] * 3 + [i32, i64, i32, i32, c_ptr]),

@@ -771,7 +771,7 @@ int sfmi_groupnorm_coeffs_partial_f32(const double* partial, const float* gamma,
 }
 
 int sfmi_affine_cl_f32(const float* x, const float* scale, const float* shift, float* y, int B, long long V, int C, void* stream) {
-  if (!x || !scale || !shift || !y || C % 4) return SFMI_EINVAL;
+  if (!x || !scale || !shift || !y || B <= 0 || V <= 0 || C <= 0 || C % 4) return SFMI_EINVAL;
   const long long total4 = (long long)B * V * (C / 4);
   hipLaunchKernelGGL(affine_cl_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, y, V, C, total4);
   SFMI_CHECK_LAUNCH();
@@ -779,7 +779,7 @@ int sfmi_affine_cl_f32(const float* x, const float* scale, const float* shift, f
 }
 
 int sfmi_maxpool2_cl_f32(const float* x, float* y, int B, int Do, int Ho, int Wo, int C, void* stream) {
-  if (!x || !y || C % 4) return SFMI_EINVAL;
+  if (!x || !y || B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C % 4) return SFMI_EINVAL;
   const long long total = (long long)B * Do * Ho * Wo * (C / 4);
   hipLaunchKernelGGL(maxpool2_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, B, Do, Ho, Wo, C);
   SFMI_CHECK_LAUNCH();
@@ -787,7 +787,7 @@ int sfmi_maxpool2_cl_f32(const float* x, float* y, int B, int Do, int Ho, int Wo
 }
 
 int sfmi_upcat_cl_f32(const float* skip, const float* low, float* y, int B, int D, int H, int W, int Cs, int Cu, void* stream) {
-  if (!skip || !low || !y || Cs % 4 || Cu % 4) return SFMI_EINVAL;
+  if (!skip || !low || !y || B <= 0 || D <= 0 || H <= 0 || W <= 0 || D % 2 || H % 2 || W % 2 || Cs <= 0 || Cu <= 0 || Cs % 4 || Cu % 4) return SFMI_EINVAL;
   const long long total = (long long)B * D * H * W * ((Cs + Cu) / 4);
   hipLaunchKernelGGL(upcat_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, skip, low, y, B, D, H, W, Cs, Cu);
   SFMI_CHECK_LAUNCH();

@@ -173,16 +173,37 @@ __global__ void cell_scatter_add_kernel(const float* __restrict__ src, const int
   if (count && c == 0) atomicAdd(&count[g], 1);
 }
 
-// local max-pool backward: dnet[pt][c] (+)= (net[pt][c] == cell max) ? d_cell[cell][c] : 0
-__global__ void cell_max_bwd_kernel(const float* __restrict__ net, const int* __restrict__ keys, const long long* __restrict__ acc,
-                                    const int* __restrict__ cell, float* __restrict__ dnet, int T, long long ncell, int C, int ldd,
-                                    int accumulate, long long total) {
+// local max-pool backward.  torch_scatter.scatter_max routes the gradient of a (cell, channel) to ONE arg-max point; points whose value
+// ties the maximum (exact copies of a row: the data loader draws the cloud with replacement) must not each receive it.  The winner is
+// the lowest point index among those whose key equals the cell's: pass 0 resets win[cell][c] of every occupied cell (all writers store
+// the same value), pass 1 takes an integer atomicMin over the attaining points, pass 2 routes.  Integer atomics only: bit-reproducible.
+__global__ void cell_win_reset_kernel(const int* __restrict__ cell, int* __restrict__ win, int T, long long ncell, int C, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // over (B, T, C)
+  if (i >= total) return;
+  const int c = (int)(i % C);
+  const long long pt = i / C, b = pt / T;
+  win[(b * ncell + cell[pt]) * C + c] = INT_MAX;
+}
+
+__global__ void cell_win_min_kernel(const float* __restrict__ net, const int* __restrict__ keys, const int* __restrict__ cell,
+                                    int* __restrict__ win, int T, long long ncell, int C, long long total) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int c = (int)(i % C);
   const long long pt = i / C, b = pt / T;
   const long long g = (b * ncell + cell[pt]) * C + c;
-  const float v = (f2key(net[i]) == keys[g]) ? (float)((double)acc[g] * (1.0 / FIX_SCALE)) : 0.f;
+  if (f2key(net[i]) == keys[g]) atomicMin(&win[g], (int)(pt - b * T));
+}
+
+// dnet[pt][c] (+)= (pt is the winner of its cell in channel c) ? d_cell[cell][c] : 0
+__global__ void cell_max_bwd_kernel(const int* __restrict__ win, const long long* __restrict__ acc, const int* __restrict__ cell,
+                                    float* __restrict__ dnet, int T, long long ncell, int C, int ldd, int accumulate, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % C);
+  const long long pt = i / C, b = pt / T;
+  const long long g = (b * ncell + cell[pt]) * C + c;
+  const float v = (win[g] == (int)(pt - b * T)) ? (float)((double)acc[g] * (1.0 / FIX_SCALE)) : 0.f;
   float* o = dnet + pt * ldd + c;
   *o = accumulate ? *o + v : v;
 }
@@ -377,14 +398,14 @@ inline unsigned nblk(long long n, int t = 256) { return (unsigned)((n + t - 1) /
 extern "C" {
 
 int sfmi_relu_bwd_f32(const float* dy, const float* y, float* dx, long long n, void* stream) {
-  if (!dy || !y || !dx || n % 4) return SFMI_EINVAL;
+  if (!dy || !y || !dx || n <= 0 || n % 4) return SFMI_EINVAL;
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(nblk(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n / 4);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
 
 int sfmi_lincomb_f32(float a, const float* x, float b, const float* y, float* out, long long n, void* stream) {
-  if (!x || !out) return SFMI_EINVAL;
+  if (!x || !out || n <= 0) return SFMI_EINVAL;
   hipLaunchKernelGGL(lincomb_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, a, x, b, y, out, n);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -392,7 +413,7 @@ int sfmi_lincomb_f32(float a, const float* x, float b, const float* y, float* ou
 
 int sfmi_affine2_cl_f32(const float* u, const float* v, const float* A, const float* Bc, const float* Cc, float* out, int B,
                         long long V, int C, void* stream) {
-  if (!u || !v || !A || !Bc || !Cc || !out) return SFMI_EINVAL;
+  if (!u || !v || !A || !Bc || !Cc || !out || B <= 0 || V <= 0 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * V * C;
   hipLaunchKernelGGL(affine2_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, u, v, A, Bc, Cc, out, V, C, total);
   SFMI_CHECK_LAUNCH();
@@ -401,14 +422,14 @@ int sfmi_affine2_cl_f32(const float* u, const float* v, const float* A, const fl
 
 /* partial: B*S*C*2 doubles with S = sfmi_gn_splits(V) */
 int sfmi_chan_dot_stats_f32(const float* dy, const float* x, double* partial, int B, long long V, int C, int S, void* stream) {
-  if (!dy || !x || !partial || S <= 0 || C % 4 || C > 1024) return SFMI_EINVAL;
+  if (!dy || !x || !partial || B <= 0 || V <= 0 || S <= 0 || C <= 0 || C % 4 || C > 1024) return SFMI_EINVAL;
   hipLaunchKernelGGL(chan_dot_stats_kernel, dim3(S, B), dim3(256), 0, (hipStream_t)stream, dy, x, partial, V, C, S);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
 
 int sfmi_upsample2_cl_f32(const float* x, float* y, int B, int D, int H, int W, int C, void* stream) {
-  if (!x || !y) return SFMI_EINVAL;
+  if (!x || !y || B <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * 8 * D * H * W * C;
   hipLaunchKernelGGL(upsample2_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, y, D, H, W, C, total);
   SFMI_CHECK_LAUNCH();
@@ -416,7 +437,7 @@ int sfmi_upsample2_cl_f32(const float* x, float* y, int B, int D, int H, int W, 
 }
 
 int sfmi_sumpool2_cl_f32(const float* dy, float* dx, int B, int Do, int Ho, int Wo, int Ctot, int c0, int Cs, void* stream) {
-  if (!dy || !dx || c0 + Cs > Ctot) return SFMI_EINVAL;
+  if (!dy || !dx || B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cs <= 0 || c0 < 0 || c0 + Cs > Ctot) return SFMI_EINVAL;
   const long long total = (long long)B * Do * Ho * Wo * Cs;
   hipLaunchKernelGGL(sumpool2_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, Do, Ho, Wo, Ctot, c0, Cs, total);
   SFMI_CHECK_LAUNCH();
@@ -425,7 +446,7 @@ int sfmi_sumpool2_cl_f32(const float* dy, float* dx, int B, int Do, int Ho, int 
 
 int sfmi_maxpool2_bwd_cl_f32(const float* x, const float* y, const float* dy, float* dx, int B, int Do, int Ho, int Wo, int C,
                              void* stream) {
-  if (!x || !y || !dy || !dx) return SFMI_EINVAL;
+  if (!x || !y || !dy || !dx || B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * Do * Ho * Wo * C;
   hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, y, dy, dx, Do, Ho, Wo, C, total);
   SFMI_CHECK_LAUNCH();
@@ -433,7 +454,7 @@ int sfmi_maxpool2_bwd_cl_f32(const float* x, const float* y, const float* dy, fl
 }
 
 int sfmi_cells_f32(const float* cloud, int* cell, float* p_half, int B, int T, int G, void* stream) {
-  if (!cloud || !cell) return SFMI_EINVAL;
+  if (!cloud || !cell || B <= 0 || T <= 0 || G < 1 || G > 1024) return SFMI_EINVAL;   // G^3 must fit the int32 cell index
   const long long n = (long long)B * T;
   hipLaunchKernelGGL(cells_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, cloud, cell, p_half, n, G);
   SFMI_CHECK_LAUNCH();
@@ -443,7 +464,7 @@ int sfmi_cells_f32(const float* cloud, int* cell, float* p_half, int B, int T, i
 /* keys (B,ncell,C) int32 must be pre-filled with INT_MIN (hipMemset 0x80); out row stride ldo, column offset co */
 int sfmi_cell_max_f32(const float* net, const int* cell, int* keys, float* out, int B, int T, long long ncell, int C, int ldo, int co,
                       void* stream) {
-  if (!net || !cell || !keys || !out) return SFMI_EINVAL;
+  if (!net || !cell || !keys || !out || B <= 0 || T <= 0 || ncell <= 0 || C <= 0 || co < 0 || ldo < co + C) return SFMI_EINVAL;
   const long long total = (long long)B * T * C;
   hipLaunchKernelGGL(cell_max_scatter_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, net, cell, keys, T, ncell, C, total);
   hipLaunchKernelGGL(cell_gather_max_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, keys, cell, out, T, ncell, C, ldo, co, total);
@@ -454,24 +475,43 @@ int sfmi_cell_max_f32(const float* net, const int* cell, int* keys, float* out, 
 /* acc (B,ncell,C) int64 zeroed by the caller; src row stride lds, column offset cs; count (B,ncell) optional */
 int sfmi_cell_scatter_add_f32(const float* src, const int* cell, long long* acc, int* count, int B, int T, long long ncell, int C,
                               int lds, int cs, void* stream) {
-  if (!src || !cell || !acc) return SFMI_EINVAL;
+  if (!src || !cell || !acc || B <= 0 || T <= 0 || ncell <= 0 || C <= 0 || cs < 0 || lds < cs + C) return SFMI_EINVAL;
   const long long total = (long long)B * T * C;
   hipLaunchKernelGGL(cell_scatter_add_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, src, cell, acc, count, T, ncell, C, lds, cs, total);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
 
-int sfmi_cell_max_bwd_f32(const float* net, const int* keys, const long long* acc, const int* cell, float* dnet, int B, int T,
-                          long long ncell, int C, int ldd, int accumulate, void* stream) {
-  if (!net || !keys || !acc || !cell || !dnet) return SFMI_EINVAL;
+/* win (B,ncell,C) int32: scratch, contents ignored on entry; on return the lowest index (within its sample) of the points that attain
+ * the maximum of every occupied (cell, channel).  dnet row stride ldd. */
+int sfmi_cell_max_bwd_ws_f32(const float* net, const int* keys, const long long* acc, const int* cell, int* win, float* dnet, int B, int T,
+                             long long ncell, int C, int ldd, int accumulate, void* stream) {
+  if (!net || !keys || !acc || !cell || !win || !dnet || B <= 0 || T <= 0 || ncell <= 0 || C <= 0 || ldd < C) return SFMI_EINVAL;
   const long long total = (long long)B * T * C;
-  hipLaunchKernelGGL(cell_max_bwd_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, net, keys, acc, cell, dnet, T, ncell, C, ldd, accumulate, total);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cell_win_reset_kernel, dim3(nblk(total)), dim3(256), 0, st, cell, win, T, ncell, C, total);
+  hipLaunchKernelGGL(cell_win_min_kernel, dim3(nblk(total)), dim3(256), 0, st, net, keys, cell, win, T, ncell, C, total);
+  hipLaunchKernelGGL(cell_max_bwd_kernel, dim3(nblk(total)), dim3(256), 0, st, win, acc, cell, dnet, T, ncell, C, ldd, accumulate, total);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }
 
+/* The same without a caller's scratch: the winner buffer is taken from and returned to the device's stream-ordered pool around the three
+ * launches (the only allocation libsfmi makes; the trainer passes its own buffer to the _ws form above). */
+int sfmi_cell_max_bwd_f32(const float* net, const int* keys, const long long* acc, const int* cell, float* dnet, int B, int T,
+                          long long ncell, int C, int ldd, int accumulate, void* stream) {
+  if (!net || !keys || !acc || !cell || !dnet || B <= 0 || T <= 0 || ncell <= 0 || C <= 0 || ldd < C) return SFMI_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  int* win = nullptr;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&win), (size_t)B * (size_t)ncell * (size_t)C * sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  const int rc = sfmi_cell_max_bwd_ws_f32(net, keys, acc, cell, win, dnet, B, T, ncell, C, ldd, accumulate, stream);
+  e = hipFreeAsync(win, st);
+  return rc != SFMI_OK ? rc : (int)e;
+}
+
 int sfmi_cell_mean_f32(const long long* acc, const int* count, float* grid, int B, long long ncell, int C, void* stream) {
-  if (!acc || !count || !grid) return SFMI_EINVAL;
+  if (!acc || !count || !grid || B <= 0 || ncell <= 0 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * ncell * C;
   hipLaunchKernelGGL(cell_mean_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, acc, count, grid, C, total);
   SFMI_CHECK_LAUNCH();
@@ -480,7 +520,7 @@ int sfmi_cell_mean_f32(const long long* acc, const int* count, float* grid, int 
 
 int sfmi_cell_mean_bwd_f32(const float* dgrid, const int* count, const int* cell, float* dc, int B, int T, long long ncell, int C,
                            void* stream) {
-  if (!dgrid || !count || !cell || !dc) return SFMI_EINVAL;
+  if (!dgrid || !count || !cell || !dc || B <= 0 || T <= 0 || ncell <= 0 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * T * C;
   hipLaunchKernelGGL(cell_mean_bwd_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, dgrid, count, cell, dc, T, ncell, C, total);
   SFMI_CHECK_LAUNCH();
@@ -489,7 +529,7 @@ int sfmi_cell_mean_bwd_f32(const float* dgrid, const int* count, const int* cell
 
 /* xyz (B,N,3) in [-1,1]; grid (B,G,G,G,C) -> out (B,N,C) */
 int sfmi_trilinear_cl_f32(const float* xyz, const float* grid, float* out, int B, long long N, int G, int C, void* stream) {
-  if (!xyz || !grid || !out) return SFMI_EINVAL;
+  if (!xyz || !grid || !out || B <= 0 || N <= 0 || G < 1 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * N * C;
   hipLaunchKernelGGL((trilinear_kernel<false>), dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, xyz, grid, out, nullptr, nullptr, N, G, C, total);
   SFMI_CHECK_LAUNCH();
@@ -498,7 +538,7 @@ int sfmi_trilinear_cl_f32(const float* xyz, const float* grid, float* out, int B
 
 /* acc (B,G,G,G,C) int64 zeroed by the caller; convert with sfmi_fixed_to_float_f32 */
 int sfmi_trilinear_bwd_cl_f32(const float* xyz, const float* dout, long long* acc, int B, long long N, int G, int C, void* stream) {
-  if (!xyz || !dout || !acc) return SFMI_EINVAL;
+  if (!xyz || !dout || !acc || B <= 0 || N <= 0 || G < 1 || C <= 0) return SFMI_EINVAL;
   const long long total = (long long)B * N * C;
   hipLaunchKernelGGL((trilinear_kernel<true>), dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, xyz, nullptr, nullptr, dout, acc, N, G, C, total);
   SFMI_CHECK_LAUNCH();
@@ -507,7 +547,7 @@ int sfmi_trilinear_bwd_cl_f32(const float* xyz, const float* dout, long long* ac
 
 int sfmi_bce_logits_f32(const float* logits, const float* label, float* loss_rows, float* dlogits, long long n, float scale,
                         void* stream) {
-  if (!logits || !label || !loss_rows || !dlogits) return SFMI_EINVAL;
+  if (!logits || !label || !loss_rows || !dlogits || n <= 0) return SFMI_EINVAL;
   hipLaunchKernelGGL(bce_logits_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, logits, label, loss_rows, dlogits, n, scale);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -515,7 +555,7 @@ int sfmi_bce_logits_f32(const float* logits, const float* label, float* loss_row
 
 /* sums (K,D) int64 and counts (K) int32 zeroed by the caller */
 int sfmi_vq_stats_f32(const float* x, const int* idx, long long* sums, int* counts, long long rows, int D, void* stream) {
-  if (!x || !idx || !sums || !counts) return SFMI_EINVAL;
+  if (!x || !idx || !sums || !counts || rows <= 0 || D <= 0) return SFMI_EINVAL;
   const long long total = rows * D;
   hipLaunchKernelGGL(vq_stats_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, idx, sums, counts, D, total);
   SFMI_CHECK_LAUNCH();
@@ -524,7 +564,7 @@ int sfmi_vq_stats_f32(const float* x, const int* idx, long long* sums, int* coun
 
 int sfmi_vq_ema_update_f32(float* N, float* z_avg, float* emb, const float* counts, const float* sums, int K, int D, float gamma,
                            float eps, void* stream) {
-  if (!N || !z_avg || !emb || !counts || !sums) return SFMI_EINVAL;
+  if (!N || !z_avg || !emb || !counts || !sums || K <= 0 || D <= 0) return SFMI_EINVAL;
   hipLaunchKernelGGL(vq_ema_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, N, z_avg, emb, counts, sums, K, D, gamma, eps);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -534,7 +574,9 @@ int sfmi_vq_ema_update_f32(float* N, float* z_avg, float* emb, const float* coun
  * row slices of `rows_per_split` output voxels (multiple of 16); reduce over nsplit with sfmi_colsum_f32. */
 int sfmi_conv3d_wgrad_f32(const float* dy, const float* x, float* part, int B, int Di, int Hi, int Wi, int Cin, int Cout, int KS,
                           int stride, int pad, int ldy, int ldx, int nsplit, void* stream) {
-  if (!dy || !x || !part || nsplit <= 0 || KS <= 0 || stride <= 0) return SFMI_EINVAL;
+  if (!dy || !x || !part || nsplit <= 0 || KS <= 0 || stride <= 0 || pad < 0 || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 ||
+      ldy < Cout || ldx < Cin || KS > Di + 2 * pad || KS > Hi + 2 * pad || KS > Wi + 2 * pad)
+    return SFMI_EINVAL;
   WgArgs a;
   a.dy = dy; a.x = x; a.part = part; a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.KS = KS; a.stride = stride;
   a.pad = pad; a.ldy = ldy; a.ldx = ldx;

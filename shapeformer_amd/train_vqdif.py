@@ -299,11 +299,12 @@ class VQDIFTrainer:
             _ck(lib.sfmi_cell_max_f32(L.ptr(net), L.ptr(cell), L.ptr(keys), L.ptr(cat), B, T, ncell, 32, 64, 32, L.stream_ptr()), "cell_max")
 
             def bwd(dcat, net=net, keys=keys):
-                # left half: identity; right half: pooled -> scatter to cells, route to the arg-max points
+                # left half: identity; right half: pooled -> scatter to cells, route to the one arg-max point of each (cell, channel)
                 acc = torch.zeros(B, ncell, 32, device=self.dev, dtype=torch.int64)
                 _ck(lib.sfmi_cell_scatter_add_f32(L.ptr(dcat), L.ptr(cell), L.ptr(acc), None, B, T, ncell, 32, 64, 32, L.stream_ptr()), "cell_scatter")
                 dnet = dcat[:, :32].contiguous()
-                _ck(lib.sfmi_cell_max_bwd_f32(L.ptr(net), L.ptr(keys), L.ptr(acc), L.ptr(cell), L.ptr(dnet), B, T, ncell, 32, 32, 1,
+                win = torch.empty(B, ncell, 32, device=self.dev, dtype=torch.int32)     # transient: the arg-max point of every (cell, channel)
+                _ck(lib.sfmi_cell_max_bwd_ws_f32(L.ptr(net), L.ptr(keys), L.ptr(acc), L.ptr(cell), L.ptr(win), L.ptr(dnet), B, T, ncell, 32, 32, 1,
                                               L.stream_ptr()), "cell_max_bwd")
                 return [dnet]
             self.tape.add(cat, [net], bwd)

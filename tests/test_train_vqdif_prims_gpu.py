@@ -1,7 +1,9 @@
 """GPU: every backward primitive of the VQDIF training step (csrc/train_vqdif.hip + the reused forward kernels) against
 torch autograd of the same op in float64: GEMM / Linear weight gradient, conv3d forward / weight gradient / input
 gradient (3^3 pad 1, 2^3 stride 2), GroupNorm, max-pool with ties, nearest upsample + concat, trilinear sampling,
-the encoder's local max pool and scatter-mean.  Tolerance 2e-5 (max-normalised) - these are exact up to fp32 rounding."""
+the encoder's local max pool and scatter-mean.  Tolerance 2e-5 (max-normalised) - these are exact up to fp32 rounding.
+Every entry at every launch form, with derived per-element bounds, guard bands and the tie contract of the local max-pool
+backward: tests/test_train_vqdif_kernels_gpu.py."""
 import os
 import sys
 
