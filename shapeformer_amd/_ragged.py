@@ -7,6 +7,11 @@ A ragged batch is B sets stored back to back with (B+1,) exclusive offsets: off[
 means one set.  Every check here runs on the host and raises SfmiError before the library is loaded, so a refused call launches
 nothing.  Where the tensors live is NOT part of `mesh_args` / `point_sets`: a caller finishes its own host checks and then calls
 `on_device`, last, so a CPU tensor reports the first wrong argument and not the device.
+
+What a caller's tensor may look like is one contract for every public entry point (stated in tests/input_forms.py, held by
+tests/test_input_forms_cpu.py / _gpu.py): a strided view, a float64 cloud, int64 faces or offsets in any integer form give the bits of
+the canonical call - `mesh_args`, `.float().contiguous()` after `point_sets`, `i32_dev` are how - or are refused here on the host; a
+caller's output buffer of another dtype or layout is always refused.  A new public function gets a row in that table.
 """
 from __future__ import annotations
 

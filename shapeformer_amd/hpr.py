@@ -130,12 +130,26 @@ def sample_cameras(B, radius=10, seed=0, shape0=0):
 
 def resample_visible_dev(x, o, visible, count, context_N, noise=0., seed=0, shape0=0):
     """x (N,3) flat device tensor, o host offsets, visible (N,) uint8, count (B,) int32 -> (B, context_N, 3) f32 (csrc/hpr.hip).
-    A shape without points gives NaN rows."""
-    dev, B, N = x.device, len(o) - 1, x.shape[0]
+    A shape without points gives NaN rows.  x: f32 or f64 of any layout (another dtype is read as f32), visible: N bytes, booleans or
+    integers (non-zero: visible), count: B integers; tensors that already have the kernel's dtype and layout are used as they are."""
+    what = "resample_visible_dev"
+    x = _ragged.points_arg(x, what)
+    if x.dim() != 2:
+        raise L.SfmiError(f"{what}: expected flat (N,3) points, got {tuple(x.shape)}")
+    o = _ragged.host_offsets(o, x.shape[0], f"{what} offsets", empty_ok=True)
+    B, N = len(o) - 1, x.shape[0]
+    if not isinstance(visible, torch.Tensor) or visible.numel() != N or visible.dtype.is_floating_point:
+        raise L.SfmiError(f"{what}: visible must be a tensor of {N} bytes, one per point")
+    if not isinstance(count, torch.Tensor) or count.numel() != B or count.dtype.is_floating_point or count.dtype == torch.bool:
+        raise L.SfmiError(f"{what}: count must be a tensor of {B} integers, one per shape")
     if context_N < 0 or noise < 0:
         raise L.SfmiError("virtual_scan_dev: context_N and noise must be >= 0")
+    dev = on_device(what, x, visible, count)
+    x = (x if x.dtype in (torch.float32, torch.float64) else x.float()).contiguous()
+    count = count.reshape(-1).to(torch.int32).contiguous()
     out = torch.empty(B, context_N, 3, device=dev, dtype=torch.float32)
     v = visible.reshape(-1)
+    v = (v if v.dtype == torch.uint8 else (v != 0).to(torch.uint8)).contiguous()
     prefix = (torch.cumsum(v, 0, dtype=torch.int32) - v).to(torch.int32).contiguous()
     od = torch.from_numpy(o).to(dev)
     L.check(L.lib().sfmi_hpr_resample_f32(L.ptr(x), int(x.dtype == torch.float64), L.ptr(v), L.ptr(prefix), L.ptr(od), L.ptr(count),

@@ -49,6 +49,8 @@ def _check(coarse_Q, levels, margin):
 
 def table_field(F):
     """field(keys, koff) for a dense (B,Q,Q,Q) f32 device tensor: values F[b].flatten()[key] of every shape's keys."""
+    if not isinstance(F, torch.Tensor) or F.dim() != 4 or F.device.type != "cuda":
+        raise L.SfmiError("table_field: F must be a (B,Q,Q,Q) torch tensor on the HIP device (no CPU fallback)")
     F = F.contiguous().float()
     B, n3 = F.shape[0], F[0].numel()
     flat = F.reshape(-1)

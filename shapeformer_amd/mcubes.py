@@ -19,12 +19,13 @@ def marching_cubes_dev(occ: torch.Tensor, thresh: float = 0.5, bbox=((-1.0, -1.0
     """occ (B,Q,Q,Q) f32 on the HIP device (axes = grid axes 0,1,2 == x,y,z of nputil.makeGrid 'ij').
 
     -> verts (V,3) f32, faces (T,3) int32 (indices local to each shape), voff (B+1,), toff (B+1,) host int arrays."""
+    if not isinstance(occ, torch.Tensor) or occ.dim() != 4 or not (occ.shape[1] == occ.shape[2] == occ.shape[3]):
+        raise L.SfmiError(f"marching_cubes_dev: occ must be a (B,Q,Q,Q) torch tensor, got {tuple(getattr(occ, 'shape', ()))}")
     if occ.device.type != "cuda":
         raise L.SfmiError("marching_cubes_dev needs a HIP device tensor (no CPU fallback)")
     lib = L.lib()
     occ = occ.contiguous().float()
     B, Q = occ.shape[0], occ.shape[1]
-    assert occ.shape == (B, Q, Q, Q)
     ws = _ragged.workspace(lib.sfmi_mc_workspace_bytes(B, Q), occ.device)
     offs = torch.zeros(2 * (B + 1), device=occ.device, dtype=torch.int32)
     L.check(lib.sfmi_mc_count_f32(L.ptr(occ), float(thresh), B, Q, L.ptr(ws), L.ptr(offs), L.stream_ptr()), "sfmi_mc_count_f32")

@@ -191,6 +191,7 @@ def evaluate(Xct, completions, Xbd=None, tau=0.01, emd_n=None):
         completions = [f32_dev(c, dev) for c in completions]
     Xct = f32_dev(Xct, dev).reshape(-1, 3)
     cf, co = _pack(completions, "evaluate completions")
+    on_device("evaluate", cf, Xct, *([Xbd] if isinstance(Xbd, torch.Tensor) else []))       # every cloud, before the first launch
     k = len(co) - 1
     S = [cf[int(co[i]):int(co[i + 1])] for i in range(k)]
     per, mean = uhd(Xct, S)
@@ -492,7 +493,7 @@ def chamfer_dist(p1, p2):
 def chamfer_distance(points1, points2, use_kdtree=True, give_id=False):
     """vqdif/common.py chamfer_distance on (B,N,3) / (B,M,3) batches: chamfer1 = mean d2(points1 -> points2), chamfer2 =
     mean d2(points2 -> points1) per batch item; returns chamfer1 + chamfer2, or (chamfer1, chamfer2, idx_nn_12, idx_nn_21)
-    with give_id.  torch in -> torch out on the input's device (f32 means, int64 indices); numpy in -> numpy out.
+    with give_id.  torch in -> torch out on the input's device (means in points1's dtype, int64 indices; the search itself is f32); numpy in -> numpy out.
     use_kdtree is accepted and ignored (the search is exact either way)."""
     as_np = not isinstance(points1, torch.Tensor)
     a = f32_dev(points1)

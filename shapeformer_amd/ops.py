@@ -17,9 +17,27 @@ def _chk_cuda(*ts):
             raise L.SfmiError("libsfmi kernels need CUDA/HIP device tensors (no CPU fallback)")
 
 
-def _c(t, dtype):
-    assert t.dtype == dtype, (t.dtype, dtype)
+def _c(t, dtype, name="tensor"):
+    """a kernel's input in the dtype it reads, contiguous (the tensor itself when it already is); another dtype is refused"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise L.SfmiError(f"libsfmi: {name} must be a {dtype} torch tensor, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _need(cond, msg):
+    if not cond:
+        raise L.SfmiError(f"libsfmi: {msg}")
+
+
+def _out(out, numel, like, name="out"):
+    """a caller's output buffer goes to the kernel as it is: f32, contiguous, `numel` elements, on the inputs' device - converting it
+    would lose the result, so every other form is refused"""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != numel:
+        got = f"{out.dtype} {tuple(out.shape)}{'' if out.is_contiguous() else ' strided'}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise L.SfmiError(f"libsfmi: {name} must be a contiguous float32 tensor of {numel} elements, got {got}")
+    _chk_cuda(out)
+    _need(out.device == like.device, f"{name} is on {out.device}, the inputs on {like.device}")
+    return out
 
 
 # ---------------------------------------------------------------- SDF query
@@ -37,11 +55,14 @@ def sdf_pack_weights(sd, prefix="decoder.") -> np.ndarray:
 
 def sdf_query(xyz, grid_cl, wpack, sigmoid=False, out=None):
     """xyz (B,N,3) in [-1,1]; grid_cl (B,G,G,G,32) channels-last; -> (B,N,1) logits."""
-    _chk_cuda(xyz, grid_cl, wpack)
-    xyz, grid_cl = _c(xyz, torch.float32), _c(grid_cl, torch.float32)
+    xyz, grid_cl, wpack = _c(xyz, torch.float32, "xyz"), _c(grid_cl, torch.float32, "grid_cl"), _c(wpack, torch.float32, "wpack")
+    _need(xyz.dim() == 3 and xyz.shape[2] == 3 and grid_cl.dim() == 5, f"xyz (B,N,3) and grid_cl (B,G,G,G,32), got {tuple(xyz.shape)}, {tuple(grid_cl.shape)}")
     B, N, _ = xyz.shape
     G = grid_cl.shape[1]
-    assert grid_cl.shape == (B, G, G, G, 32)
+    _need(grid_cl.shape == (B, G, G, G, 32), f"grid_cl must be ({B},G,G,G,32), got {tuple(grid_cl.shape)}")
+    if out is not None:
+        _out(out, B * N, xyz)
+    _chk_cuda(xyz, grid_cl, wpack)
     if out is None:
         out = torch.empty(B, N, 1, device=xyz.device, dtype=torch.float32)
     L.check(L.lib().sfmi_sdf_query_f32(L.ptr(xyz), L.ptr(grid_cl), L.ptr(wpack), L.ptr(out), B, N, G,
@@ -52,11 +73,13 @@ def sdf_query(xyz, grid_cl, wpack, sigmoid=False, out=None):
 def sdf_query_keys(axis, keys, koff, grid_cl, wpack, sigmoid=False):
     """Keyed lattice points (csrc/sdf_query.hip KEYS): axis (Q) f32 table, keys (n) int32 shape-local fine indices (ix*Q+iy)*Q+iz ascending
     per shape, koff (B+1) int32 device offsets -> (n) values, each equal to sdf_query_grid's value at (shape, key) bit for bit."""
-    _chk_cuda(axis, keys, koff, grid_cl, wpack)
-    axis, grid_cl = _c(axis, torch.float32), _c(grid_cl, torch.float32)
-    keys, koff = _c(keys, torch.int32), _c(koff, torch.int32)
+    axis, grid_cl, wpack = _c(axis, torch.float32, "axis"), _c(grid_cl, torch.float32, "grid_cl"), _c(wpack, torch.float32, "wpack")
+    keys, koff = _c(keys, torch.int32, "keys"), _c(koff, torch.int32, "koff")
+    _need(grid_cl.dim() == 5, f"grid_cl must be (B,G,G,G,32), got {tuple(grid_cl.shape)}")
     B, G = grid_cl.shape[0], grid_cl.shape[1]
-    assert grid_cl.shape == (B, G, G, G, 32) and koff.shape == (B + 1,) and keys.dim() == 1
+    _need(grid_cl.shape == (B, G, G, G, 32) and koff.shape == (B + 1,) and keys.dim() == 1,
+          f"grid_cl (B,G,G,G,32), koff (B+1,), keys (n,), got {tuple(grid_cl.shape)}, {tuple(koff.shape)}, {tuple(keys.shape)}")
+    _chk_cuda(axis, keys, koff, grid_cl, wpack)
     out = torch.empty(keys.numel(), device=axis.device, dtype=torch.float32)
     L.check(L.lib().sfmi_sdf_query_keys_f32(L.ptr(axis), axis.numel(), L.ptr(keys), L.ptr(koff), keys.numel(), L.ptr(grid_cl), L.ptr(wpack),
                                             L.ptr(out), B, G, int(sigmoid), L.stream_ptr()), "sfmi_sdf_query_keys_f32")
@@ -65,12 +88,14 @@ def sdf_query_keys(axis, keys, koff, grid_cl, wpack, sigmoid=False):
 
 def sigmoid(x, out=None):
     """nputil.sigmoid of a device logits tensor (in-tree kernel: the SDF query's own epilogue expression)."""
+    x = _c(x, torch.float32, "x")
+    if out is not None:
+        _out(out, x.numel(), x)
+        _need(out.data_ptr() % 16 == 0, "out must start on a 16-byte line (the kernel writes float4)")
     _chk_cuda(x)
-    x = _c(x, torch.float32)
     if x.data_ptr() % 16:          # a contiguous view that starts inside a 16-byte line: the kernel reads float4
         x = x.clone()
     out = torch.empty_like(x) if out is None else out
-    assert out.data_ptr() % 16 == 0 and out.is_contiguous()
     L.check(L.lib().sfmi_sigmoid_f32(L.ptr(x), L.ptr(out), x.numel(), L.stream_ptr()), "sfmi_sigmoid_f32")
     return out
 
@@ -79,15 +104,18 @@ def sdf_query_grid(axis, grid_cl, wpack, sigmoid=False, out=None, x_range=None, 
     """Structured Q^3 'ij' query grid from a Q-entry f32 axis table -> (B,Q^3,1); x_range = (x0, x1): only the planes x0 <= ix < x1 of
     the slowest lattice index -> (B,(x1-x0) Q^2,1), the same values the whole-lattice call computes for them.  affine = (scale, shift)
     (B,32) each: grid_cl is the decoder grid BEFORE its last GroupNorm, whose affine the kernel applies to the interpolated features."""
-    _chk_cuda(axis, grid_cl, wpack)
-    axis, grid_cl = _c(axis, torch.float32), _c(grid_cl, torch.float32)
+    axis, grid_cl, wpack = _c(axis, torch.float32, "axis"), _c(grid_cl, torch.float32, "grid_cl"), _c(wpack, torch.float32, "wpack")
     Q = axis.numel()
     x0, x1 = (0, Q) if x_range is None else (int(x_range[0]), int(x_range[1]))
+    _need(grid_cl.dim() == 5 and 0 <= x0 <= x1 <= Q, f"grid_cl (B,G,G,G,32) and 0 <= x0 <= x1 <= Q, got {tuple(grid_cl.shape)}, {(x0, x1)}")
     B, G = grid_cl.shape[0], grid_cl.shape[1]
+    sc, sh = (None, None) if affine is None else (_c(affine[0], torch.float32, "affine scale"), _c(affine[1], torch.float32, "affine shift"))
+    _need(affine is None or (sc.shape == (B, 32) and sh.shape == (B, 32)), f"affine = (scale, shift), ({B},32) each")
+    if out is not None:
+        _out(out, B * (x1 - x0) * Q * Q, axis)
+    _chk_cuda(axis, grid_cl, wpack, sc, sh)
     if out is None:
         out = torch.empty(B, (x1 - x0) * Q * Q, 1, device=axis.device, dtype=torch.float32)
-    sc, sh = (None, None) if affine is None else (_c(affine[0], torch.float32), _c(affine[1], torch.float32))
-    assert affine is None or (sc.shape == (B, 32) and sh.shape == (B, 32))
     L.check(L.lib().sfmi_sdf_query_grid_aff_f32(L.ptr(axis), Q, x0, x1, L.ptr(grid_cl), L.ptr(sc), L.ptr(sh), L.ptr(wpack), L.ptr(out), B, G,
                                                 int(sigmoid), L.stream_ptr()), "sfmi_sdf_query_grid_aff_f32")
     return out
@@ -109,18 +137,21 @@ def sdf_pack_weights_grad(sd, prefix="decoder.") -> np.ndarray:
 def _sdf_grad_launch(xyz, grid_cl, wpack_grad, off, level=0.0, max_step=0.0, step=False, normals=False):
     """One launch of the gradient kernel.  xyz (B,N,3) with off None (equal offsets are built), or (N,3) with off (B+1) int32 device
     offsets (ragged).  -> val, grad, xyz_out or None, normal or None, shaped like the input."""
-    _chk_cuda(xyz, grid_cl, wpack_grad, off)
-    xyz, grid_cl = _c(xyz, torch.float32), _c(grid_cl, torch.float32)
+    xyz, grid_cl, wpack_grad = _c(xyz, torch.float32, "xyz"), _c(grid_cl, torch.float32, "grid_cl"), _c(wpack_grad, torch.float32, "wpack_grad")
+    _need(grid_cl.dim() == 5, f"grid_cl must be (B,G,G,G,32), got {tuple(grid_cl.shape)}")
     B, G = grid_cl.shape[0], grid_cl.shape[1]
-    assert grid_cl.shape == (B, G, G, G, 32) and wpack_grad.numel() == L.lib().sfmi_sdf_pack_grad_floats()
+    _need(grid_cl.shape == (B, G, G, G, 32), f"grid_cl must be ({B},G,G,G,32), got {tuple(grid_cl.shape)}")
     if off is None:
-        assert xyz.dim() == 3 and xyz.shape[0] == B and xyz.shape[2] == 3, tuple(xyz.shape)
-        off = torch.arange(B + 1, device=xyz.device, dtype=torch.int32) * xyz.shape[1]
+        _need(xyz.dim() == 3 and xyz.shape[0] == B and xyz.shape[2] == 3, f"xyz must be ({B},N,3), got {tuple(xyz.shape)}")
         vshape = (B, xyz.shape[1], 1)
     else:
-        off = _c(off, torch.int32)
-        assert xyz.dim() == 2 and xyz.shape[1] == 3 and off.shape == (B + 1,), (tuple(xyz.shape), tuple(off.shape))
+        off = _c(off, torch.int32, "off")
+        _need(xyz.dim() == 2 and xyz.shape[1] == 3 and off.shape == (B + 1,), f"xyz (N,3) with off ({B + 1},), got {tuple(xyz.shape)}, {tuple(off.shape)}")
         vshape = (xyz.shape[0],)
+    _chk_cuda(xyz, grid_cl, wpack_grad, off)
+    _need(wpack_grad.numel() == L.lib().sfmi_sdf_pack_grad_floats(), "wpack_grad is not sdf_pack_weights_grad's image")
+    if off is None:
+        off = torch.arange(B + 1, device=xyz.device, dtype=torch.int32) * xyz.shape[1]
     n = xyz.numel() // 3
     val = torch.empty(vshape, device=xyz.device, dtype=torch.float32)
     grad = torch.empty_like(xyz)

@@ -754,6 +754,7 @@ def isolate_object_dev(points, off=None, plane_threshold=0.01, cluster_radius=0.
     check_count(min_points, what, "min_points")
     x, o, shape = point_sets(points, off, what)
     B = len(o) - 1
+    up = np.asarray(up.detach().cpu().numpy() if isinstance(up, torch.Tensor) else up, np.float64)      # host or device, as upright_rotation takes it
     keep, planes, taken = remove_planes_dev(x, o, plane_threshold, max_planes, min_ratio, hypotheses, seed)
     dev = x.device
     xf = x.float().contiguous()

@@ -527,6 +527,13 @@ class VQDIF:
         return self.quantizer.get_code_cl(ind)
 
     def mode_of(self, idx, name="mode", rows=1):
+        """The most frequent code of idx (rows=B: one per shape) -> (rows,) int32 workspace view.  idx: an integer tensor of any layout
+        (an int32 contiguous one on the model's device is used as it is)."""
+        if not isinstance(idx, torch.Tensor) or idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool:
+            raise L.SfmiError("VQDIF.mode_of: idx must be an integer torch tensor on the model's device (no CPU fallback)")
+        if not idx.is_cuda or (self.dev.index is not None and idx.device.index != self.dev.index):
+            raise L.SfmiError(f"VQDIF.mode_of: idx is on {idx.device}, the model on {self.dev} (no CPU fallback)")
+        idx = idx.to(torch.int32).contiguous()
         hist = self._buf("hist", (rows * (self.K + 1),), torch.int32)
         mode = self._buf(name, (rows,), torch.int32)
         L.check(L.lib().sfmi_mode_i32(L.ptr(idx), idx.numel(), self.K + 1, rows, L.ptr(hist), L.ptr(mode), L.stream_ptr()), "sfmi_mode_i32")
