@@ -543,6 +543,59 @@ int sfmi_mesh_occupancy_f32(const float* verts, const int* faces, const long lon
 int sfmi_sdf_jitter_f32(const float* X, int B, long long n, long long n_near, float near_std, float far_std, unsigned long long seed,
                         float* out, void* stream);
 
+/* ---- Mesh queries through a bounding-volume tree (csrc/meshtree.hip): the hierarchical route next to the brute force above, for
+ *      256^3 lattices and meshes of 10^5 faces (xgutils/geoutil.py:270,345 shape2sdf / shapes2sdfs at gridDim = 256).
+ * ORDER     face centroid ((a + b) + c) / 3 in f32, each operation rounded on its own; per axis t = (c - lo) / (hi - lo) with lo, hi the
+ *           shape's vertex bounding box (a flat axis: 0); u = clamp((int)floorf(t * 1024), 0, 1023); the 30-bit Morton key takes bit k
+ *           of ux, uy, uz to bits 3k+2, 3k+1, 3k.  Faces are sorted by (shape, key, face index): key = shape << 30 | Morton, sorted
+ *           stably by the caller.
+ * TOPOLOGY  implicit: leaves are runs of 64 consecutive sorted faces (the last may be short); level l + 1 groups 8 consecutive nodes
+ *           of level l until a level has one node, the root; a shape of at most 64 faces is one leaf that is also the root.  A shape's
+ *           nodes are stored level by level, leaves first, from noff[b]; sfmi_meshtree_nodes(T_b) of them.
+ * NODE      9 x float4: (aabb min, r) (aabb max, noprune) (p~, tr Q) (dipole, 0) and five more with the second and third moments.
+ *           aabb of the vertices of the faces below, exact; p~ = sum a_t c_t / sum a_t, the area-weighted centroid (the middle of the aabb
+ *           when the area is 0); dipole D = sum a_t n_t; r >= |v - p~| for every vertex v below, about the stored p~, rounded up;
+ *           noprune = 1 when a face below is a sliver (width <= 2^-8 longest edge).  About the stored p~: Q = sum (c_t - p~) (x) a_t n_t and
+ *           M = sum S_t (x) a_t n_t with S_t = (c_t - p~)(c_t - p~)^T + sum_k (v_k - c_t)(v_k - c_t)^T / 12, stored as the expansion reads them:
+ *           (Qxx, Qyy, Qzz, Qxy+Qyx) (Qxz+Qzx, Qyz+Qzy, gx, gy) (gz, Kxxx, Kyyy, Kzzz) (Kxxy, Kxxz, Kyyx, Kyyz) (Kzzx, Kzzy, Kxyz, 0) with
+ *           g_j = -6 sum_i M_iji - 3 sum_i M_iij and K the coefficients of the cubic form sum M_ijk r_i r_j r_k.  Degenerate faces
+ *           (meshsdf's rule) add no area.  The sums are f64 in a fixed order - a leaf's faces in order, a node's children in order, one
+ *           launch per level, no float atomics - taken about the origin and kept in mom (36 doubles per node: area, a c (3), D (3),
+ *           sum c (x) a n (9), sum S (x) a n (18, S in the order xx yy zz xy xz yz), sliver flag, pad); they are shifted to p~ in f64 and
+ *           the node holds them rounded to f32.
+ * STATUS    per shape: 0 ok, 1 no faces, 2 a vertex index outside the shape, 3 a non-finite vertex.  A shape's tree depends on that
+ *           shape alone: a batch equals per-shape calls bitwise. */
+int sfmi_meshtree_leaf_faces(void);
+long long sfmi_meshtree_nodes(long long T);
+/* bbox (B,6) f32 = min xyz, max xyz of each shape's vertices; keys (T) int64 as above; flags (B) int32 for sfmi_meshtree_build_f32 */
+int sfmi_meshtree_keys_f32(const float* verts, const int* faces, const long long* voff, const long long* toff, int B, long long T,
+                           float* bbox, long long* keys, int* flags, void* stream);
+/* order (T) int64: the faces' global indices sorted by key (stable); noff (B+1) int64: exclusive offsets of sfmi_meshtree_nodes(T_b);
+ * max_faces: the largest T_b.  -> rec (T x 5 float4) the packed face records of sfmi_mesh_sdf_f32 in sorted order, orig (T) int32 each
+ * sorted face's index local to its shape, nodes (NN x 9 float4), mom (NN x 36) f64, status (B) int32. */
+int sfmi_meshtree_build_f32(const float* verts, const int* faces, const long long* voff, const long long* toff, const long long* noff,
+                            const long long* order, const int* flags, int B, long long T, long long max_faces, void* rec, int* orig,
+                            void* nodes, double* mom, int* status, void* stream);
+/* Queries Q (N,3) f32 with qoff (B+1) int64, in any order (neighbours in memory should be neighbours in space: 64 consecutive queries
+ * of a set share one wave); boff (B+1) int64: exclusive offsets of ceil(N_b / 64), blocks = boff[B].  Outputs as sfmi_mesh_sdf_f32:
+ *   sqrt(d2), I (the ORIGINAL face index, lowest among equal f32 d2) and C are bit-identical to sfmi_mesh_sdf_f32 for finite inputs: a
+ *        node is skipped only when a lower bound of the face routine's d2 over its faces EXCEEDS the query's best (csrc/meshtree.hip);
+ *   W = W_tree: walking from the root, a node with |q - p~|^2 > (beta r)^2 (f32, direct form) adds, with r = p~ - q,
+ *        ((D . r + tr Q) / |r|^3 + (g . r / 2 - 3 r^T Q r) / |r|^5 + 7.5 K(r, r, r) / |r|^7) / 4 pi  (Barill et al. 2018, third order)
+ *        and is not entered; a leaf that fails the test adds its faces' exact solid angles / 4 pi (an f32 run in sorted order); an
+ *        internal node that fails it is descended.  Contributions are added as 2^-29 fixed-point integers: W_tree is a function of
+ *        (query, mesh, beta) alone - not of the batch, the order of the queries or the run;
+ *   S = -sqrt(d2) where |W_tree| > 0.5, else +sqrt(d2): the sign differs from sfmi_mesh_sdf_f32's only where |W| is near 0.5.
+ * A query of a shape with status != 0 gets S = NaN, I = -1, C = NaN, W = 0.  counters: NULL, or 3 uint64 that gain (faces evaluated,
+ * expansions taken, queries). */
+int sfmi_meshtree_query_f32(const float* Q, const long long* qoff, const long long* boff, long long blocks, const long long* toff,
+                            const long long* noff, const void* rec, const int* orig, const void* nodes, const int* status, int B, long long N,
+                            float beta, float* S, int* I, float* C, float* W, unsigned long long* counters, void* stream);
+/* occ (B,G,G,G) uint8 = (|W_tree| > 0.5) on sfmi_mesh_occupancy_f32's lattice, 0 for a shape with status != 0; one wave per 4 x 4 x 4
+ * block of lattice points, no workspace.  ceil(G / 4)^3 B < 2^31. */
+int sfmi_meshtree_occupancy_f32(const long long* toff, const long long* noff, const void* rec, const void* nodes, const int* status, int B, int G,
+                                const double* lo, const double* hi, float beta, unsigned char* occ, unsigned long long* counters, void* stream);
+
 /* ---- Hidden-point removal (csrc/hpr.hip): which points of a cloud a camera sees, by vertex membership in the convex hull of the
  *      spherically flipped cloud plus the viewpoint.  xgutils/geoutil.py:58-74 (hidden_point_removal: spherical flip, then
  *      scipy.spatial.ConvexHull), shapeformer/data/partial.py:127-146 (VirtualScanSelector: camera on a sphere, resample, jitter). -- */

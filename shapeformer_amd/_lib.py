@@ -181,6 +181,13 @@ PROTOTYPES = {
     "sfmi_mesh_sdf_f32": (i32, [c_ptr] * 6 + [i32, i64, i64] + [c_ptr] * 7),
     "sfmi_mesh_occupancy_f32": (i32, [c_ptr] * 4 + [i32, i64, i32] + [c_ptr] * 6),
     "sfmi_sdf_jitter_f32": (i32, [c_ptr, i32, i64, i64, f32, f32, C.c_ulonglong, c_ptr, c_ptr]),
+    # mesh queries through a bounding-volume tree (csrc/meshtree.hip)
+    "sfmi_meshtree_leaf_faces": (i32, []),
+    "sfmi_meshtree_nodes": (i64, [i64]),
+    "sfmi_meshtree_keys_f32": (i32, [c_ptr] * 4 + [i32, i64] + [c_ptr] * 4),
+    "sfmi_meshtree_build_f32": (i32, [c_ptr] * 7 + [i32, i64, i64] + [c_ptr] * 6),
+    "sfmi_meshtree_query_f32": (i32, [c_ptr] * 3 + [i64] + [c_ptr] * 6 + [i32, i64, f32] + [c_ptr] * 6),
+    "sfmi_meshtree_occupancy_f32": (i32, [c_ptr] * 5 + [i32, i32, c_ptr, c_ptr, f32] + [c_ptr] * 3),
     # hidden-point removal (csrc/hpr.hip)
     "sfmi_hpr_workspace_bytes": (sz, [i32, i64]),
     "sfmi_hpr_visible": (i32, [c_ptr, i32, c_ptr, c_ptr, c_ptr, i32, i64, C.c_double] + [c_ptr] * 6),

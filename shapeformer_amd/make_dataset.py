@@ -4,12 +4,13 @@ shapeformer/data/imnet_datasets/utils.py:33-70, with the occupancy the IMNet2 st
     python -m shapeformer_amd.make_dataset MESH... --out ROOT --dataset NAME --split train [--grid 64] [--boundary-n 32768]
                                            [--cate NAME=GLOB ...] [--seed 0] [--batch K] [--scale 1.0]
                                            [--occupancy winding|morph|poisson] [--morph-grid 128] [--selem 6] [--morph-samples 1000000]
-                                           [--poisson-grid m*(grid-1)+1] [--orient tangent]
+                                           [--poisson-grid m*(grid-1)+1] [--orient tangent] [--winding brute|tree] [--beta 2.0]
 
 Each mesh (.obj / .off / .ply) is normalised with normalize_point_set (bounding box centred, longest side 2) and multiplied by
 --scale, then batches of K meshes go through the device: lattice occupancy on the grid^3 makeGrid lattice of [-1, 1]^3 and
 area-weighted surface samples (sample_mesh_dev).  --occupancy winding (the default) is mesh_occupancy_dev's inside test |W| > 0.5: for
-closed, consistently oriented meshes.  --occupancy morph is for triangle soups (open shells, interior partitions, doubled and flipped
+closed, consistently oriented meshes; --winding tree takes it through meshtree's bounding-volume tree (|W_tree| > 0.5 with far-field
+expansions beyond --beta radii), the route for --grid 256.  --occupancy morph is for triangle soups (open shells, interior partitions, doubled and flipped
 faces): morph_voxelization_dev's watertight voxels on a --morph-grid^3 grid (closing with a ball of --selem cells over --morph-samples
 surface samples), read at each lattice point from the cell that holds it; the outside is flooded from voxel (0,0,0), so a shape that
 fills the box needs --scale 0.9 or so to keep that corner empty.  --occupancy poisson is for scans: the inputs are .ply point clouds
@@ -36,6 +37,7 @@ import numpy as np
 
 
 OCCUPANCY = ("winding", "morph", "poisson")
+WINDING = ("brute", "tree")
 
 
 def write_imnet_store(root, dataset, split, Xbd, occ, cates=None):
@@ -118,12 +120,14 @@ def _poisson_batch(paths, grid, poisson_grid, boundary_n, scale, seed, dev, orie
 
 def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, cates=None, seed=0, batch=8, device="cuda:0",
                  log=None, occupancy="winding", morph_grid=128, selem=6, morph_samples=1_000_000, scale=1.0, poisson_grid=None,
-                 orient=None):
+                 orient=None, winding="brute", beta=2.0):
     """Read, normalise and sample every mesh of `paths`; write the store.  cates: {name: glob} matched against each path.
     occupancy: "winding" (mesh_occupancy_dev), "morph" (morph_voxelization_dev on a morph_grid^3 grid, ball of selem cells,
     morph_samples surface samples) or "poisson" (paths are .ply clouds with normals: poisson_field_dev on a poisson_grid^3 lattice);
     scale multiplies the normalised vertices (poisson: the cloud as it is) on every route.  orient="tangent" (poisson only): clouds
-    without normals get normals over estimate_normals_dev's default neighbourhood, oriented outward by tangent-plane propagation."""
+    without normals get normals over estimate_normals_dev's default neighbourhood, oriented outward by tangent-plane propagation.
+    winding (the "winding" route only): "brute" (mesh_occupancy_dev) or "tree" (meshtree.mesh_occupancy_tree_dev at `beta`, for grids of
+    256 and meshes of 10^5 faces)."""
     import torch
     from . import meshio, meshsdf
     from ._ragged import batch_meshes
@@ -132,6 +136,10 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
         raise ValueError(f"occupancy = {occupancy!r} must be one of {OCCUPANCY}")
     if not (np.isfinite(scale) and scale > 0):
         raise ValueError(f"scale = {scale!r} must be a positive number")
+    if winding not in WINDING:
+        raise ValueError(f"winding = {winding!r} must be one of {WINDING}")
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError(f"beta = {beta!r} must be a number >= 0")
     if occupancy == "poisson":
         check_poisson_grid(grid, poisson_grid)
     if orient not in (None, "tangent") or (orient is not None and occupancy != "poisson"):
@@ -160,6 +168,9 @@ def make_dataset(paths, out, dataset, split="train", grid=64, boundary_n=32768, 
         v, f, voff, toff = batch_meshes(meshes, dev)
         if occupancy == "morph":
             o, st = _morph_occupancy(v, f, voff, toff, paths[s:s + batch], lattice, grid, morph_grid, selem, morph_samples, seed + s)
+        elif winding == "tree":
+            from . import meshtree
+            o, st = meshtree.mesh_occupancy_tree_dev(meshtree.mesh_tree_dev(v, f, voff, toff), grid_dim=grid, beta=float(beta), return_status=True)
         else:
             o, st = meshsdf.mesh_occupancy_dev(v, f, voff, toff, grid_dim=grid, return_status=True)
         x, st2 = sample_mesh_dev(v, f, voff, toff, boundary_n, seed=seed + s)
@@ -188,6 +199,9 @@ def parse_args(argv=None):
     ap.add_argument("--occupancy", choices=OCCUPANCY, default="winding",
                     help="winding: |W| > 0.5, for closed oriented meshes; morph: watertight voxelization, for triangle soups; "
                          "poisson: Poisson reconstruction of .ply point clouds with normals")
+    ap.add_argument("--winding", choices=WINDING, default="brute",
+                    help="winding: brute force over the faces, or the bounding-volume tree with far-field expansions (--grid 256, large meshes)")
+    ap.add_argument("--beta", type=float, default=2.0, help="--winding tree: a node farther than beta radii is approximated")
     ap.add_argument("--poisson-grid", type=int, default=None,
                     help="poisson: nodes per axis of the Poisson lattice, m * (grid - 1) + 1 (default: the smallest such >= 129)")
     ap.add_argument("--orient", choices=("tangent",), default=None,
@@ -203,6 +217,8 @@ def parse_args(argv=None):
         ap.error("--selem must lie in [0, 16]")
     if not (np.isfinite(a.scale) and a.scale > 0):
         ap.error("--scale must be a positive number")
+    if not (np.isfinite(a.beta) and a.beta >= 0):
+        ap.error("--beta must be a number >= 0")
     if a.occupancy == "poisson":
         try:
             check_poisson_grid(a.grid, a.poisson_grid)
@@ -224,7 +240,8 @@ def main(argv=None):
     a = parse_args(argv)
     d = make_dataset(a.meshes, a.out, a.dataset, a.split, a.grid, a.boundary_n, a.cates, a.seed, max(1, a.batch),
                      log=lambda m: print(m, file=sys.stderr), occupancy=a.occupancy, morph_grid=a.morph_grid, selem=a.selem,
-                     morph_samples=a.morph_samples, scale=a.scale, poisson_grid=a.poisson_grid, orient=a.orient)
+                     morph_samples=a.morph_samples, scale=a.scale, poisson_grid=a.poisson_grid, orient=a.orient, winding=a.winding,
+                     beta=a.beta)
     print(d)
 
 

@@ -119,23 +119,37 @@ def _one_mesh(vert, face):
     return batch_meshes([(np.asarray(vert).reshape(-1, 3), np.asarray(face).reshape(-1, 3))], torch.device("cuda"))
 
 
-def signed_distance(queries, vert, face):
-    """geoutil.signed_distance: (S f64 with NaN -> 0 as np.nan_to_num, I int64 closest face, C (N,3) f64 closest point)."""
+def _method(method, what):
+    if method not in ("brute", "tree"):
+        raise L.SfmiError(f"{what}: method must be 'brute' or 'tree', got {method!r}")
+    return method
+
+
+def signed_distance(queries, vert, face, method="brute"):
+    """geoutil.signed_distance: (S f64 with NaN -> 0 as np.nan_to_num, I int64 closest face, C (N,3) f64 closest point).
+    method "tree": through meshtree's bounding-volume tree: |S|, I and C the same bits, the sign from the tree-code winding number."""
+    _method(method, "signed_distance")
     v, f, _, _ = _one_mesh(vert, face)
     q = f32_dev(np.asarray(queries, np.float32).reshape(-1, 3), v.device)
-    S, I, C, _ = signed_distance_dev(q, v, f)
+    if method == "tree":
+        from . import meshtree
+        S, I, C, _ = meshtree.signed_distance_tree_dev(q, meshtree.mesh_tree_dev(v, f))
+    else:
+        S, I, C, _ = signed_distance_dev(q, v, f)
     return (np.nan_to_num(S.cpu().numpy().astype(np.float64)), I.cpu().numpy().astype(np.int64),
             C.cpu().numpy().astype(np.float64))
 
 
-def mesh2sdf(vert, face, gridDim=64, disturb=False):
+def mesh2sdf(vert, face, gridDim=64, disturb=False, method="brute"):
     """geoutil.mesh2sdf: the makeGrid([-1]*3, [1]*3, [gridDim]*3, indexing="ij") lattice (+ U[0, 1/gridDim) per coordinate from
-    numpy's global RNG when disturb) and its signed distance -> (gridDim^3, 4) f64 [x, y, z, S]."""
+    numpy's global RNG when disturb) and its signed distance -> (gridDim^3, 4) f64 [x, y, z, S].  method "tree": the route for
+    gridDim = 256 (geoutil.shape2sdf's high resolution)."""
     from .data import make_grid
+    _method(method, "mesh2sdf")
     samples = make_grid([-1, -1, -1.], [1., 1, 1], [gridDim] * 3)
     if disturb:
         samples = samples + np.random.rand(samples.shape[0], 3) / gridDim
-    S, _, _ = signed_distance(samples, vert, face)
+    S, _, _ = signed_distance(samples, vert, face, method=method)
     return np.concatenate([samples, S[:, None]], axis=-1)
 
 
