@@ -5,11 +5,17 @@
  * operator call site it replaces (file:line under shapeformer/ in the reference tree).  A reference-side
  * ctypes binding is shown in INTEGRATION.md.
  *
+ * This file is the single statement of the ABI.  Every source under shapeformer_amd/csrc/ is compiled against it (through
+ * csrc/sfmi_common.h), so a definition that differs from its declaration stops the build with `conflicting types`; the Python binding
+ * (shapeformer_amd/_lib.py) derives every restype / argtypes and the SFMI_* codes from the text below at import.  An entry point is its
+ * definition plus its declaration here, nothing else.  Keep declarations to `ret name(type name, ...);` over int, long long, size_t,
+ * float, double, unsigned, unsigned long long and pointers: the binding refuses anything it cannot map.
+ *
  * Conventions
  *   - the caller owns every buffer; nothing is allocated or freed here; scratch sizes come from *_bytes/_floats;
  *   - all pointers are DEVICE pointers unless the function is marked [host];
  *   - `stream` is a hipStream_t (passed as void*); launches are asynchronous on it, no internal sync;
- *   - returns 0 on success, a negative SFMI_E* code for bad arguments, or a positive hipError_t;
+ *   - returns 0 on success, a negative SFMI_E* code (all of them are listed below; bad arguments are SFMI_EINVAL), or a positive hipError_t;
  *   - no global mutable state (apart from the launch-shape knobs of sfmi_tune_set and immutable, once-initialised tables: the rocBLAS function pointers and one
  *     rocblas_handle per host thread, csrc/blas.hip); re-entrant for distinct streams and buffers;
  *   - layouts: feature grids are channels-last (B,D,H,W,C) f32; token buffers are int32; decode activations of the
@@ -24,8 +30,9 @@ extern "C" {
 
 #define SFMI_OK 0
 #define SFMI_EINVAL (-1)
-#define SFMI_ELDS (-4)    /* hipFuncSetAttribute refused the dynamic-LDS size a kernel needs (csrc/sgemm.hip: 73.7 KB) */
+#define SFMI_ELAUNCH (-2) /* a runtime call on the stream failed, or the finite-input pre-check could not run */
 #define SFMI_ENOBLAS (-3) /* rocBLAS could not be bound (csrc/blas.hip); callers fall back to the tile kernels */
+#define SFMI_ELDS (-4)    /* hipFuncSetAttribute refused the dynamic-LDS size a kernel needs (csrc/sgemm.hip: 73.7 KB) */
 
 int sfmi_version(void);
 /* one wavefront busy for `ticks` of the 100 MHz wall clock (<= 1 s) on `stream`: the stream-concurrency probe of the interleaved

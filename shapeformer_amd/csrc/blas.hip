@@ -12,8 +12,6 @@
 #include "sfmi_common.h"
 #include <dlfcn.h>
 
-#define SFMI_ENOBLAS (-3)
-
 namespace {
 
 typedef struct _rocblas_handle* rb_handle;

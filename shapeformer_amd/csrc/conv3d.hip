@@ -624,9 +624,6 @@ int sfmi_conv_pack_weight(const float* w, int Cout, int Cin, int KS, float* out)
 
 // replaces nn.Conv3d (+ fused input GroupNorm-apply, nearest-x2 upsample, bias, ReLU); see file header.
 // x (B,Di,Hi,Wi,Cin) -> y (B,Do,Ho,Wo,Cout), Do = ((Di<<up) + 2*pad - KS)/stride + 1.
-int sfmi_conv3d_cl_stats_f32(const float* x, const float* wT, const float* in_scale, const float* in_shift, const float* bias, float* y, int B,
-                             int Di, int Hi, int Wi, int Cin, int Cout, int KS, int stride, int pad, int up, int relu, double* partial, int* splits,
-                             void* stream);
 int sfmi_conv3d_cl_f32(const float* x, const float* wT, const float* in_scale, const float* in_shift,
                        const float* bias, float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int KS,
                        int stride, int pad, int up, int relu, void* stream) {
@@ -706,8 +703,6 @@ int sfmi_conv_pack_weight_subpixel(const float* w, int Cout, int Cin, float* out
 }
 
 // x (B,Di,Hi,Wi,Cin) low resolution -> y (B,2Di,2Hi,2Wi,Cout) = act(conv3(nearest_x2(affine(x))) + bias); 8 launches
-int sfmi_conv3d_up2_cl_stats_f32(const float* x, const float* wsub, const float* in_scale, const float* in_shift, const float* bias,
-                                 float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int relu, double* partial, int* splits, void* stream);
 int sfmi_conv3d_up2_cl_f32(const float* x, const float* wsub, const float* in_scale, const float* in_shift, const float* bias,
                            float* y, int B, int Di, int Hi, int Wi, int Cin, int Cout, int relu, void* stream) {
   return sfmi_conv3d_up2_cl_stats_f32(x, wsub, in_scale, in_shift, bias, y, B, Di, Hi, Wi, Cin, Cout, relu, nullptr, nullptr, stream);

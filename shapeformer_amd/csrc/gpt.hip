@@ -1346,7 +1346,6 @@ __global__ void set_len_kernel(int* len, const int* src, int B, int delta) {
   if (i < B) len[i] = src[i] + delta;
 }
 
-extern "C" int sfmi_decode_gemm_padded_rows(int M);
 // Host side of sfmi_decode_gemm_f32: picks the instantiation from the launch shape (and the explicit sfmi_tune_set knobs dgemm_nw /
 // dgemm_un / dgemm_nt2 - nothing is read from the environment).  Only instantiations the default rules can reach exist: UN (k16-steps
 // of loads in flight) is at most 8 / 4 / 2 / 2 / 2 / 1 for 1 .. 6 row tiles, which keeps every one of them free of scratch.
@@ -1596,16 +1595,11 @@ int sfmi_gpt_attn_decode_f32(const float* qkv_part, const float* bqkv, float* Kc
 }
 
 // causal self-attention over the conditioning prefix (positions 0..Lc[b]-2), also fills the KV caches
-int sfmi_gpt_attn_prefill_lse_f32(const float* qkv, float* Kc, float* Vc, const int* nval, float* y, int B, int P, int D, int H,
-                                  int Lmax, const int* rowoff, float drop_p, unsigned drop_seed, float* lse, void* stream);
 int sfmi_gpt_attn_prefill_f32(const float* qkv, float* Kc, float* Vc, const int* nval, float* y, int B, int P, int D, int H,
                               int Lmax, const int* rowoff, float drop_p, unsigned drop_seed, void* stream) {
   return sfmi_gpt_attn_prefill_lse_f32(qkv, Kc, Vc, nval, y, B, P, D, H, Lmax, rowoff, drop_p, drop_seed, nullptr, stream);
 }
 // the same launch; lse != NULL also receives the (B,H,P) row log-sum-exps of the scaled scores (what sfmi_attn_bwd_lse_f32 starts from)
-int sfmi_gpt_attn_prefill_lse_sd_f32(const float* qkv, float* Kc, float* Vc, const int* nval, float* y, int B, int P, int D, int H,
-                                     int Lmax, const int* rowoff, float drop_p, unsigned drop_seed, const unsigned* drop_seed_dev, float* lse,
-                                     void* stream);
 int sfmi_gpt_attn_prefill_lse_f32(const float* qkv, float* Kc, float* Vc, const int* nval, float* y, int B, int P, int D, int H,
                                   int Lmax, const int* rowoff, float drop_p, unsigned drop_seed, float* lse, void* stream) {
   return sfmi_gpt_attn_prefill_lse_sd_f32(qkv, Kc, Vc, nval, y, B, P, D, H, Lmax, rowoff, drop_p, drop_seed, nullptr, lse, stream);

@@ -297,8 +297,6 @@ int sfmi_sdf_query_f32(const float* xyz, const float* grid_cl, const float* wpac
 
 // structured Q^3 query grid (nputil.makeGrid 'ij', shapeformer.py:219-220 / vqdif.py:223-224):
 // coordinates synthesised from the Q-entry axis table -> 4 B/pt of HBM traffic.
-int sfmi_sdf_query_grid_slab_f32(const float* axis, int Q, int x0, int x1, const float* grid_cl, const float* wpack, float* out,
-                                 int B, int G, int apply_sigmoid, void* stream);
 int sfmi_sdf_query_grid_f32(const float* axis, int Q, const float* grid_cl, const float* wpack, float* out,
                             int B, int G, int apply_sigmoid, void* stream) {
   return sfmi_sdf_query_grid_slab_f32(axis, Q, 0, Q, grid_cl, wpack, out, B, G, apply_sigmoid, stream);
@@ -306,8 +304,6 @@ int sfmi_sdf_query_grid_f32(const float* axis, int Q, const float* grid_cl, cons
 // the planes x0 <= ix < x1 of the same lattice (ix is the slowest index of the 'ij' flatten, so a slab is a contiguous range of lattice
 // points): out (B, (x1 - x0) Q^2).  Every point's arithmetic is that of the whole-lattice call - the slabs of a lattice, computed by
 // different processes, concatenate to its result bit for bit (the z-slab split of ONE shape, dist.sdf_query_sharded).
-int sfmi_sdf_query_grid_aff_f32(const float* axis, int Q, int x0, int x1, const float* grid_cl, const float* aff_scale, const float* aff_shift,
-                                const float* wpack, float* out, int B, int G, int apply_sigmoid, void* stream);
 int sfmi_sdf_query_grid_slab_f32(const float* axis, int Q, int x0, int x1, const float* grid_cl, const float* wpack, float* out,
                                  int B, int G, int apply_sigmoid, void* stream) {
   return sfmi_sdf_query_grid_aff_f32(axis, Q, x0, x1, grid_cl, nullptr, nullptr, wpack, out, B, G, apply_sigmoid, stream);

@@ -2,15 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sfmi.h"   // every entry point is defined against its public declaration: a drift is `conflicting types`, at compile time
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-#define SFMI_OK 0
-#define SFMI_EINVAL (-1)
-#define SFMI_ELAUNCH (-2)
-#define SFMI_ELDS (-4)   /* the device refused the dynamic-LDS size a kernel needs */
 
 #define SFMI_CHECK_LAUNCH()                       \
   do {                                            \

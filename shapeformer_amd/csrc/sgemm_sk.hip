@@ -481,10 +481,6 @@ long long sfmi_sgemm_sk_cnt_ints(int M, int N) { return 4ll * ((M + 63) / 64) * 
 // GELU'(aux[m][n]) (aux (M,N; ldc)).  slab / cnt: caller-owned scratch (sfmi_sgemm_sk_slab_floats / _cnt_ints; cnt zeroed once), one
 // pair per stream that may run these launches concurrently.  Deterministic: a tile's slices are added in k order.
 // Replaces the cuBLAS sgemm behind nn.Linear and its autograd (mingpt.py:46-111) in the training step at small batch.
-int sfmi_sgemm_sk_sd_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, float* C2,
-                         int ldc, int accumulate, const float* bias, int act, const float* aux, const float* resid, float drop_p,
-                         unsigned drop_seed, const unsigned* drop_seed_dev, float* slab, long long slab_floats, int* cnt, long long cnt_ints,
-                         void* stream);
 int sfmi_sgemm_sk_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, float* C2,
                       int ldc, int accumulate, const float* bias, int act, const float* aux, const float* resid, float drop_p,
                       unsigned drop_seed, float* slab, long long slab_floats, int* cnt, long long cnt_ints, void* stream) {

@@ -33,6 +33,148 @@ def test_library_exports_every_declared_symbol():
     assert lib.sfmi_sdf_pack_floats() == 15876
 
 
+_SYNTHETIC_HEADER = """
+/* a block comment that quotes a call: sfmi_fake(int) must yield nothing;
+ * nor may its second line: int sfmi_fake2(void); */
+#ifndef X_H
+#define X_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define SFMI_OK 0
+#define SFMI_EINVAL (-1)   /* bad arguments */
+#define SFMI_ELAUNCH (-2)  // sfmi_fake(
+// sfmi_fake(int x);
+int sfmi_version(void);
+size_t sfmi_bytes(int B, long long n);   /* trailing comment; with a semicolon */
+long long sfmi_words(const unsigned* m,
+                     unsigned seed,
+                     unsigned long long seed64);
+int sfmi_mixed(float* const* p, void** out, const char* name, const char* const* names, const float* x, unsigned char* mask,
+               float eps,
+               double tol, const int n, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_parser_on_synthetic_text():
+    """Declarations over several lines, every pointer and scalar spelling the header uses, (void), size_t / long long returns; comments
+    and preprocessor lines yield no declaration, and #define SFMI_* integers come back as the return codes."""
+    import ctypes as C
+    from shapeformer_amd import _lib as L
+    protos, codes = L.parse_header(_SYNTHETIC_HEADER)
+    assert list(protos) == ["sfmi_version", "sfmi_bytes", "sfmi_words", "sfmi_mixed"]
+    want = {
+        "sfmi_version": (C.c_int, []),
+        "sfmi_bytes": (C.c_size_t, [C.c_int, C.c_longlong]),
+        "sfmi_words": (C.c_longlong, [C.c_void_p, C.c_uint, C.c_ulonglong]),
+        "sfmi_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double, C.c_int,
+                                 C.c_void_p]),
+    }
+    for name, (res, args) in want.items():
+        assert protos[name][0] is res, name
+        assert len(protos[name][1]) == len(args) and all(a is b for a, b in zip(protos[name][1], args)), (name, protos[name][1])
+    assert codes == {"SFMI_OK": 0, "SFMI_EINVAL": -1, "SFMI_ELAUNCH": -2}
+    # the module's own table is this parser over include/sfmi.h, and the codes it exports are the header's
+    with open(L.HEADER) as f:
+        real, rc = L.parse_header(f.read())
+    assert real == L.PROTOTYPES and sorted(real) == _declared()
+    assert (L.SFMI_OK, L.SFMI_EINVAL) == (rc["SFMI_OK"], rc["SFMI_EINVAL"]) == (0, -1)
+    assert rc == {"SFMI_OK": 0, "SFMI_EINVAL": -1, "SFMI_ELAUNCH": -2, "SFMI_ENOBLAS": -3, "SFMI_ELDS": -4}
+
+
+@pytest.mark.parametrize("decl, names", [
+    ("int sfmi_bad_param(int n, short x, void* stream);", ["sfmi_bad_param", "short x"]),
+    ("short sfmi_bad_return(int n);", ["sfmi_bad_return", "short"]),
+    ("int sfmi_unnamed(int);", ["sfmi_unnamed", "int"]),
+    ("int sfmi_uint(unsigned int n);", ["sfmi_uint", "unsigned int n"]),
+    ("int sfmi_noargs();", ["sfmi_noargs"]),
+    ("typedef int sfmi_t;", ["sfmi_t"]),
+])
+def test_header_parser_refuses_what_it_cannot_map(decl, names):
+    """An unknown parameter type, an unknown return type and anything that is not `ret name(type name, ...)` raise SfmiError naming the
+    function (and the parameter text): the parser never guesses."""
+    from shapeformer_amd import _lib as L
+    with pytest.raises(L.SfmiError) as e:
+        L.parse_header("int sfmi_fine(int a);\n" + decl)
+    for n in names:
+        assert n in str(e.value), (n, str(e.value))
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    from shapeformer_amd import _lib as L
+    monkeypatch.setattr(L, "HEADER", str(tmp_path / "nope.h"))
+    with pytest.raises(L.SfmiError, match="REQUIRED"):
+        L.load_header()
+
+
+def _hipcc_sibling(tool):
+    """`tool`, or its LLVM twin from the toolchain that built the library."""
+    import shutil
+    from shapeformer_amd import build as B
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(B._hipcc())))
+    for c in (shutil.which(tool), os.path.join(rocm, "llvm", "bin", "llvm-" + tool), os.path.join(rocm, "lib", "llvm", "bin", "llvm-" + tool)):
+        if c and os.path.exists(c):
+            return c
+    raise AssertionError(f"no {tool} / llvm-{tool} on this machine")
+
+
+def test_exports_and_declarations_agree_both_ways():
+    """The dynamic symbol table of the built library against the header: an `extern "C"` definition that the header does not declare
+    still compiles, so `every export is declared` needs its own check beside `every declaration is exported`."""
+    from shapeformer_amd import _lib as L
+    from shapeformer_amd import build as B
+    B.build(verbose=False)
+    out = subprocess.run([_hipcc_sibling("nm"), "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {w[-1].split("@")[0] for w in (ln.split() for ln in out.splitlines()) if w and w[-1].startswith("sfmi_")}
+    declared = set(L.PROTOTYPES)
+    assert len(exported) >= 243
+    assert exported - declared == set(), f"exported but not declared in include/sfmi.h: {sorted(exported - declared)}"
+    assert declared - exported == set(), f"declared but not exported: {sorted(declared - exported)}"
+
+
+def test_compiler_refuses_a_definition_that_differs_from_the_header(tmp_path):
+    """The mechanism itself: a source that includes sfmi.h cannot define an entry point with other parameter types."""
+    from shapeformer_amd import build as B
+    src = tmp_path / "drift.hip"
+    src.write_text('#include "sfmi.h"\nextern "C" int sfmi_version(int) { return 0; }\n')
+    r = subprocess.run([B._hipcc()] + B.FLAGS + ["--offload-host-only", "-I", os.path.join(ROOT, "include"), "-c", str(src),
+                        "-o", str(tmp_path / "drift.o")], capture_output=True, text=True)
+    assert r.returncode != 0 and "conflicting types" in r.stderr, r.stderr
+    src.write_text('#include "sfmi.h"\nextern "C" int sfmi_version(void) { return 0; }\n')       # the control: the true signature compiles
+    r = subprocess.run([B._hipcc()] + B.FLAGS + ["--offload-host-only", "-I", os.path.join(ROOT, "include"), "-c", str(src),
+                        "-o", str(tmp_path / "drift.o")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_every_source_reaches_the_header():
+    """Follow the #include "..." lines from each csrc/*.hip through csrc/*.h: every one arrives at sfmi.h, so every definition meets its
+    declaration.  And no source restates what the header states: no SFMI_* code, no declaration of an entry point without its body."""
+    import glob
+    csrc = os.path.join(ROOT, "shapeformer_amd", "csrc")
+
+    def reaches(path, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            if inc == "sfmi.h":
+                return True
+            nxt = os.path.join(csrc, inc)
+            if nxt not in seen and os.path.exists(nxt) and reaches(nxt, seen | {nxt}):
+                return True
+        return False
+
+    srcs = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert len(srcs) >= 31
+    assert [os.path.basename(s) for s in srcs if not reaches(s, {s})] == []
+    for path in srcs + sorted(glob.glob(os.path.join(csrc, "*.h"))):
+        text = open(path).read()
+        assert not re.search(r"#\s*define\s+SFMI_(OK|E[A-Z]+)\b", text), path
+        assert re.findall(r"\b(?:int|size_t|long long)\s+(sfmi_\w+)\s*\([^;{}]*\)\s*;", text) == [], path
+
+
 def test_host_packers_match_torch_layouts():
     """[host] packers are pure C (no GPU): fragment orders must equal the documented index formulas."""
     import ctypes
