@@ -15,7 +15,10 @@
  *   - the caller owns every buffer; nothing is allocated or freed here; scratch sizes come from *_bytes/_floats;
  *   - all pointers are DEVICE pointers unless the function is marked [host];
  *   - `stream` is a hipStream_t (passed as void*); launches are asynchronous on it, no internal sync;
- *   - returns 0 on success, a negative SFMI_E* code (all of them are listed below; bad arguments are SFMI_EINVAL), or a positive hipError_t;
+ *   - returns 0 on success, a negative SFMI_E* code (all of them are listed below), or a positive hipError_t.  Which failure gives which:
+ *     bad arguments SFMI_EINVAL, before anything is launched; a runtime call the stream refuses (a memset, a copy) SFMI_ELAUNCH; a refused
+ *     raise of a kernel's dynamic-LDS limit SFMI_ELDS; a failed kernel launch the positive hipError_t of hipGetLastError (so are a failed
+ *     stream create / destroy / synchronize and the stream-ordered allocation of sfmi_cell_max_bwd_f32);
  *   - no global mutable state (apart from the launch-shape knobs of sfmi_tune_set and immutable, once-initialised tables: the rocBLAS function pointers and one
  *     rocblas_handle per host thread, csrc/blas.hip); re-entrant for distinct streams and buffers;
  *   - layouts: feature grids are channels-last (B,D,H,W,C) f32; token buffers are int32; decode activations of the
@@ -32,7 +35,7 @@ extern "C" {
 #define SFMI_EINVAL (-1)
 #define SFMI_ELAUNCH (-2) /* a runtime call on the stream failed, or the finite-input pre-check could not run */
 #define SFMI_ENOBLAS (-3) /* rocBLAS could not be bound (csrc/blas.hip); callers fall back to the tile kernels */
-#define SFMI_ELDS (-4)    /* hipFuncSetAttribute refused the dynamic-LDS size a kernel needs (csrc/sgemm.hip: 73.7 KB) */
+#define SFMI_ELDS (-4)    /* hipFuncSetAttribute refused the dynamic-LDS size a kernel needs */
 
 int sfmi_version(void);
 /* one wavefront busy for `ticks` of the 100 MHz wall clock (<= 1 s) on `stream`: the stream-concurrency probe of the interleaved

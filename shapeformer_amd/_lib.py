@@ -65,8 +65,9 @@ def load_header():
 
 
 # name -> (restype, argtypes), and the SFMI_* return codes: read once from include/sfmi.h
-PROTOTYPES, _CODES = load_header()
-SFMI_OK, SFMI_EINVAL = _CODES["SFMI_OK"], _CODES["SFMI_EINVAL"]
+PROTOTYPES, CODES = load_header()
+SFMI_OK, SFMI_EINVAL = CODES["SFMI_OK"], CODES["SFMI_EINVAL"]
+_CODE_NAMES = {v: k for k, v in CODES.items()}
 
 
 def lib():
@@ -92,8 +93,9 @@ def lib():
 
 
 def check(rc: int, what: str):
+    """Raise on a non-zero return of an entry point, naming the code as sfmi.h does: an SFMI_E* name, or hipError_t for a positive one."""
     if rc != 0:
-        raise SfmiError(f"{what} failed with code {rc}")
+        raise SfmiError(f"{what} failed with code {rc} ({_CODE_NAMES.get(rc, 'hipError_t' if rc > 0 else 'unknown')})")
 
 
 def ptr(t):

@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsfmi.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on",
-         "-Wno-unused-result"]
+         "-Werror=unused-value"]     # a HIP runtime call whose hipError_t is dropped stops the build (SFMI_TRY, csrc/sfmi_common.h)
 
 
 def _hipcc() -> str:

@@ -224,8 +224,8 @@ int sfmi_cc_init_f32(const float* verts, const int* faces, const int* voff, cons
                      unsigned char* ref, int* flags, void* stream) {
   if (!cc_sizes(B, V, T) || !voff || !toff || !flags || (V > 0 && (!verts || !parent || !ref)) || (T > 0 && !faces)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(flags, 0, (size_t)B * 4, st);
-  if (V > 0) hipMemsetAsync(ref, 0, (size_t)V, st);
+  SFMI_TRY(hipMemsetAsync(flags, 0, (size_t)B * 4, st));
+  if (V > 0) SFMI_TRY(hipMemsetAsync(ref, 0, (size_t)V, st));
   hipLaunchKernelGGL(cc_init_kernel, dim3(blocks256((long long)V + T + B)), dim3(256), 0, st, verts, faces, voff, toff, B, V, T, parent, flags);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

@@ -539,12 +539,10 @@ static int conv_dispatch(const ConvArgs& a, void* stream) {
   if (a.stats) {      // only through the *_stats entry points, which checked conv_stats_tile first
     const int mt = conv_stats_tile(a);
     if (mt == 256) {
-      static const hipError_t at = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<2, 1, 4, false, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      if (at != hipSuccess) return SFMI_ELDS;
+      if (!SFMI_LDS_ONCE(96 * 1024, conv3d_igemm_kernel<2, 1, 4, false, true, 2, true>)) return SFMI_ELDS;
       hipLaunchKernelGGL((conv3d_igemm_kernel<2, 1, 4, false, true, 2, true>), dim3((unsigned)(M / 256)), dim3(256), lds_bytes(256, 64, true), st, a);
     } else if (mt == 512) {
-      static const hipError_t at = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<1, 1, 4, false, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      if (at != hipSuccess) return SFMI_ELDS;
+      if (!SFMI_LDS_ONCE(80 * 1024, conv3d_igemm_kernel<1, 1, 4, false, true, 4, true>)) return SFMI_ELDS;
       hipLaunchKernelGGL((conv3d_igemm_kernel<1, 1, 4, false, true, 4, true>), dim3((unsigned)(M / 512)), dim3(256), lds_bytes(512, 32, true), st, a);
     } else return SFMI_EINVAL;
     SFMI_CHECK_LAUNCH();
@@ -559,18 +557,16 @@ static int conv_dispatch(const ConvArgs& a, void* stream) {
       // the 512 workgroups the chip holds) takes in every mode
       constexpr int N_H = 64;
       dim3 grid((unsigned)(((M + M_T - 1) / M_T) * (Cout / N_H)));
-      static const hipError_t attrh = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<1, 2, 2, false, true>,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      if (xr128 && attrh == hipSuccess && lds_bytes(M_T, N_H, true) <= 80 * 1024)
+      const bool ldsh = SFMI_LDS_ONCE(80 * 1024, conv3d_igemm_kernel<1, 2, 2, false, true>);
+      if (xr128 && ldsh && lds_bytes(M_T, N_H, true) <= 80 * 1024)
         hipLaunchKernelGGL((conv3d_igemm_kernel<1, 2, 2, false, true>), grid, dim3(256), lds_bytes(M_T, N_H, true), st, a);
       else hipLaunchKernelGGL((conv3d_igemm_kernel<1, 2, 2, false>), grid, dim3(256), lds_bytes(M_T, N_H, false), st, a);
       SFMI_CHECK_LAUNCH();
       return SFMI_OK;
     }
     dim3 grid((unsigned)tiles);
-    static const hipError_t attr128 = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<2, 2, 2, false, true>,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (xr128 && attr128 == hipSuccess && lds_bytes(M_T, N_T, true) <= 80 * 1024)
+    const bool lds128 = SFMI_LDS_ONCE(80 * 1024, conv3d_igemm_kernel<2, 2, 2, false, true>);
+    if (xr128 && lds128 && lds_bytes(M_T, N_T, true) <= 80 * 1024)
       hipLaunchKernelGGL((conv3d_igemm_kernel<2, 2, 2, false, true>), grid, dim3(256), lds_bytes(M_T, N_T, true), st, a);
     else if (a.up) hipLaunchKernelGGL((conv3d_igemm_kernel<2, 2, 2, true>), grid, dim3(256), lds_bytes(M_T, N_T, false), st, a);
     else hipLaunchKernelGGL((conv3d_igemm_kernel<2, 2, 2, false>), grid, dim3(256), lds_bytes(M_T, N_T, false), st, a);
@@ -579,9 +575,8 @@ static int conv_dispatch(const ConvArgs& a, void* stream) {
     dim3 grid((unsigned)(((M + M_T - 1) / M_T) * (Cout / N_T)));
     // the framed x-rows of a narrow grid (Wo <= 2: 112 KB) do not fit the 96 KB the x-reuse instance may ask for, and the device
     // may refuse the raised limit: both fall through to the per-tap form instead of failing the call
-    static const hipError_t attr64 = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<2, 1, 4, false, true>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (xr && attr64 == hipSuccess && lds_bytes(M_T, N_T, true) <= 96 * 1024)
+    const bool lds64 = SFMI_LDS_ONCE(96 * 1024, conv3d_igemm_kernel<2, 1, 4, false, true>);
+    if (xr && lds64 && lds_bytes(M_T, N_T, true) <= 96 * 1024)
       hipLaunchKernelGGL((conv3d_igemm_kernel<2, 1, 4, false, true>), grid, dim3(256), lds_bytes(M_T, N_T, true), st, a);
     else if (a.up) hipLaunchKernelGGL((conv3d_igemm_kernel<2, 1, 4, true>), grid, dim3(256), lds_bytes(M_T, N_T, false), st, a);
     else hipLaunchKernelGGL((conv3d_igemm_kernel<2, 1, 4, false>), grid, dim3(256), lds_bytes(M_T, N_T, false), st, a);
@@ -590,18 +585,16 @@ static int conv_dispatch(const ConvArgs& a, void* stream) {
     dim3 grid((unsigned)(((M + M_T - 1) / M_T) * (Cout / N_T)));
     // 512-voxel tiles (four 32-voxel tiles per wave) where the grid is wide enough for their framed rows to fit twice per CU
     // (Wo >= 32) and there are enough of them to fill the chip; conv_xreuse 1 keeps the round-4 256-voxel tile
-    static const hipError_t attr32w = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<1, 1, 4, false, true, 4>,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (xr && g_sfmi_tune.conv_xreuse >= 2 && attr32w == hipSuccess && 512 % a.Wo == 0 && lds_bytes(512, N_T, true) <= 80 * 1024 &&
+    const bool lds32w = SFMI_LDS_ONCE(80 * 1024, conv3d_igemm_kernel<1, 1, 4, false, true, 4>);
+    if (xr && g_sfmi_tune.conv_xreuse >= 2 && lds32w && 512 % a.Wo == 0 && lds_bytes(512, N_T, true) <= 80 * 1024 &&
         ((long long)a.Do * a.Ho * a.Wo) % 512 == 0 && (M / 512) * (Cout / N_T) >= 1024) {
       dim3 gridw((unsigned)(((M + 511) / 512) * (Cout / N_T)));
       hipLaunchKernelGGL((conv3d_igemm_kernel<1, 1, 4, false, true, 4>), gridw, dim3(256), lds_bytes(512, N_T, true), st, a);
       SFMI_CHECK_LAUNCH();
       return SFMI_OK;
     }
-    static const hipError_t attr32 = hipFuncSetAttribute((const void*)conv3d_igemm_kernel<1, 1, 4, false, true>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (xr && attr32 == hipSuccess && lds_bytes(M_T, N_T, true) <= 96 * 1024)      // Wo == 1 needs 138 KB: per-tap form
+    const bool lds32 = SFMI_LDS_ONCE(96 * 1024, conv3d_igemm_kernel<1, 1, 4, false, true>);
+    if (xr && lds32 && lds_bytes(M_T, N_T, true) <= 96 * 1024)      // Wo == 1 needs 138 KB: per-tap form
       hipLaunchKernelGGL((conv3d_igemm_kernel<1, 1, 4, false, true>), grid, dim3(256), lds_bytes(M_T, N_T, true), st, a);
     else if (a.up) hipLaunchKernelGGL((conv3d_igemm_kernel<1, 1, 4, true>), grid, dim3(256), lds_bytes(M_T, N_T, false), st, a);
     else hipLaunchKernelGGL((conv3d_igemm_kernel<1, 1, 4, false>), grid, dim3(256), lds_bytes(M_T, N_T, false), st, a);

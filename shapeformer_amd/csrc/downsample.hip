@@ -411,10 +411,10 @@ int sfmi_voxel_keys_f32(const float* P, const long long* off, int B, long long N
                         int* status, void* stream) {
   if (B <= 0 || B >= VOX_MAX_SETS || N < 0 || !(voxel > 0.0) || !(voxel < INFINITY) || !off || !lo || !status) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipMemsetAsync(status, 0, sizeof(int), st);
+  SFMI_TRY(hipMemsetAsync(status, 0, sizeof(int), st));
   if (N == 0) return SFMI_OK;
   if (!P || !keys) return SFMI_EINVAL;
-  (void)hipMemsetAsync(lo, 0xFF, (size_t)B * 3 * sizeof(unsigned), st);
+  SFMI_TRY(hipMemsetAsync(lo, 0xFF, (size_t)B * 3 * sizeof(unsigned), st));
   long long S = N / ((long long)B * 16384);
   S = S < 1 ? 1 : (S > 256 ? 256 : S);
   hipLaunchKernelGGL(vox_bounds_kernel, dim3((unsigned)S, (unsigned)B), dim3(256), 0, st, P, off, lo);

@@ -434,11 +434,9 @@ int sfmi_emd_f32(const float* A, const long long* aoff, int SA, const float* B, 
   if (N > 0 && (!A || !B || !assign || !price)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   // above the 64 KB default: raised once per process; a refusal is an error the caller sees
-  static const hipError_t attr_r = hipFuncSetAttribute((const void*)emd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       EMD_RES_BYTES * EMD_N_RES);
-  static const hipError_t attr_s = hipFuncSetAttribute((const void*)emd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       EMD_STREAM_BYTES * EMD_N_MAX);
-  if (attr_r != hipSuccess || attr_s != hipSuccess) return SFMI_ELDS;
+  const bool lds_res = SFMI_LDS_ONCE(EMD_RES_BYTES * EMD_N_RES, emd_kernel<true>);
+  const bool lds_stream = SFMI_LDS_ONCE(EMD_STREAM_BYTES * EMD_N_MAX, emd_kernel<false>);
+  if (!lds_res || !lds_stream) return SFMI_ELDS;
 
   EmdArgs a;
   a.A = A; a.aoff = aoff; a.SA = SA; a.B = B; a.boff = boff; a.SB = SB; a.pa = pa; a.pb = pb; a.poff = poff;
@@ -453,15 +451,15 @@ int sfmi_emd_f32(const float* A, const long long* aoff, int SA, const float* B, 
   const long long cap = max_rounds > 0 ? (long long)max_rounds : (long long)EMD_CAP_MUL * max_n + EMD_CAP_ADD;
   const long long max_launches = cap / chunk + 2;              // a pair does `chunk` rounds per launch until it is done or capped
 
-  if (hipMemsetAsync(a.state, 0, sizeof(EmdState) * (size_t)P, st) != hipSuccess) return SFMI_ELAUNCH;
-  if (ticks && hipMemsetAsync(ticks, 0, 2 * sizeof(long long) * (size_t)P, st) != hipSuccess) return SFMI_ELAUNCH;
+  SFMI_TRY(hipMemsetAsync(a.state, 0, sizeof(EmdState) * (size_t)P, st));
+  if (ticks) SFMI_TRY(hipMemsetAsync(ticks, 0, 2 * sizeof(long long) * (size_t)P, st));
   int left = 0;
   for (long long launch = 0; launch < max_launches; ++launch) {
-    if (hipMemsetAsync(a.unfinished, 0, sizeof(int), st) != hipSuccess) return SFMI_ELAUNCH;
+    SFMI_TRY(hipMemsetAsync(a.unfinished, 0, sizeof(int), st));
     hipLaunchKernelGGL(emd_kernel<true>, dim3((unsigned)P), dim3(EMD_THREADS), lds_r, st, a);
     if (max_n > EMD_N_RES) hipLaunchKernelGGL(emd_kernel<false>, dim3((unsigned)P), dim3(EMD_THREADS), lds_s, st, a);
     SFMI_CHECK_LAUNCH();
-    if (hipMemcpyAsync(&left, a.unfinished, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return SFMI_ELAUNCH;
+    SFMI_TRY(hipMemcpyAsync(&left, a.unfinished, sizeof(int), hipMemcpyDeviceToHost, st));
     const hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return (int)e;
     if (left == 0) return SFMI_OK;

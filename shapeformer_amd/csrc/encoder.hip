@@ -757,11 +757,11 @@ static int enc_pipeline(const float* cloud, const float* wpack, float* grid_cl, 
   int* chunk_sum = (int*)w; w += (size_t)B * 64 * 4;     // (B, 64) chunk totals of the cell-count scan
   w = (char*)(((uintptr_t)w + 255) & ~(uintptr_t)255);
   float* down_wt = (float*)w;    // [8][32][64] transposed copy of the first Downsampler convolution's weights (64 KB)
-  hipMemsetAsync(start, 0, nc * 4, st);
-  hipMemsetAsync(mask, 0, (size_t)B * R * R * R, st);
+  SFMI_TRY(hipMemsetAsync(start, 0, nc * 4, st));
+  SFMI_TRY(hipMemsetAsync(mask, 0, (size_t)B * R * R * R, st));
   // per-cell sums and counts: the fused kernel writes whole rows, only the staged kernels' atomics need them zeroed (conditional fill below)
-  hipMemsetAsync(flag, 0, flag_bytes, st);
-  if (grid_cl) hipMemsetAsync(grid_cl, 0, nc * 32 * 4, st);
+  SFMI_TRY(hipMemsetAsync(flag, 0, flag_bytes, st));
+  if (grid_cl) SFMI_TRY(hipMemsetAsync(grid_cl, 0, nc * 32 * 4, st));
   int nb = (int)((bt + 255) / 256);
   // the five stages in one launch (enc_fused_kernel) unless a debug tap wants the per-stage buffers or the knob says otherwise;
   // limit < 0 makes the scan raise the flag unconditionally
@@ -775,8 +775,7 @@ static int enc_pipeline(const float* cloud, const float* wpack, float* grid_cl, 
   hipLaunchKernelGGL(enc_fill_kernel, dim3(2048), dim3(256), 0, st, (int4*)csum, (long long)((bt * 256 + cc_bytes) / 16), fused ? flag : nullptr, 0);
   if (fused) {
     constexpr size_t ef_lds = (size_t)(EF_W_FLOATS + EF_CAP * EF_ROW) * 4;   // 98.7 KB: one workgroup of eight waves per CU
-    static const hipError_t attr = hipFuncSetAttribute((const void*)enc_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ef_lds);
-    if (attr != hipSuccess) return SFMI_ELDS;
+    if (!SFMI_LDS_ONCE(ef_lds, enc_fused_kernel)) return SFMI_ELDS;
     hipLaunchKernelGGL(enc_fused_kernel, dim3((T + EF_NOM - 1) / EF_NOM, B), dim3(EF_THREADS), ef_lds, st, cloud, scell, start, cursor, order,
                        csum, ccount, wpack, flag, T);
   }
@@ -814,7 +813,7 @@ static int enc_pipeline(const float* cloud, const float* wpack, float* grid_cl, 
     hipLaunchKernelGGL(enc_down0_sparse_kernel, dim3(ENC_G / 2, B), dim3(256), 0, st, start, cursor, csum, ccount, down_wt, down_y,
                        T, down_relu);
   }
-  if (cell_out) hipMemcpyAsync(cell_out, cell, bt * 4, hipMemcpyDeviceToDevice, st);
+  if (cell_out) SFMI_TRY(hipMemcpyAsync(cell_out, cell, bt * 4, hipMemcpyDeviceToDevice, st));
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
 }

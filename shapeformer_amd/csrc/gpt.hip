@@ -15,7 +15,6 @@
 //             common.py:260-299) fused per row: radix-select top-k, bitonic sort of the candidates,
 //             top-p cut, counter-hash uniforms (no host RNG, no per-step D2H of (B,4097) logits)
 #include "sfmi_common.h"
-#include <mutex>
 #include <type_traits>
 #include <string>
 
@@ -1555,15 +1554,13 @@ static int attn_decode_launch(const float* qkv_part, float* Kc, float* Vc, const
   const int grid = g_tune.attn_blocks > 0 ? min(g_tune.attn_blocks, nitems) : nitems;
   const size_t pad = (size_t)g_tune.attn_lds_pad;
   hipStream_t st = (hipStream_t)stream;
-  static std::once_flag once;
-  static hipError_t attr_err = hipSuccess;
-  std::call_once(once, [] {   // the occupancy-cap experiments ask for more dynamic LDS than the 64 KB default
-#define AT_ATTR(W_, U_) do { hipError_t e_ = hipFuncSetAttribute((const void*)attn_decode_kernel<W_, U_, W_ != 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024); if (e_ != hipSuccess) attr_err = e_; \
-                            e_ = hipFuncSetAttribute((const void*)attn_decode_kernel<W_, U_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024); if (e_ != hipSuccess) attr_err = e_; } while (0)
-    AT_ATTR(16, 2); AT_ATTR(16, 4); AT_ATTR(16, 8); AT_ATTR(8, 2); AT_ATTR(8, 4); AT_ATTR(8, 8); AT_ATTR(4, 8); AT_ATTR(4, 16);
-#undef AT_ATTR
-  });
-  if (pad && attr_err != hipSuccess) return (int)attr_err;
+  // the occupancy-cap experiments ask for more dynamic LDS than the 64 KB default: all sixteen instances at the first launch (the
+  // decode step's warm-up, never inside a stream capture); a refusal matters only to a launch that asks for the pad
+#define AT_BOTH(W_, U_) attn_decode_kernel<W_, U_, W_ != 16>, attn_decode_kernel<W_, U_, true>
+  const bool lds_ok = SFMI_LDS_ONCE(140 * 1024, AT_BOTH(16, 2), AT_BOTH(16, 4), AT_BOTH(16, 8), AT_BOTH(8, 2), AT_BOTH(8, 4), AT_BOTH(8, 8),
+                                    AT_BOTH(4, 8), AT_BOTH(4, 16));
+#undef AT_BOTH
+  if (pad && !lds_ok) return SFMI_ELDS;
   if (sem) hipLaunchKernelGGL(attn_gate_kernel, dim3(1), dim3(64), 0, st, sem, lanes);
   // the plain instance exists for the 16-wave shapes (the product's); the 8- / 4-wave experiment shapes keep the general one (the
   // 8-wave plain instance spilled 12 bytes)

@@ -393,7 +393,7 @@ int sfmi_hpr_visible(const void* X, int is_f64, const long long* off, const doub
   hipStream_t st = (hipStream_t)stream;
   SfmiCarver carver{(char*)workspace};
   const auto [fx, fy, fz, R, orig] = hpr_ws(carver, B, N);
-  if (N > 0 && order) (void)hipMemsetAsync(visible, 0, (size_t)N, st);     // an `order` that is no permutation leaves no byte unwritten
+  if (N > 0 && order) SFMI_TRY(hipMemsetAsync(visible, 0, (size_t)N, st));     // an `order` that is no permutation leaves no byte unwritten
   const double scale = pow(10.0, param);
   const unsigned fb = (unsigned)cdiv(N, 256), vb = (unsigned)cdiv(N, HV_WAVES);
   if (is_f64) {

@@ -264,8 +264,8 @@ int sfmi_iso_seed_i32(int B, int Q0, int L, int Q, unsigned* pbits, unsigned* cb
   if (!pbits || !cbits || !iso_ok(B, Q0, L, Q) || (long long)B * Q0 * Q0 * Q0 >= (1ll << 31)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const IsoLat g = iso_lat(B, Q);
-  hipMemsetAsync(pbits, 0, (size_t)B * g.W * 4, st);
-  hipMemsetAsync(cbits, 0, (size_t)B * g.W * 4, st);
+  SFMI_TRY(hipMemsetAsync(pbits, 0, (size_t)B * g.W * 4, st));
+  SFMI_TRY(hipMemsetAsync(cbits, 0, (size_t)B * g.W * 4, st));
   hipLaunchKernelGGL(iso_seed_kernel, dim3(blocks256((long long)B * Q0 * Q0 * Q0)), dim3(256), 0, st, g, Q0, 1 << L, pbits, cbits);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;
@@ -330,8 +330,8 @@ int sfmi_iso_refine_i32(const int* cells, const int* coff, const unsigned char* 
   if (nC > 0 && (!cells || !flag)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const IsoLat g = iso_lat(B, Q);
-  hipMemsetAsync(pbits, 0, (size_t)B * g.W * 4, st);
-  hipMemsetAsync(cbits, 0, (size_t)B * g.W * 4, st);
+  SFMI_TRY(hipMemsetAsync(pbits, 0, (size_t)B * g.W * 4, st));
+  SFMI_TRY(hipMemsetAsync(cbits, 0, (size_t)B * g.W * 4, st));
   if (nC > 0)
     hipLaunchKernelGGL(iso_refine_kernel, dim3(blocks256(nC)), dim3(256), 0, st, g, cells, coff, flag, nC, 1 << (L - level), margin, pbits, cbits);
   SFMI_CHECK_LAUNCH();
@@ -344,7 +344,7 @@ int sfmi_iso_mc_count_i32(const int* cells, const int* coff, const unsigned char
   if (nP > 0 && !emask) return SFMI_EINVAL;
   if (nC > 0 && (!cells || !flag || !ntri || nP == 0)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (nP > 0) hipMemsetAsync(emask, 0, (size_t)nP * 4, st);
+  if (nP > 0) SFMI_TRY(hipMemsetAsync(emask, 0, (size_t)nP * 4, st));
   if (nC > 0)
     hipLaunchKernelGGL(iso_mc_count_kernel, dim3(blocks256(nC)), dim3(256), 0, st, iso_lat(B, Q), cells, coff, flag, nC, pbits, prank, nP, emask, ntri);
   SFMI_CHECK_LAUNCH();

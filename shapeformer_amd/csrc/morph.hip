@@ -234,7 +234,7 @@ int sfmi_voxelize_points_f32(const float* points, const int* off, int B, long lo
   if (!mv_sizes(B, G) || N < 0 || 3 * N >= (1ll << 31) || !off || !bits || (N > 0 && !points)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int Wz = mv_wz(G);
-  hipMemsetAsync(bits, 0, (size_t)B * G * G * Wz * 4, st);
+  SFMI_TRY(hipMemsetAsync(bits, 0, (size_t)B * G * G * Wz * 4, st));
   if (N > 0) hipLaunchKernelGGL(mv_voxelize_kernel, dim3(blocks256(N)), dim3(256), 0, st, points, off, B, (int)N, G, Wz, bits);
   SFMI_CHECK_LAUNCH();
   return SFMI_OK;

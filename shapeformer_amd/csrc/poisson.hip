@@ -464,8 +464,8 @@ int sfmi_poisson_keys_f32(const float* P, const float* Nrm, const long long* off
   PBox bx;
   if (!p_dims_ok(B, R) || N < 0 || N >= (1ll << 31) || !p_box(box, R, bx) || !off || !outside || !status) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipMemsetAsync(status, 0, sizeof(int), st);
-  (void)hipMemsetAsync(outside, 0, (size_t)B * sizeof(int), st);
+  SFMI_TRY(hipMemsetAsync(status, 0, sizeof(int), st));
+  SFMI_TRY(hipMemsetAsync(outside, 0, (size_t)B * sizeof(int), st));
   if (N == 0) return SFMI_OK;
   if (!P || !Nrm || !keys) return SFMI_EINVAL;
   hipLaunchKernelGGL(poisson_key_kernel, dim3(blocks256(N)), dim3(256), 0, st, P, Nrm, off, B, N, R, bx, keys, outside, status);

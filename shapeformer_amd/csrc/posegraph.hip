@@ -522,7 +522,7 @@ int sfmi_pg_information_f32(const float* src, const float* tgt, const long long*
       !pose || !maxd2 || !bad || !part || !info || !count || !flag || (N > 0 && (!src || !idx || !d2)) || (M > 0 && !tgt))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (!sfmi_pairs_finite<false>(src, tgt, nullptr, soff, toff, nullptr, B, max_n, max_m, bad, st)) return SFMI_ELAUNCH;
+  if (const int rc = sfmi_pairs_finite<false>(src, tgt, nullptr, soff, toff, nullptr, B, max_n, max_m, bad, st)) return rc;
   const int chunks = (int)(max_n > 0 ? cdiv(max_n, SFMI_CHUNK) : 1);
   if (N > 0 && M > 0)
     hipLaunchKernelGGL(pg_info_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(SFMI_CHUNK_THREADS), 0, st, tgt, soff, toff, pose,
@@ -544,8 +544,7 @@ int sfmi_pg_optimize_f64(const long long* noff, const long long* eoff, int Bg, i
   const size_t lds = (size_t)(nmax + 1) * (nmax + 2) / 2 * sizeof(double);
   // up to 137.3 KB for 32 nodes, above the 64 KB default: raised once per process; a refusal is an error the caller sees
   constexpr int lds_cap = (6 * (PG_MAX_NODES - 1) + 1) * (6 * (PG_MAX_NODES - 1) + 2) / 2 * (int)sizeof(double);
-  static const hipError_t attr = hipFuncSetAttribute((const void*)pg_optimize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);
-  if (attr != hipSuccess) return SFMI_ELDS;
+  if (!SFMI_LDS_ONCE(lds_cap, pg_optimize_kernel)) return SFMI_ELDS;
   PgArgs a;
   a.noff = noff; a.eoff = eoff; a.X = X; a.src = src; a.tgt = tgt; a.T = T; a.Lam = Lam; a.unc = uncertain; a.alive = alive; a.mu = mu;
   a.max_iter = max_iter; a.tol = tol; a.max_s = max_s; a.l = l; a.cost = cost; a.iterations = iterations; a.status = status; a.ew = ework;

@@ -296,7 +296,7 @@ int sfmi_icp_begin_f32(const float* src, const float* tgt, const float* nrm, con
       !pose || !metric || !bad || !block_off || !state || !status || !iterations || !fitness || !rmse || (N > 0 && !src) || (M > 0 && !tgt))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (!sfmi_pairs_finite<true>(src, tgt, nrm, soff, toff, metric, B, max_n, max_m, bad, st)) return SFMI_ELAUNCH;
+  if (const int rc = sfmi_pairs_finite<true>(src, tgt, nrm, soff, toff, metric, B, max_n, max_m, bad, st)) return rc;
   hipLaunchKernelGGL(icp_begin_kernel, dim3(blocks256(B)), dim3(256), 0, st, soff, pose, (const int*)bad, B, block_off, state, status,
                      iterations, fitness, rmse);
   SFMI_CHECK_LAUNCH();

@@ -664,8 +664,7 @@ int sfmi_sdf_query_grad_f32(const float* xyz, const int* poff, long long N, cons
   if (val_cap < N || grad_cap < 3 * N || (xyz_out && xyz_out_cap < 3 * N) || (normal_out && normal_cap < 3 * N)) return SFMI_EINVAL;
   if ((long long)B * G >= (1ll << 31) || ((N + 31) >> 5) >= (1ll << 31)) return SFMI_EINVAL;
   constexpr size_t lds = SDF_GRAD_PACK_FLOATS * sizeof(float);   // 125.3 KB: above the 64 KB default, one workgroup per CU
-  static const hipError_t attr = hipFuncSetAttribute((const void*)sdf_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return SFMI_ELDS;
+  if (!SFMI_LDS_ONCE(lds, sdf_grad_kernel)) return SFMI_ELDS;
   long long wgs = (((N + 31) >> 5) + 7) / 8;
   if (wgs > 256) wgs = 256;                                      // one resident workgroup per CU, persistent tile loop
   hipLaunchKernelGGL(sdf_grad_kernel, dim3((unsigned)wgs), dim3(512), lds, (hipStream_t)stream, xyz, poff, grid_cl, wpack_grad, val, grad,

@@ -14,6 +14,23 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
     if (e__ != hipSuccess) return (int)e__;       \
   } while (0)
 
+// Every other HIP runtime call of an entry point (memset, copy): a refusal is SFMI_ELAUNCH.  The build makes an unchecked one an error.
+#define SFMI_TRY(call)                             \
+  do {                                             \
+    if ((call) != hipSuccess) return SFMI_ELAUNCH; \
+  } while (0)
+
+// Dynamic LDS above the 64 KB default: raise the limit of every kernel given to `bytes`; true when the runtime agreed to all of them.
+template <class... Kernel>
+inline bool sfmi_lds_raise(int bytes, Kernel... kernel) {
+  return (... & (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess));
+}
+// The same once per process: the raise happens when control first reaches the expression (a thread-safe function-local static), every
+// later evaluation is the remembered answer.  Required: `if (!SFMI_LDS_ONCE(..)) return SFMI_ELDS;`; optional: the answer is the gate.
+// SFMI_ONCE_OK is the bare once, for a group whose instances need different sizes (several sfmi_lds_raise joined with `&`).
+#define SFMI_ONCE_OK(...) ([&]() -> bool { static const bool ok__ = (__VA_ARGS__); return ok__; }())
+#define SFMI_LDS_ONCE(bytes, ...) SFMI_ONCE_OK(sfmi_lds_raise((int)(bytes), __VA_ARGS__))
+
 // reference constants: vqdif/common.py:260-276 (padding 0.1, "10e-4" == 1e-3)
 #define SFMI_NORM_DIV 1.101f
 #define SFMI_NORM_HI 0.999f

@@ -241,16 +241,16 @@ static __global__ __launch_bounds__(SFMI_CHUNK_THREADS) void sfmi_pairs_finite_k
   if (__any(x) && (threadIdx.x & 63) == 0) atomicOr(bad + b, 1);
 }
 
-// bad[0 .. B) <- 0, then the kernel above over the largest set of the batch.  false: the memset was refused
+// bad[0 .. B) <- 0, then the kernel above over the largest set of the batch.  SFMI_ELAUNCH: the memset was refused
 template <bool NORMALS>
-inline bool sfmi_pairs_finite(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
-                              const int* metric, int B, long long max_n, long long max_m, int* bad, hipStream_t st) {
-  if (hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st) != hipSuccess) return false;
+inline int sfmi_pairs_finite(const float* src, const float* tgt, const float* nrm, const long long* soff, const long long* toff,
+                             const int* metric, int B, long long max_n, long long max_m, int* bad, hipStream_t st) {
+  SFMI_TRY(hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st));
   const long long most = max_n > max_m ? max_n : max_m;
   if (most > 0)
     hipLaunchKernelGGL(sfmi_pairs_finite_kernel<NORMALS>, dim3((unsigned)((most + SFMI_CHUNK - 1) / SFMI_CHUNK), (unsigned)B),
                        dim3(SFMI_CHUNK_THREADS), 0, st, src, tgt, nrm, soff, toff, metric, bad);
-  return true;
+  return SFMI_OK;
 }
 
 // ---- RANSAC over hypotheses (segment.hip's planes, global_register.hip's poses): integer counts, so the result is a function of the input

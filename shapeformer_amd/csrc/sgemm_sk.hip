@@ -25,7 +25,6 @@
 // the fc2 weight gradient, one launch instead of GEMM + gelu_fwd); act 3 multiplies by GELU'(aux[m][n]) (dX of fc2 -> dhpre, instead
 // of GEMM + gelu_bwd).
 #include "sfmi_common.h"
-#include <mutex>
 
 #define SK_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
@@ -452,9 +451,11 @@ __global__ __launch_bounds__(256, 2) void sgemm_sk_kernel(SkArgs a) {
   }
 }
 
-template <bool AK, bool BK, int TM, int LOOP>
-hipError_t sk_attr() {
-  return hipFuncSetAttribute((const void*)sgemm_sk_kernel<AK, BK, TM, LOOP>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * TM * SK_KS * (int)sizeof(float));
+// the three instances of one operand form, each tile shape to the dynamic LDS of its four operand tiles
+template <bool AK, bool BK>
+bool sk_lds_raise() {
+  return sfmi_lds_raise(4 * 64 * SK_KS * (int)sizeof(float), sgemm_sk_kernel<AK, BK, 1, 0>, sgemm_sk_kernel<AK, BK, 1, 1>) &
+         sfmi_lds_raise(4 * 128 * SK_KS * (int)sizeof(float), sgemm_sk_kernel<AK, BK, 2, 0>);
 }
 
 }  // namespace
@@ -508,16 +509,9 @@ int sfmi_sgemm_sk_sd_f32(int transA, int transB, int M, int N, int K, const floa
   long long G = g_sfmi_tune.sk_grid;                   // default 512: two resident workgroups per CU
   if (G > a.units) G = a.units;
   if (G * 2 * BM * BM > slab_floats) return SFMI_EINVAL;
-  static std::once_flag once;
-  static hipError_t attr_err = hipSuccess;
-  std::call_once(once, [] {
-    const hipError_t es[12] = {sk_attr<true, true, 1, 0>(), sk_attr<true, false, 1, 0>(), sk_attr<false, false, 1, 0>(), sk_attr<false, true, 1, 0>(),
-                               sk_attr<true, true, 1, 1>(), sk_attr<true, false, 1, 1>(), sk_attr<false, false, 1, 1>(), sk_attr<false, true, 1, 1>(),
-                               sk_attr<true, true, 2, 0>(), sk_attr<true, false, 2, 0>(), sk_attr<false, false, 2, 0>(), sk_attr<false, true, 2, 0>()};
-    for (hipError_t e : es)
-      if (e != hipSuccess) attr_err = e;
-  });
-  if (attr_err != hipSuccess) return SFMI_ELDS;
+  // all twelve instances at the first launch, whichever of them it takes
+  if (!SFMI_ONCE_OK(sk_lds_raise<true, true>() & sk_lds_raise<true, false>() & sk_lds_raise<false, false>() & sk_lds_raise<false, true>()))
+    return SFMI_ELDS;
   const size_t lds = (size_t)4 * BM * SK_KS * sizeof(float);
   const dim3 grid((unsigned)G), block(256);
   hipStream_t st = (hipStream_t)stream;

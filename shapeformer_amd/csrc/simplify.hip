@@ -256,8 +256,8 @@ int sfmi_simplify_cells_f32(const float* verts, const int* faces, const int* vof
   if (nW < 0 || V < 0 || T < 0 || (long long)V + T + B >= (1ll << 31) || !simp_box(lo, hi, &box, nullptr)) return SFMI_EINVAL;
   if (!voff || !toff || !grid || !woff || !bits || !flags || (V > 0 && (!verts || !vkey)) || (T > 0 && !faces)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(bits, 0, (size_t)nW * 4, st);
-  hipMemsetAsync(flags, 0, (size_t)B * 4, st);
+  SFMI_TRY(hipMemsetAsync(bits, 0, (size_t)nW * 4, st));
+  SFMI_TRY(hipMemsetAsync(flags, 0, (size_t)B * 4, st));
   hipLaunchKernelGGL(simp_cells_kernel, dim3(blocks256((long long)V + T + B)), dim3(256), 0, st, verts, faces, voff, toff, grid, woff, B, V, T, box,
                      vkey, bits, flags);
   SFMI_CHECK_LAUNCH();
@@ -288,7 +288,7 @@ int sfmi_simplify_faces_i32(const int* faces, const int* voff, const int* toff, 
   if (B <= 0 || T < 0 || 3ll * T >= (1ll << 31) || !voff || !toff || !flags || !count || (T > 0 && (!faces || !vslot || !surv)))
     return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(count, 0, (size_t)B * 4, st);
+  SFMI_TRY(hipMemsetAsync(count, 0, (size_t)B * 4, st));
   if (T > 0)
     hipLaunchKernelGGL(simp_faces_kernel, dim3(blocks256(T)), dim3(256), 0, st, faces, voff, toff, vslot, flags, B, T, cslot, surv, count);
   SFMI_CHECK_LAUNCH();

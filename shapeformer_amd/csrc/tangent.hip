@@ -318,8 +318,8 @@ int sfmi_tangent_forest_f32(const float* normal, const long long* off, const int
   const TgState s = tg_ws(carver, N);
   const long long items = N > B ? (N > TG_MAX_ROUNDS + 2 ? N : TG_MAX_ROUNDS + 2) : (B > TG_MAX_ROUNDS + 2 ? B : TG_MAX_ROUNDS + 2);
   if (N == 0) {                                                // no workspace: rounds and status alone
-    hipMemsetAsync(rounds, 0, sizeof(int) * (size_t)B, st);
-    hipMemsetAsync(status, 0, sizeof(int) * (size_t)B, st);
+    SFMI_TRY(hipMemsetAsync(rounds, 0, sizeof(int) * (size_t)B, st));
+    SFMI_TRY(hipMemsetAsync(status, 0, sizeof(int) * (size_t)B, st));
     SFMI_CHECK_LAUNCH();
     return SFMI_OK;
   }
@@ -346,7 +346,7 @@ int sfmi_tangent_apply_f32(const float* P, const float* normal, const long long*
   if (!P || !normal || !component || !parity || !votes || !out || (!viewpoint && !workspace)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(blocks256(N)), block(TG_THREADS);
-  hipMemsetAsync(votes, 0, sizeof(int) * 2 * (size_t)N, st);
+  SFMI_TRY(hipMemsetAsync(votes, 0, sizeof(int) * 2 * (size_t)N, st));
   const double* ref = viewpoint;
   if (!viewpoint) {
     SfmiCarver carver{(char*)workspace};

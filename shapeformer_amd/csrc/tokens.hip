@@ -147,7 +147,7 @@ extern "C" {
 int sfmi_mode_i32(const int* idx, long long n, int K, int rows, int* hist, int* mode_out, void* stream) {
   if (!idx || !hist || !mode_out || n <= 0 || K <= 0 || rows <= 0 || n % rows || (long long)rows * K >= (1ll << 31)) return SFMI_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipMemsetAsync(hist, 0, (size_t)K * rows * 4, st);
+  SFMI_TRY(hipMemsetAsync(hist, 0, (size_t)K * rows * 4, st));
   hipLaunchKernelGGL(hist_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, idx, hist, n, K, n / rows);
   hipLaunchKernelGGL(mode_select_kernel, dim3(rows), dim3(256), 0, st, hist, K, mode_out);
   SFMI_CHECK_LAUNCH();

@@ -22,10 +22,6 @@ from . import _lib as L
 G = 64   # encoder / decoder feature grid
 
 
-def _ck(rc, what):
-    L.check(rc, what)
-
-
 class Tape:
     def __init__(self):
         self.ops, self.grads = [], {}
@@ -95,17 +91,17 @@ class VQDIFTrainer:
 
     def _add(self, a, b):
         out = self._f(*a.shape)
-        _ck(self.lib.sfmi_add_f32(L.ptr(a), L.ptr(b), L.ptr(out), a.numel(), L.stream_ptr()), "add")
+        L.check(self.lib.sfmi_add_f32(L.ptr(a), L.ptr(b), L.ptr(out), a.numel(), L.stream_ptr()), "add")
         return out
 
     def _gemm(self, x, W, bias, resid, M, N, K, act=0):
         y = self._f(M, N)
-        _ck(self.lib.sfmi_gemm_f32(L.ptr(x), L.ptr(W), L.ptr(bias), L.ptr(resid), L.ptr(y), M, N, K, act, 0, 0, L.stream_ptr()), "gemm")
+        L.check(self.lib.sfmi_gemm_f32(L.ptr(x), L.ptr(W), L.ptr(bias), L.ptr(resid), L.ptr(y), M, N, K, act, 0, 0, L.stream_ptr()), "gemm")
         return y
 
     def _relu(self, x):
         y = self._f(*x.shape)       # relu(x) == relu_bwd(dy = x, y = x)
-        _ck(self.lib.sfmi_relu_bwd_f32(L.ptr(x), L.ptr(x), L.ptr(y), x.numel(), L.stream_ptr()), "relu")
+        L.check(self.lib.sfmi_relu_bwd_f32(L.ptr(x), L.ptr(x), L.ptr(y), x.numel(), L.stream_ptr()), "relu")
         self._tap_relu(y)
         return y
 
@@ -117,15 +113,15 @@ class VQDIFTrainer:
 
     def _relu_bwd(self, dy, y):
         dx = self._f(*dy.shape)
-        _ck(self.lib.sfmi_relu_bwd_f32(L.ptr(dy), L.ptr(y), L.ptr(dx), dy.numel(), L.stream_ptr()), "relu_bwd")
+        L.check(self.lib.sfmi_relu_bwd_f32(L.ptr(dy), L.ptr(y), L.ptr(dx), dy.numel(), L.stream_ptr()), "relu_bwd")
         return dx
 
     def _colsum_into(self, x, M, N, gname):
         if M >= 256:
             ws = self._f(self.lib.sfmi_colsum_slices(M, N) * N)
-            _ck(self.lib.sfmi_colsum_ws_f32(L.ptr(x), L.ptr(self.g[gname]), M, N, N, 0, L.ptr(ws), L.stream_ptr()), "colsum_ws")
+            L.check(self.lib.sfmi_colsum_ws_f32(L.ptr(x), L.ptr(self.g[gname]), M, N, N, 0, L.ptr(ws), L.stream_ptr()), "colsum_ws")
         else:
-            _ck(self.lib.sfmi_colsum_f32(L.ptr(x), L.ptr(self.g[gname]), M, N, N, 0, L.stream_ptr()), "colsum")
+            L.check(self.lib.sfmi_colsum_f32(L.ptr(x), L.ptr(self.g[gname]), M, N, N, 0, L.stream_ptr()), "colsum")
 
     def _wgrad_into(self, dy, x, gname, B, Di, Hi, Wi, Cin, Cout, KS, stride, pad, ldy=None, ldx=None, rows=None):
         """dW[tap][co][ci] of a channels-last conv (KS == 1: a Linear over `Wi` rows) -> self.g[gname] (first Cin cols)."""
@@ -134,11 +130,11 @@ class VQDIFTrainer:
         tiles = -(-Cout // 64) * -(-Cin // 64) * KS ** 3
         nsplit = max(1, min(512, -(-1024 // tiles), rows // 256))
         part = self._f(nsplit, KS ** 3 * Cout * Cin)
-        _ck(self.lib.sfmi_conv3d_wgrad_f32(L.ptr(dy), L.ptr(x), L.ptr(part), B, Di, Hi, Wi, Cin, Cout, KS, stride, pad,
+        L.check(self.lib.sfmi_conv3d_wgrad_f32(L.ptr(dy), L.ptr(x), L.ptr(part), B, Di, Hi, Wi, Cin, Cout, KS, stride, pad,
                                            ldy or Cout, ldx or Cin, nsplit, L.stream_ptr()), "wgrad")
         g = self.g[gname]
         assert g.numel() == KS ** 3 * Cout * Cin, (gname, g.shape, Cout, Cin)
-        _ck(self.lib.sfmi_colsum_f32(L.ptr(part), L.ptr(g), nsplit, g.numel(), g.numel(), 0, L.stream_ptr()), "colsum")
+        L.check(self.lib.sfmi_colsum_f32(L.ptr(part), L.ptr(g), nsplit, g.numel(), g.numel(), 0, L.stream_ptr()), "colsum")
 
     # ------------------------------------------------------------------------------------------------ taped ops
     def linear(self, x, wname, bname=None, act=0, resid=None, need_dx=True):
@@ -181,7 +177,7 @@ class VQDIFTrainer:
         w = self.p[wname]
         Do = (Di + 2 * pad - KS) // stride + 1
         y = self._f(B, Do, Do, Do, Cout)
-        _ck(self.lib.sfmi_conv3d_cl_f32(L.ptr(x), L.ptr(w), None, None, L.ptr(self.p[bias]) if bias else None, L.ptr(y), B, Di, Di, Di,
+        L.check(self.lib.sfmi_conv3d_cl_f32(L.ptr(x), L.ptr(w), None, None, L.ptr(self.p[bias]) if bias else None, L.ptr(y), B, Di, Di, Di,
                                         Cin, Cout, KS, stride, pad, 0, int(relu), L.stream_ptr()), "conv")
         if relu:
             self._tap_relu(y)
@@ -197,11 +193,11 @@ class VQDIFTrainer:
             dx = self._f(B, Di, Di, Di, Cin)
             if KS == 3:      # stride 1, pad 1: correlation with the tap-flipped, channel-transposed kernel
                 wd = w.flip(0).transpose(1, 2).contiguous()
-                _ck(self.lib.sfmi_conv3d_cl_f32(L.ptr(dy), L.ptr(wd), None, None, None, L.ptr(dx), B, Do, Do, Do, Cout, Cin, 3, 1, 1, 0, 0,
+                L.check(self.lib.sfmi_conv3d_cl_f32(L.ptr(dy), L.ptr(wd), None, None, None, L.ptr(dx), B, Do, Do, Do, Cout, Cin, 3, 1, 1, 0, 0,
                                                 L.stream_ptr()), "conv dgrad")
             elif KS == 1:
                 wd = w[0].t().contiguous()
-                _ck(self.lib.sfmi_gemm_f32(L.ptr(dy), L.ptr(wd), None, None, L.ptr(dx), B * Do ** 3, Cin, Cout, 0, 0, 0, L.stream_ptr()), "1x1 dgrad")
+                L.check(self.lib.sfmi_gemm_f32(L.ptr(dy), L.ptr(wd), None, None, L.ptr(dx), B * Do ** 3, Cin, Cout, 0, 0, 0, L.stream_ptr()), "1x1 dgrad")
             else:            # k2 s2: every input voxel belongs to exactly one (output voxel, tap)
                 dxv = dx.view(B, Do, 2, Do, 2, Do, 2, Cin)
                 for t in range(8):
@@ -218,10 +214,10 @@ class VQDIFTrainer:
         gamma, beta = self.p[gname], self.p[bname]
         scale, shift = self._f(B, C), self._f(B, C)
         part = torch.empty(B, S, C, 2, device=self.dev, dtype=torch.float64)
-        _ck(lib.sfmi_groupnorm_coeffs_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(part), B, V, C, self.ng,
+        L.check(lib.sfmi_groupnorm_coeffs_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(part), B, V, C, self.ng,
                                           1e-5, L.stream_ptr()), "gn coeffs")
         y = self._f(*x.shape)
-        _ck(lib.sfmi_affine_cl_f32(L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(y), B, V, C, L.stream_ptr()), "affine")
+        L.check(lib.sfmi_affine_cl_f32(L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(y), B, V, C, L.stream_ptr()), "affine")
 
         def bwd(dy):
             cg = C // self.ng
@@ -231,7 +227,7 @@ class VQDIFTrainer:
             var = sx[..., 1].view(B, self.ng, cg).sum(-1) / n - mu * mu
             rstd = 1.0 / torch.sqrt(var.clamp_min(0) + 1e-5)
             pd = torch.empty(B, S, C, 2, device=self.dev, dtype=torch.float64)
-            _ck(lib.sfmi_chan_dot_stats_f32(L.ptr(dy), L.ptr(x), L.ptr(pd), B, V, C, S, L.stream_ptr()), "chan_dot_stats")
+            L.check(lib.sfmi_chan_dot_stats_f32(L.ptr(dy), L.ptr(x), L.ptr(pd), B, V, C, S, L.stream_ptr()), "chan_dot_stats")
             sd = pd.sum(1)
             s1, s2 = sd[..., 0], sd[..., 1]                                    # (B,C): sum dy, sum dy*x
             gm = gamma.double()
@@ -245,14 +241,14 @@ class VQDIFTrainer:
             self.g[gname].copy_(xh.sum(0).float())
             self.g[bname].copy_(s1.sum(0).float())
             dx = self._f(*x.shape)
-            _ck(lib.sfmi_affine2_cl_f32(L.ptr(dy), L.ptr(x), L.ptr(A), L.ptr(Bc), L.ptr(Cc), L.ptr(dx), B, V, C, L.stream_ptr()), "affine2")
+            L.check(lib.sfmi_affine2_cl_f32(L.ptr(dy), L.ptr(x), L.ptr(A), L.ptr(Bc), L.ptr(Cc), L.ptr(dx), B, V, C, L.stream_ptr()), "affine2")
             return [dx]
         self.tape.add(y, [x], bwd)
         return y
 
     def maxpool(self, x, B, Do, C):
         y = self._f(B, Do, Do, Do, C)
-        _ck(self.lib.sfmi_maxpool2_cl_f32(L.ptr(x), L.ptr(y), B, Do, Do, Do, C, L.stream_ptr()), "maxpool")
+        L.check(self.lib.sfmi_maxpool2_cl_f32(L.ptr(x), L.ptr(y), B, Do, Do, Do, C, L.stream_ptr()), "maxpool")
         if getattr(self, "pool_tap", None) is not None:   # debug tap: the selected window element (first maximum, 4 dz + 2 dy + dx)
             win = x.view(B, Do, 2, Do, 2, Do, 2, C).permute(0, 1, 3, 5, 7, 2, 4, 6).reshape(B, Do, Do, Do, C, 8)
             first = (win == y.unsqueeze(-1)).int() * torch.arange(8, 0, -1, device=self.dev, dtype=torch.int32)
@@ -260,7 +256,7 @@ class VQDIFTrainer:
 
         def bwd(dy):
             dx = self._f(*x.shape)
-            _ck(self.lib.sfmi_maxpool2_bwd_cl_f32(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(dx), B, Do, Do, Do, C, L.stream_ptr()), "maxpool bwd")
+            L.check(self.lib.sfmi_maxpool2_bwd_cl_f32(L.ptr(x), L.ptr(y), L.ptr(dy), L.ptr(dx), B, Do, Do, Do, C, L.stream_ptr()), "maxpool bwd")
             return [dx]
         self.tape.add(y, [x], bwd)
         return y
@@ -269,13 +265,13 @@ class VQDIFTrainer:
         """cat(skip, nearest_x2(low)) on channels (unet3d.py:268-293); Cs == 0: plain nearest x2 (updown.py:121)."""
         y = self._f(B, D, D, D, Cs + Cu)
         if Cs:
-            _ck(self.lib.sfmi_upcat_cl_f32(L.ptr(skip), L.ptr(low), L.ptr(y), B, D, D, D, Cs, Cu, L.stream_ptr()), "upcat")
+            L.check(self.lib.sfmi_upcat_cl_f32(L.ptr(skip), L.ptr(low), L.ptr(y), B, D, D, D, Cs, Cu, L.stream_ptr()), "upcat")
         else:
-            _ck(self.lib.sfmi_upsample2_cl_f32(L.ptr(low), L.ptr(y), B, D // 2, D // 2, D // 2, Cu, L.stream_ptr()), "upsample2")
+            L.check(self.lib.sfmi_upsample2_cl_f32(L.ptr(low), L.ptr(y), B, D // 2, D // 2, D // 2, Cu, L.stream_ptr()), "upsample2")
 
         def bwd(dy):
             dlow = self._f(B, D // 2, D // 2, D // 2, Cu)
-            _ck(self.lib.sfmi_sumpool2_cl_f32(L.ptr(dy), L.ptr(dlow), B, D // 2, D // 2, D // 2, Cs + Cu, Cs, Cu, L.stream_ptr()), "sumpool2")
+            L.check(self.lib.sfmi_sumpool2_cl_f32(L.ptr(dy), L.ptr(dlow), B, D // 2, D // 2, D // 2, Cs + Cu, Cs, Cu, L.stream_ptr()), "sumpool2")
             return [dy[..., :Cs].contiguous() if Cs else None, dlow]
         self.tape.add(y, [skip, low], bwd)
         return y
@@ -286,7 +282,7 @@ class VQDIFTrainer:
         M, ncell = B * T, G ** 3
         cell = torch.empty(B, T, device=self.dev, dtype=torch.int32)
         ph = self._f(M, 3)
-        _ck(lib.sfmi_cells_f32(L.ptr(Xbd), L.ptr(cell), L.ptr(ph), B, T, G, L.stream_ptr()), "cells")
+        L.check(lib.sfmi_cells_f32(L.ptr(Xbd), L.ptr(cell), L.ptr(ph), B, T, G, L.stream_ptr()), "cells")
         p16 = torch.zeros(M, 16, device=self.dev)
         p16[:, :3] = ph
         net = self.linear(p16, "encoder.fc_pos.weight", "encoder.fc_pos.bias", need_dx=False)            # (M,64)
@@ -296,15 +292,15 @@ class VQDIFTrainer:
             keys.view(torch.uint8).fill_(0x80)
             cat = self._f(M, 64)
             cat[:, :32] = net
-            _ck(lib.sfmi_cell_max_f32(L.ptr(net), L.ptr(cell), L.ptr(keys), L.ptr(cat), B, T, ncell, 32, 64, 32, L.stream_ptr()), "cell_max")
+            L.check(lib.sfmi_cell_max_f32(L.ptr(net), L.ptr(cell), L.ptr(keys), L.ptr(cat), B, T, ncell, 32, 64, 32, L.stream_ptr()), "cell_max")
 
             def bwd(dcat, net=net, keys=keys):
                 # left half: identity; right half: pooled -> scatter to cells, route to the one arg-max point of each (cell, channel)
                 acc = torch.zeros(B, ncell, 32, device=self.dev, dtype=torch.int64)
-                _ck(lib.sfmi_cell_scatter_add_f32(L.ptr(dcat), L.ptr(cell), L.ptr(acc), None, B, T, ncell, 32, 64, 32, L.stream_ptr()), "cell_scatter")
+                L.check(lib.sfmi_cell_scatter_add_f32(L.ptr(dcat), L.ptr(cell), L.ptr(acc), None, B, T, ncell, 32, 64, 32, L.stream_ptr()), "cell_scatter")
                 dnet = dcat[:, :32].contiguous()
                 win = torch.empty(B, ncell, 32, device=self.dev, dtype=torch.int32)     # transient: the arg-max point of every (cell, channel)
-                _ck(lib.sfmi_cell_max_bwd_ws_f32(L.ptr(net), L.ptr(keys), L.ptr(acc), L.ptr(cell), L.ptr(win), L.ptr(dnet), B, T, ncell, 32, 32, 1,
+                L.check(lib.sfmi_cell_max_bwd_ws_f32(L.ptr(net), L.ptr(keys), L.ptr(acc), L.ptr(cell), L.ptr(win), L.ptr(dnet), B, T, ncell, 32, 32, 1,
                                               L.stream_ptr()), "cell_max_bwd")
                 return [dnet]
             self.tape.add(cat, [net], bwd)
@@ -312,13 +308,13 @@ class VQDIFTrainer:
         c = self.linear(net, "encoder.fc_c.weight", "encoder.fc_c.bias")                                   # (M,32)
         acc = torch.zeros(B, ncell, 32, device=self.dev, dtype=torch.int64)
         cnt = torch.zeros(B, ncell, device=self.dev, dtype=torch.int32)
-        _ck(lib.sfmi_cell_scatter_add_f32(L.ptr(c), L.ptr(cell), L.ptr(acc), L.ptr(cnt), B, T, ncell, 32, 32, 0, L.stream_ptr()), "cell_scatter")
+        L.check(lib.sfmi_cell_scatter_add_f32(L.ptr(c), L.ptr(cell), L.ptr(acc), L.ptr(cnt), B, T, ncell, 32, 32, 0, L.stream_ptr()), "cell_scatter")
         grid = self._f(B, G, G, G, 32)
-        _ck(lib.sfmi_cell_mean_f32(L.ptr(acc), L.ptr(cnt), L.ptr(grid), B, ncell, 32, L.stream_ptr()), "cell_mean")
+        L.check(lib.sfmi_cell_mean_f32(L.ptr(acc), L.ptr(cnt), L.ptr(grid), B, ncell, 32, L.stream_ptr()), "cell_mean")
 
         def bwd_mean(dgrid):
             dc = self._f(M, 32)
-            _ck(lib.sfmi_cell_mean_bwd_f32(L.ptr(dgrid), L.ptr(cnt), L.ptr(cell), L.ptr(dc), B, T, ncell, 32, L.stream_ptr()), "cell_mean_bwd")
+            L.check(lib.sfmi_cell_mean_bwd_f32(L.ptr(dgrid), L.ptr(cnt), L.ptr(cell), L.ptr(dc), B, T, ncell, 32, L.stream_ptr()), "cell_mean_bwd")
             return [dc]
         self.tape.add(grid, [c], bwd_mean)
         # Downsampler (updown.py:101-118): steps x [conv k2 s2 -> ReLU -> GN ; conv 1x1 -> ReLU -> GN], channels double
@@ -340,17 +336,17 @@ class VQDIFTrainer:
         W = self.emb
         pk = torch.cat([W.view(self.K // 32, 32, d // 8, 2, 4).permute(0, 2, 3, 1, 4).reshape(-1), (W * W).sum(1)]).contiguous()
         idx = torch.empty(rows, device=self.dev, dtype=torch.int32)
-        _ck(lib.sfmi_vq_argmin_f32(L.ptr(latent), L.ptr(pk), L.ptr(idx), None, rows, self.K, d, L.stream_ptr()), "vq_argmin")
+        L.check(lib.sfmi_vq_argmin_f32(L.ptr(latent), L.ptr(pk), L.ptr(idx), None, rows, self.K, d, L.stream_ptr()), "vq_argmin")
         q = self._f(*latent.shape)
-        _ck(lib.sfmi_vq_gather_f32(L.ptr(W), L.ptr(idx), L.ptr(q), rows, d, L.stream_ptr()), "vq_gather")
+        L.check(lib.sfmi_vq_gather_f32(L.ptr(W), L.ptr(idx), L.ptr(q), rows, d, L.stream_ptr()), "vq_gather")
         diffv = self._f(latent.numel())
-        _ck(lib.sfmi_lincomb_f32(1.0, L.ptr(latent), -1.0, L.ptr(q), L.ptr(diffv), latent.numel(), L.stream_ptr()), "x - q")
+        L.check(lib.sfmi_lincomb_f32(1.0, L.ptr(latent), -1.0, L.ptr(q), L.ptr(diffv), latent.numel(), L.stream_ptr()), "x - q")
         diff = (diffv.double() ** 2).mean()                               # scalar for the loss value (logging)
         cscale = 2.0 * self.beta / latent.numel()
 
         def bwd(dq):   # d loss / d latent = straight-through + beta * d mean((x - q)^2) / dx
             dl = self._f(*latent.shape)
-            _ck(lib.sfmi_lincomb_f32(1.0, L.ptr(dq), cscale, L.ptr(diffv), L.ptr(dl), latent.numel(), L.stream_ptr()), "st + commit")
+            L.check(lib.sfmi_lincomb_f32(1.0, L.ptr(dq), cscale, L.ptr(diffv), L.ptr(dl), latent.numel(), L.stream_ptr()), "st + commit")
             return [dl]
         self.tape.add(q, [latent], bwd)
         return q, idx, diff
@@ -388,13 +384,13 @@ class VQDIFTrainer:
         lib, B, N = self.lib, Xtg.shape[0], Xtg.shape[1]
         M = B * N
         c = self._f(M, 32)
-        _ck(lib.sfmi_trilinear_cl_f32(L.ptr(Xtg), L.ptr(grid), L.ptr(c), B, N, G, 32, L.stream_ptr()), "trilinear")
+        L.check(lib.sfmi_trilinear_cl_f32(L.ptr(Xtg), L.ptr(grid), L.ptr(c), B, N, G, 32, L.stream_ptr()), "trilinear")
 
         def bwd(dc):
             acc = torch.zeros(B, G ** 3, 32, device=self.dev, dtype=torch.int64)
-            _ck(lib.sfmi_trilinear_bwd_cl_f32(L.ptr(Xtg), L.ptr(dc), L.ptr(acc), B, N, G, 32, L.stream_ptr()), "trilinear bwd")
+            L.check(lib.sfmi_trilinear_bwd_cl_f32(L.ptr(Xtg), L.ptr(dc), L.ptr(acc), B, N, G, 32, L.stream_ptr()), "trilinear bwd")
             dgrid = self._f(B, G, G, G, 32)
-            _ck(lib.sfmi_fixed_to_float_f32(L.ptr(acc), L.ptr(dgrid), acc.numel(), 0, L.stream_ptr()), "fixed_to_float")
+            L.check(lib.sfmi_fixed_to_float_f32(L.ptr(acc), L.ptr(dgrid), acc.numel(), 0, L.stream_ptr()), "fixed_to_float")
             return [dgrid]
         self.tape.add(c, [grid], bwd)
         p16 = torch.zeros(M, 16, device=self.dev)
@@ -417,7 +413,7 @@ class VQDIFTrainer:
             dY = torch.zeros(M, 32, device=self.dev)
             dY[:, 0] = dlog
             gw = self._f(1, 32 * 32)
-            _ck(lib.sfmi_conv3d_wgrad_f32(L.ptr(dY), L.ptr(a), L.ptr(gw), 1, 1, 1, M, 32, 32, 1, 1, 0, 32, 32, 1, L.stream_ptr()), "wgrad fc_out")
+            L.check(lib.sfmi_conv3d_wgrad_f32(L.ptr(dY), L.ptr(a), L.ptr(gw), 1, 1, 1, M, 32, 32, 1, 1, 0, 32, 32, 1, L.stream_ptr()), "wgrad fc_out")
             self.g["decoder.fc_out.weight"].copy_(gw.view(32, 32)[0:1])
             self.g["decoder.fc_out.bias"].copy_(dlog.sum().view(1))
             return [self._gemm(dY, Wp.t().contiguous(), None, None, M, 32, 32)]
@@ -441,7 +437,7 @@ class VQDIFTrainer:
         logits = self._sdf_head(self._decoder_grid(q, B), Xtg)
         n = logits.numel()
         rows, dlog = self._f(n), self._f(n)
-        _ck(lib.sfmi_bce_logits_f32(L.ptr(logits), L.ptr(Ytg), L.ptr(rows), L.ptr(dlog), n, 1.0 / n, L.stream_ptr()), "bce")
+        L.check(lib.sfmi_bce_logits_f32(L.ptr(logits), L.ptr(Ytg), L.ptr(rows), L.ptr(dlog), n, 1.0 / n, L.stream_ptr()), "bce")
         recon = rows.double().mean()
         self.tape.backward(logits, dlog, self._add)
         return dict(loss=(recon + self.beta * diff).float(), recon_loss=recon.float(), diff_loss=diff.float(), logits=logits)
@@ -454,14 +450,14 @@ class VQDIFTrainer:
         rows = latent.numel() // self.d
         sums = torch.zeros(self.K, self.d, device=self.dev, dtype=torch.int64)
         cnts = torch.zeros(self.K, device=self.dev, dtype=torch.int32)
-        _ck(lib.sfmi_vq_stats_f32(L.ptr(latent), L.ptr(idx), L.ptr(sums), L.ptr(cnts), rows, self.d, L.stream_ptr()), "vq_stats")
+        L.check(lib.sfmi_vq_stats_f32(L.ptr(latent), L.ptr(idx), L.ptr(sums), L.ptr(cnts), rows, self.d, L.stream_ptr()), "vq_stats")
         sf = self._f(self.K, self.d)
-        _ck(lib.sfmi_fixed_to_float_f32(L.ptr(sums), L.ptr(sf), sums.numel(), 0, L.stream_ptr()), "fixed_to_float")
+        L.check(lib.sfmi_fixed_to_float_f32(L.ptr(sums), L.ptr(sf), sums.numel(), 0, L.stream_ptr()), "fixed_to_float")
         cf = cnts.float()
         if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
             self.dist.all_reduce(sf)
             self.dist.all_reduce(cf)
-        _ck(lib.sfmi_vq_ema_update_f32(L.ptr(self.N), L.ptr(self.z_avg), L.ptr(self.emb), L.ptr(cf), L.ptr(sf), self.K, self.d, self.gamma, 1e-7,
+        L.check(lib.sfmi_vq_ema_update_f32(L.ptr(self.N), L.ptr(self.z_avg), L.ptr(self.emb), L.ptr(cf), L.ptr(sf), self.K, self.d, self.gamma, 1e-7,
                                        L.stream_ptr()), "vq_ema")
 
     @torch.no_grad()
@@ -470,7 +466,7 @@ class VQDIFTrainer:
         from .dist import allreduce_mean_
         allreduce_mean_(self.flat_g, self.dist)
         self.step_count += 1
-        _ck(self.lib.sfmi_adamw_f32(L.ptr(self.flat_p), L.ptr(self.flat_g), L.ptr(self.flat_m), L.ptr(self.flat_v), self.flat_p.numel(),
+        L.check(self.lib.sfmi_adamw_f32(L.ptr(self.flat_p), L.ptr(self.flat_g), L.ptr(self.flat_m), L.ptr(self.flat_v), self.flat_p.numel(),
                                     self.lr, 0.9, 0.999, 1e-8, 0.0, self.step_count, L.stream_ptr()), "adam")
 
     def training_step(self, batch):

@@ -151,6 +151,101 @@ def test_compiler_refuses_a_definition_that_differs_from_the_header(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def _hipcc_host(tmp_path, name, text, *more):
+    """Compile `text` as the library's sources are compiled (build.FLAGS, the same include paths), host side only."""
+    from shapeformer_amd import build as B
+    src = tmp_path / (name + ".hip")
+    src.write_text(text)
+    return subprocess.run([B._hipcc()] + B.FLAGS + ["--offload-host-only", "-I", os.path.join(ROOT, "include"), "-I", B.CSRC, str(src)]
+                          + list(more), capture_output=True, text=True)
+
+
+def test_sfmi_try_returns_elaunch_for_a_refused_call(tmp_path):
+    """SFMI_TRY in a stand-alone host program (no runtime call is made): hipSuccess passes through to the statements after it, any other
+    hipError_t leaves the enclosing function with SFMI_ELAUNCH."""
+    exe = tmp_path / "try"
+    r = _hipcc_host(tmp_path, "try", '#include "sfmi_common.h"\n'
+                    "static int f(hipError_t e) { SFMI_TRY(e); return SFMI_OK; }\n"
+                    "int main() { return (f(hipSuccess) == SFMI_OK ? 0 : 1) + (f(hipErrorInvalidValue) == SFMI_ELAUNCH ? 0 : 2); }\n",
+                    "-o", str(exe))
+    assert r.returncode == 0, r.stderr
+    assert subprocess.run([str(exe)], timeout=60).returncode == 0
+
+
+def test_compiler_refuses_an_unchecked_runtime_call(tmp_path):
+    """The mechanism that keeps the rule: under build.FLAGS a runtime call whose hipError_t is dropped does not compile, the SFMI_TRY
+    form does, and no flag switches a warning category off."""
+    from shapeformer_amd import build as B
+    body = '#include "sfmi_common.h"\nextern "C" int sfmi_version(void) { %s; return SFMI_OK; }\n'
+    r = _hipcc_host(tmp_path, "bare", body % "hipMemsetAsync(nullptr, 0, 4, nullptr)", "-c", "-o", str(tmp_path / "bare.o"))
+    assert r.returncode != 0 and "nodiscard" in r.stderr, r.stderr
+    r = _hipcc_host(tmp_path, "tried", body % "SFMI_TRY(hipMemsetAsync(nullptr, 0, 4, nullptr))", "-c", "-o", str(tmp_path / "tried.o"))
+    assert r.returncode == 0, r.stderr
+    assert [f for f in B.FLAGS if f.startswith("-Wno-")] == []
+
+
+def test_runtime_calls_have_one_spelling():
+    """No source silences a runtime call's result with a cast, and the dynamic-LDS limit is raised in one place (sfmi_lds_raise)."""
+    import glob
+    csrc = os.path.join(ROOT, "shapeformer_amd", "csrc")
+    paths = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(paths) >= 33
+    texts = {os.path.basename(p): open(p).read() for p in paths}
+    assert [n for n, t in texts.items() if "(void)hip" in t] == []
+    assert [n for n, t in texts.items() if "hipFuncSetAttribute" in t] == ["sfmi_common.h"]
+
+
+def test_check_names_the_code():
+    from shapeformer_amd import _lib as L
+    assert L.CODES == {"SFMI_OK": 0, "SFMI_EINVAL": -1, "SFMI_ELAUNCH": -2, "SFMI_ENOBLAS": -3, "SFMI_ELDS": -4}
+    assert L.check(0, "x") is None
+    with pytest.raises(L.SfmiError, match=r"x failed with code -2 \(SFMI_ELAUNCH\)"):
+        L.check(-2, "x")
+    with pytest.raises(L.SfmiError, match=r"x failed with code -4 \(SFMI_ELDS\)"):
+        L.check(-4, "x")
+    with pytest.raises(L.SfmiError, match=r"x failed with code 98 \(hipError_t\)"):
+        L.check(98, "x")
+
+
+_REFUSED = r"""
+import ctypes, sys, numpy as np
+sys.path.insert(0, %r)
+from shapeformer_amd import _lib as L
+lib = ctypes.CDLL(L.LIB_PATH)
+def fn(name):
+    f = getattr(lib, name)
+    f.restype, f.argtypes = L.PROTOTYPES[name]
+    return f
+p = lambda a: a.ctypes.data
+B, G = 1, 4
+off, bits = np.zeros(B + 1, np.int32), np.zeros(B * G * G * 1, np.uint32)                   # G = 4: one word per z column
+rc = [fn("sfmi_voxelize_points_f32")(None, p(off), B, 0, G, p(bits), None)]
+Q0, Lv, Q = 2, 1, 3                                                                         # 27 lattice points: one word per bit set
+pbits, cbits = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+rc.append(fn("sfmi_iso_seed_i32")(1, Q0, Lv, Q, p(pbits), p(cbits), None))
+idx, hist, mode = np.zeros(8, np.int32), np.zeros(2 * 5, np.int32), np.zeros(2, np.int32)   # n = 8, K = 5, rows = 2
+rc.append(fn("sfmi_mode_i32")(p(idx), 8, 5, 2, p(hist), p(mode), None))
+x, y = np.zeros(8, np.float32), np.zeros(8, np.float32)
+rc.append(fn("sfmi_sigmoid_f32")(p(x), p(y), 8, None))
+print("RC", *rc, flush=True)
+"""
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="with a device present the runtime accepts these calls: host buffers would be wrong arguments")
+def test_refused_memset_is_reported():
+    """Without a device every runtime call is refused (hipErrorNoDevice), cleanly.  An entry point whose first runtime call is a memset
+    returns SFMI_ELAUNCH for it instead of launching on and returning the launch's error; one that only launches keeps the positive
+    hipError_t.  Host buffers of the stated sizes, a fresh process."""
+    from shapeformer_amd import _lib as L
+    from shapeformer_amd import build as B
+    B.build(verbose=False)
+    out = subprocess.run([sys.executable, "-c", _REFUSED % ROOT], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    rc = [int(v) for v in re.search(r"^RC (.*)$", out.stdout, re.M).group(1).split()]
+    assert rc[:3] == [L.CODES["SFMI_ELAUNCH"]] * 3, rc
+    assert rc[3] > 0, rc
+
+
 def test_every_source_reaches_the_header():
     """Follow the #include "..." lines from each csrc/*.hip through csrc/*.h: every one arrives at sfmi.h, so every definition meets its
     declaration.  And no source restates what the header states: no SFMI_* code, no declaration of an entry point without its body."""
