@@ -170,7 +170,12 @@ int sfmi_gpt_attn_prefill_lse_f32(const float* qkv, float* Kc, float* Vc, const 
 /* plain f32 GEMM on the matrix cores (csrc/sgemm.hip): row-major C (M,N;ldc) = op(A) op(B) (+C) (+bias[n]) -> act -> (+resid).
  * transA == 0: A stored (M,K;lda), else (K,M;lda); transB != 0: B stored (N,K;ldb) (nn.Linear weight), else (K,N;ldb).
  * Replaces the sgemm behind nn.Linear and its autograd (mingpt.py:46-111) in the prefill and the training step.
- * ws (optional, >= splits*M*N floats): split-K scratch for outputs with too few tiles (weight gradients), summed in slice order */
+ * ws (optional, >= splits*M*N floats): split-K scratch for outputs with too few tiles (weight gradients), summed in slice order;
+ * a ws of fewer floats halves the slice count until it fits (1 slice: ws unused).
+ * Accepted (else SFMI_EINVAL, nothing launched): A, B, C non-NULL; M, N, K > 0; N a multiple of 4; K a multiple of 4 unless
+ * (transA && !transB); M a multiple of 4 when transA; lda, ldb, ldc multiples of 4 and not shorter than the row they stride
+ * (lda >= K, or M when transA; ldb >= N, or K when transB; ldc >= N); act 0 none / 1 ReLU / 2 GELU-erf; ws_floats >= 0;
+ * 0 <= drop_p < 1. */
 int sfmi_sgemm_mfma_splits(int M, int N, int K);
 int sfmi_sgemm_mfma_f32(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                         int ldc, int accumulate, const float* bias, int act, const float* resid, float* ws, long long ws_floats,
@@ -180,7 +185,11 @@ int sfmi_sgemm_mfma_f32(int transA, int transB, int M, int N, int K, const float
  * tiles cut between workgroups are finished in the same launch (write-through slabs + tickets, slices added in k order:
  * deterministic).  act: 0 none, 1 ReLU, 2 GELU(erf) (C2 != NULL also receives the pre-activation), 3 multiply by GELU'(aux[m][n]).
  * slab (>= sfmi_sgemm_sk_slab_floats() floats) / cnt (>= sfmi_sgemm_sk_cnt_ints(M, N) ints, zeroed ONCE): caller-owned scratch,
- * one pair per stream that runs these launches concurrently.  Replaces nn.Linear and its autograd, mingpt.py:46-111 */
+ * one pair per stream that runs these launches concurrently.  Replaces nn.Linear and its autograd, mingpt.py:46-111.
+ * Accepted (else SFMI_EINVAL, nothing launched): the shape, alignment and stride rules of sfmi_sgemm_mfma_f32 (lda, ldb, ldc not
+ * shorter than the row they stride); slab, cnt non-NULL; act 0 .. 3, aux non-NULL when act == 3; 0 <= drop_p < 1;
+ * cnt_ints >= 4 x the tiles of the chosen tile shape; slab_floats >= G * 2 * BM * BM for G = min(`sk_grid`, tiles x K-chunks)
+ * workgroups of BM x BM tiles (sfmi_sgemm_sk_slab_floats() covers every product and grid). */
 int sfmi_sgemm_sk_tile(int M, int N, int K);          /* [host] 2 = 128 x 128 workgroup tiles, 1 = 64 x 64 */
 long long sfmi_sgemm_sk_slab_floats(void);            /* [host] */
 long long sfmi_sgemm_sk_cnt_ints(int M, int N);       /* [host] */

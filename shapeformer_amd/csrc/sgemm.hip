@@ -264,7 +264,8 @@ int sfmi_sgemm_mfma_f32(int transA, int transB, int M, int N, int K, const float
   if (!transA && K % 4) return SFMI_EINVAL;          // A K-contiguous: float4 along k
   if (transA && (M % 4 || M < 4)) return SFMI_EINVAL; // A row-contiguous: float4 along m
   if (transB && K % 4) return SFMI_EINVAL;
-  if (N < 4) return SFMI_EINVAL;
+  if (N < 4 || act < 0 || act > 2 || ws_floats < 0) return SFMI_EINVAL;
+  if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N) return SFMI_EINVAL;   // a stride shorter than the row it strides
   SgemmArgs a;
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.resid = resid; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.accumulate = accumulate; a.act = act; a.ws = ws; a.drop_p = drop_p; a.drop_seed = drop_seed;

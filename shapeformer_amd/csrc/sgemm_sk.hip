@@ -498,6 +498,7 @@ int sfmi_sgemm_sk_sd_f32(int transA, int transB, int M, int N, int K, const floa
   if (transA && (M % 4 || M < 4)) return SFMI_EINVAL; // A row-contiguous: float4 along m
   if (transB && K % 4) return SFMI_EINVAL;
   if (N < 4 || act < 0 || act > 3 || (act == 3 && !aux) || drop_p < 0.f || drop_p >= 1.f) return SFMI_EINVAL;
+  if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N) return SFMI_EINVAL;   // a stride shorter than the row it strides
   const int TM = sfmi_sgemm_sk_tile(M, N, K), BM = 64 * TM;
   SkArgs a;
   a.A = A; a.B = B; a.C = C; a.C2 = C2; a.bias = bias; a.aux = aux; a.resid = resid; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb;
