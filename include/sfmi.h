@@ -859,6 +859,60 @@ int sfmi_morph_flood_u32(const unsigned* in, int B, int G, unsigned* region, int
 int sfmi_morph_pack_u8(const unsigned char* vox, int B, int G, unsigned* bits, void* stream);
 int sfmi_morph_unpack_u8(const unsigned* bits, int B, int G, unsigned char* vox, void* stream);
 
+/* ---- Smooth fields from binary voxel grids (csrc/edt.hip): the exact Euclidean distance transform, the signed
+ *      distance, a separable Gaussian filter and a constrained smoothing solve in a narrow band.  xgutils/geoutil.py:194-197: array2mesh
+ *      with gaussian_sigma passes the grid through mcubes.smooth before marching cubes.  The contract below is this library's own,
+ *      modelled on PyMCubes' smooth_gaussian / smooth_constrained (Lempitsky, Surface extraction from binary volumes with higher-order
+ *      smoothness, CVPR 2010); parity with PyMCubes' numbers is not claimed.  Its numpy / scipy statement is tests/voxfield_ref.py.
+ * CONTRACT
+ *   Grid      the bit sets of the section above, unchanged: (B, G, G, Wz) uint32, Wz = ceil(G / 32), voxel [i][j][k] is bit k % 32; pad
+ *             bits are ignored.  B * G^3 < 2^31, 1 <= G <= sfmi_vox_max_grid() (513).  sfmi_morph_pack_u8 makes them from uint8 grids.
+ *   EDT       d2 (B,G,G,G) int32: d2[v] = min |u - v|^2 in integers over the voxels u of the same grid whose bit is set (invert = 1:
+ *             clear); a voxel of the set gets 0.  With invert = 1 this is scipy.ndimage.distance_transform_edt(grid)**2.  A grid whose
+ *             set is empty gets d2 = 3 G^2 everywhere (larger than any distance inside the lattice, and finite) and status = 1, else
+ *             status = 0; status is (B) int32.  Three separable passes: along k the nearest set bit of the row by count-leading /
+ *             count-trailing-zero scans of its words, along j and then i the integer lower envelope min_j' (g[j'] + (j - j')^2).
+ *   Signed    d (B,G,G,G) f64, positive inside: a set voxel gets sqrt((double) d2_to_clear) - 0.5, a clear one -sqrt((double)
+ *             d2_to_set) + 0.5, sqrt correctly rounded.  status = 1 for a grid that is all set or all clear; its d follows from the
+ *             3 G^2 rule.
+ *   Gaussian  out (B,G,G,G) f64 = scipy.ndimage.gaussian_filter(f64(bit) - 0.5, sigma, mode="reflect"), truncate = 4.0: the host
+ *             computes radius = int(4 sigma + 0.5) and the 2 radius + 1 normalised f64 weights as scipy does and hands them over as a
+ *             device array (no kernel calls exp).  Three line passes over axes 0, 1, 2 in that order; each output is w[0] x[l], then
+ *             += (x[l - t] + x[l + t]) w[t] for t = radius down to 1, every operation rounded to f64 on its own.  Reflect:
+ *             (d c b a | a b c d | d c b a), repeated for a radius greater than G.  0 <= radius <= sfmi_vox_gaussian_max_radius() (64).
+ *   Solve     band = |d| <= band_radius (f64 compare).  lo = 0, hi = +inf on set voxels, lo = -inf, hi = 0 on clear ones.
+ *             L u (v) = (((((u[i+1] + u[i-1]) + u[j+1]) + u[j-1]) + u[k+1]) + u[k-1]) - 6.0 * u[v] with indices clamped to the lattice
+ *             (edge replication: the symmetric Neumann Laplacian), every operation rounded to f64 on its own, in this order.
+ *             u_0 = d; then iters times: g = L(L u); on the band x = u - g / 84.0 and u <- (x > hi ? hi : x), then (u < lo ? lo : u),
+ *             i.e. max(lo, min(hi, x)) with a -0.0 left as it is; off the band u stays d.  1/84 is the 0.5-weighted Jacobi step on the
+ *             interior diagonal 42 of L^2, whose largest eigenvalue is at most 144 < 2 * 84: a projected gradient step, under which
+ *             E(u) = 1/2 sum (L u)^2 cannot increase.  Jacobi form: every update of an iteration reads the previous iterate only.
+ *             The band voxels and the support of L u (the band and the voxels one clamped step from it) are compacted once, in
+ *             ascending flat index by prefix counts; an iteration is two launches over those lists.  No early exit, nothing read back:
+ *             u is a function of (bits, d, band_radius, iters).
+ *   Determinism  integer and f64 arithmetic in a fixed order, no atomics: bit-identical from run to run and between a batch and
+ *             per-grid calls.  The number of launches does not depend on the grid's content.
+ * Every entry returns SFMI_EINVAL before any launch for a NULL pointer it would use, B <= 0, G outside [1, 513], B * G^3 >= 2^31,
+ * iters < 0, a non-finite or negative band_radius, radius outside [0, 64], or u == d.  Workspaces are caller-owned; their sizes are 0
+ * for sizes the entries refuse. */
+int sfmi_vox_max_grid(void);
+int sfmi_vox_gaussian_max_radius(void);
+/* is_signed = 0: sfmi_edt_sq_u32 (one int32 lattice and the envelope's two uint16 stacks per line); 1: sfmi_edt_signed_f64 (two more) */
+size_t sfmi_edt_workspace_bytes(int B, int G, int is_signed);
+int sfmi_edt_sq_u32(const unsigned* bits, int B, int G, int invert, int* d2, int* status, void* ws, void* stream);
+int sfmi_edt_signed_f64(const unsigned* bits, int B, int G, double* d, int* status, void* ws, void* stream);
+size_t sfmi_vox_gaussian_workspace_bytes(int B, int G);
+/* weights (2 radius + 1) f64 [device] */
+int sfmi_vox_gaussian_f64(const unsigned* bits, int B, int G, const double* weights, int radius, double* out, void* ws, void* stream);
+/* L u dense, the two lists at their largest, a flag byte per voxel and the chunk counts */
+size_t sfmi_vox_constrained_workspace_bytes(int B, int G);
+/* d: the signed distance above (any f64 field is taken as given).  u (B,G,G,G) f64 */
+int sfmi_vox_constrained_f64(const unsigned* bits, const double* d, int B, int G, double band_radius, int iters, double* u, void* ws,
+                             void* stream);
+/* the lists that the last sfmi_vox_constrained_f64 on ws left, for tests: band / support (B G^3) int32 flat voxel indices, ascending, of
+ * which the first counts[0] / counts[1] are meaningful; counts (2) int32 */
+int sfmi_vox_constrained_lists_i32(const void* ws, int B, int G, int* band, int* support, int* counts, void* stream);
+
 /* ---- Exact k-nearest neighbours, outlier statistics and normals of raw scans (csrc/knn.hip).
  *      xgutils/geoutil.py:362-366 (points_dist: scipy cKDTree(p2).query(p1, k) for any k); the real-scan datasets that need a cleaning
  *      front end: shapeformer/data/imnet_datasets/redwood.py:17-104 (Redwood, Redwood2), realtest.py:17-111 (RealTest_dataset,

@@ -1,8 +1,9 @@
 """Iso-surface extraction on the GPU — host side of csrc/mcubes.hip.
 
-`array2mesh` mirrors xgutils/geoutil.py:175-233 for dim == 3 (no gaussian filter, cart_coord=True): marching cubes at `thresh`,
-vertices mapped onto the bounding box of the query coordinates, then, with `if_decimate`, decimation to `decimate_face` faces on the
-device (simplify.decimate_dev: quadric vertex clustering - the reference's face budget, not igl.decimate's output).  The reference calls
+`array2mesh` mirrors xgutils/geoutil.py:175-233 for dim == 3 (cart_coord=True): marching cubes at `thresh`, vertices mapped onto the
+bounding box of the query coordinates, then, with `if_decimate`, decimation to `decimate_face` faces on the device
+(simplify.decimate_dev: quadric vertex clustering - the reference's face budget, not igl.decimate's output).  With `gaussian_sigma` /
+`smooth` the grid is binarised and smoothed on the device first (voxfield.py, DESIGN 5.24: geoutil.py:194-197).  The reference calls
 PyMCubes on the CPU after copying the 128^3 occupancy to the host; here the grid never leaves HBM and the result is an
 indexed mesh (shared vertices), in a deterministic order.  There is no CPU fallback.
 """
@@ -40,13 +41,32 @@ def marching_cubes_dev(occ: torch.Tensor, thresh: float = 0.5, bbox=((-1.0, -1.0
     return verts[:int(voff[-1])], faces[:int(toff[-1])], voff, toff
 
 
+def _smooth_choice(gaussian_sigma=None, smooth=None):
+    """array2mesh's two smoothing keywords -> None (off) or (method, keyword arguments of voxfield.smooth_dev).  smooth names the method;
+    gaussian_sigma is the sigma of "gaussian"; a non-None gaussian_sigma with smooth=None selects "constrained", as in the reference,
+    where any non-None value just calls mcubes.smooth (geoutil.py:194-197)."""
+    if smooth is None:
+        return None if gaussian_sigma is None else ("constrained", {})
+    if smooth not in ("constrained", "gaussian"):
+        raise L.SfmiError(f"array2mesh: smooth = {smooth!r} must be None, 'constrained' or 'gaussian'")
+    if smooth == "gaussian" and gaussian_sigma is not None:
+        return smooth, {"sigma": gaussian_sigma}
+    return smooth, {}
+
+
 def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), device="cuda:0", if_decimate=False,
-               decimate_face=4096, keep_components=None):
-    """geoutil.array2mesh(array, thresh, dim=3, coords=..., if_decimate=..., decimate_face=...) for ONE flattened or cubic grid ->
-    (verts (V,3) float64, faces (T,3) int) numpy, like the reference returns (`verts*(bbmax-bbmin)+bbmin`, faces.astype(int)).
+               decimate_face=4096, keep_components=None, gaussian_sigma=None, smooth=None):
+    """geoutil.array2mesh(array, thresh, dim=3, coords=..., if_decimate=..., decimate_face=..., gaussian_sigma=...) for ONE flattened or
+    cubic grid -> (verts (V,3) float64, faces (T,3) int) numpy, like the reference returns (`verts*(bbmax-bbmin)+bbmin`,
+    faces.astype(int)).
     if_decimate: a mesh with more than `decimate_face` faces is decimated on the device, over the same box, before the copy.
     keep_components: "largest", an int k, a float in (0, 1] or a dict of components.keep_components_dev's keyword arguments: the mesh's
-    connected components are filtered on the device before the decimation; None: off."""
+    connected components are filtered on the device before the decimation; None: off.
+    gaussian_sigma / smooth (_smooth_choice above; both None: off, the mesh of the grid as it is): the grid is binarised at `> thresh`,
+    smoothed on the device (voxfield.smooth_dev: "constrained" or "gaussian" with sigma = gaussian_sigma, default 3) and marched at level
+    0.  The one deviation from the reference, which binarises at `> 0` and marches the smoothed field at `thresh`: there, an occupancy
+    grid in [0, 1] becomes all set but for its exact zeros, and a level of 0.5 lies off the smoothed surface."""
+    choice = _smooth_choice(gaussian_sigma, smooth)
     a = torch.as_tensor(occupancy, dtype=torch.float32)
     if a.dim() != 3:
         Q = round(a.numel() ** (1.0 / 3))
@@ -55,7 +75,11 @@ def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.
     if coords is not None:
         c = np.asarray(coords).reshape(-1, 3)
         bbox = (c.min(0), c.max(0))                # nputil.arrayBBox
-    v, f, voff, toff = marching_cubes_dev(a[None].to(device), thresh, bbox)
+    if choice is None:
+        v, f, voff, toff = marching_cubes_dev(a[None].to(device), thresh, bbox)
+    else:
+        from .voxfield import voxels2mesh_dev
+        v, f, voff, toff = voxels2mesh_dev((a > thresh).to(torch.uint8)[None].to(device), choice[0], bbox, **choice[1])
     if keep_components is not None:
         from .components import keep_components_dev, parse_keep
         v, f, voff, toff = keep_components_dev(v, f, voff, toff, **parse_keep(keep_components))[:4]
