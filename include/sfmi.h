@@ -1281,6 +1281,80 @@ int sfmi_emd_f32(const float* A, const long long* aoff, int SA, const float* B, 
                  double* emd, int* rounds, int* status, double* eps_final, double* price, long long* ticks, void* workspace,
                  void* stream);
 
+/* ---- Edge-collapse mesh decimation to an exact face budget (csrc/collapse.hip).  The reference's
+ *      array2mesh(..., if_decimate=True) is igl.decimate, an edge collapse (xgutils/geoutil.py:175-233); the clustering of the section
+ *      "Mesh decimation" above keeps its interface only.  This is the edge collapse, in rounds of independent collapses, stated as a
+ *      pure function of (verts, faces, target, reg) and restated in plain Python in tests/collapse_ref.py; the claim is bit equality.
+ * CONTRACT
+ *   Input     the ragged batch of the decimation section: verts (V,3) f32, faces (T,3) int32 local per shape, voff / toff (B+1) int32
+ *             [device]; a face budget target >= 0; reg > 0 (default 1e-3); a round cap max_rounds.
+ *   Status    per shape: 1 / 2 / 3 as in the decimation section (such a shape comes back empty); else 0 done (F <= target), 4 stalled
+ *             (a round without a winner), 5 the round cap was reached.  A shape runs rounds while F > target and rounds < max_rounds;
+ *             a round counts when it collapses an edge.  At status 0, target - 1 <= F <= target (shapeformer_amd/collapse.py returns a
+ *             shape with T_b <= target unchanged and uninspected).
+ *   Round     on the alive faces F of the shape:
+ *   Edges     the distinct undirected edges (lo, hi) of the faces without a repeated index, ascending, each with its face count.  A
+ *             vertex is frozen if it lies on an edge whose count is not 2 or on a face with a repeated index (such faces are carried
+ *             through untouched and have no edges).  An edge is a candidate iff its count is 2 and neither end is frozen.
+ *   Quadrics  per vertex (a00 a01 a02 a11 a12 a22, b0 b1 b2, c) in f64, absolute coordinates: once, the sum over its faces without a
+ *             repeated index in ascending face index, one after the other, of n n^T, d n, d d with n = (p1 - p0) x (p2 - p0), d =
+ *             -((n0 p0x + n1 p0y) + n2 p0z); when v collapses into u, Q_u = Q_u + Q_v entry by entry.
+ *   Position  of a candidate (u, v), u < v: Q = Q_u + Q_v, m = (p_u + p_v) / 2, tr = a00 + a11 + a22; tr > 0: x solves (A + reg tr I) x =
+ *             reg tr m - b by the Cholesky of csrc/sfmi_quadric.h, and a pivot that is not positive refuses the edge; else x = m.  A
+ *             non-finite x refuses the edge.  x32 = f32(x).
+ *   Cost      with x = x32 widened: t_r = (a_r0 x0 + a_r1 x1) + a_r2 x2; cost = (((x0 t0 + x1 t1) + x2 t2) + 2 ((b0 x0 + b1 x1) + b2 x2))
+ *             + c; not finite: refused; cost = max(cost, 0).
+ *   Validity  the region of (u, v) is every alive face with a corner at u or v; its survivors are those not holding both.  (a) u and v
+ *             have exactly two common neighbours; (b) with v renamed u no two survivors have the same three vertices; (c) every
+ *             survivor, with its corner at u or v moved to x32, has n_old . n_new = (o0 n0 + o1 n1) + o2 n2 > 0 (normals as above, from
+ *             the f32 positions widened, corner order kept).
+ *   Key       (bits of f32(cost)) << 32 | rank, rank = the edge's place in the ascending edge table (batch-wide: only keys of one shape
+ *             are ever compared).  A strict total order.
+ *   Winners   every valid candidate puts the 64-bit minimum of its key on each face of its region; it wins iff every face of its
+ *             region holds its key.  Two winners' regions are disjoint, so a round's collapses touch no common face, vertex or quadric
+ *             and commute.  allowed = (F - target + 1) / 2: the first `allowed` winners in ascending key order collapse.
+ *   Apply     u stays, at x32; v becomes u in v's faces; the two faces holding both die; Q_u += Q_v.
+ *   Output    the vertices no collapse removed, in input order (at their last positions); the alive faces in input order, corner order
+ *             kept, re-indexed; compaction by the prefix counts of sfmi_cc_emit_f32.
+ *   Determinism  integer atomics only; all floating-point work is f64 in this order inside one thread, compiled without contraction:
+ *             bit-identical from run to run, a batch equals per-shape calls, and neither depends on the rounds run per read-back.
+ * The state of a call lives in `workspace` (sfmi_collapse_workspace_bytes(B, V, T) bytes, 0 for sizes the calls refuse: B < 1, or the
+ * batch does not fit 32-bit indices); the arrays the host sorts between the passes are arguments.  n = 3T below.  One round is
+ * records, [sort ekey -> skey, sidx; stable sort of ckey -> corder, cseg (V+1)], runs, [erank = cumsum(ecnt > 0) - 1], eval, win, [sort
+ * wkey, then stably by wshape -> order, sshape, sstart], apply.  Every entry returns SFMI_EINVAL before any launch for a NULL pointer or
+ * refused sizes. */
+size_t sfmi_collapse_workspace_bytes(int B, int V, int T);
+/* validates the batch and sets the state up: positions, batch-wide faces, alive flags, per-shape status / counts / budget */
+int sfmi_collapse_init_f32(const float* verts, const int* faces, const int* voff, const int* toff, int B, int V, int T, int target,
+                           int max_rounds, void* workspace, void* stream);
+/* clears the round's frozen flags and face keys; ekey (n) int64 half-edge keys lo << 32 | hi, ckey (n) the corner's vertex; INT64_MAX / V
+ * for the records of a face that is dead, of a shape that has stopped, or has a repeated index */
+int sfmi_collapse_records_i32(int B, int V, int T, long long* ekey, int* ckey, void* workspace, void* stream);
+/* ecnt (n): the length of the run of equal keys that starts at sorted record i, 0 where none starts; freezes the ends of a count != 2 */
+int sfmi_collapse_runs_i32(const long long* skey, int B, int V, int T, int* ecnt, void* workspace, void* stream);
+/* the vertex quadrics from the current faces and positions (called once, after the first records / sort) */
+int sfmi_collapse_quadrics_f64(const int* corder, const int* cseg, int B, int V, int T, void* workspace, void* stream);
+/* cand (n) uint64: the key of every valid candidate at its sorted record, all ones elsewhere; xs (n,3) f32 its x32; marks the regions */
+int sfmi_collapse_eval_f64(const long long* skey, const int* ecnt, const int* erank, const int* corder, const int* cseg, int B, int V, int T,
+                           double reg, unsigned long long* cand, float* xs, void* workspace, void* stream);
+/* wkey (n) int64: a winner's key, INT64_MAX elsewhere; wshape (n): its shape, B elsewhere; counts the winners per shape */
+int sfmi_collapse_win_i32(const long long* skey, const long long* sidx, const unsigned long long* cand, const int* corder, const int* cseg,
+                          int B, int V, int T, long long* wkey, int* wshape, void* workspace, void* stream);
+/* order (n) int64: sorted records by (wshape, wkey); sshape (n): wshape in that order; sstart (B): the first place of each shape.  Applies
+ * the first `allowed` of each shape, then updates every shape's alive count, rounds, status and budget */
+int sfmi_collapse_apply_f32(const long long* skey, const long long* order, const int* sshape, const int* sstart, const float* xs,
+                            const int* corder, const int* cseg, int B, int V, int T, int target, int max_rounds, void* workspace,
+                            void* stream);
+/* copies of the per-shape state (each (B) int32 [device] or NULL) and of the number of shapes that go on (1 int32 [device] or NULL) */
+int sfmi_collapse_report_i32(int B, int V, int T, const void* workspace, int* status, int* rounds, int* nalive, int* nactive, void* stream);
+/* out_v (V,3) the current positions, out_f (T,3) the current faces local per shape, vkeep (V) / fkeep (T) uint8: what the output keeps */
+int sfmi_collapse_finish_f32(const int* voff, int B, int V, int T, const void* workspace, float* out_v, int* out_f, unsigned char* vkeep,
+                             unsigned char* fkeep, void* stream);
+/* the edge table on its own, after init (target 0) / records / sort / runs: ref (V) uint8 = a face names the vertex; counts (3,B) int32 =
+ * edges, boundary edges (count 1), non-manifold edges (count > 2) per shape */
+int sfmi_collapse_topology_i32(const long long* skey, const long long* sidx, const int* ecnt, int B, int V, int T, const void* workspace,
+                               unsigned char* ref, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

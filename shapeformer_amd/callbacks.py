@@ -19,6 +19,7 @@ import torch
 
 from . import meshio, ops, tokens as T
 from .dist import effective_indices
+from .mcubes import _decimate_choice
 
 
 def filter_end_tokens(indices, end_tokens):
@@ -99,12 +100,21 @@ def _np(d):
     return d.detach().cpu().numpy() if isinstance(d, torch.Tensor) else d
 
 
+def _decimate(method, v, f, voff, toff, decimate_face):
+    """the callbacks' decimation step -> verts, faces, voff, toff, ... by `decimate_method`"""
+    if method == "collapse":
+        from .collapse import decimate_collapse_dev
+        return decimate_collapse_dev(v, f, voff, toff, decimate_face)
+    from .simplify import decimate_dev
+    return decimate_dev(v, f, voff, toff, decimate_face)
+
+
 class VisSparseRecon3D(VisCallback):
     """vqdif.py:217-310: quantize -> sparse tokens -> dense -> decode on the `decoder_resolution`^3 lattice -> mesh."""
 
     def __init__(self, samples=32, Xct_as_Xbd=False, quant_grid_depth=4, decoder_resolution=128, vocab_size=4096,
                  max_length=512, end_tokens=(4096, 4096), resolution=(512, 512), vis_Ytg=True, thresh=0.5, decimate_face=None,
-                 refine_steps=0, vertex_normals=False, keep_components=None, **kw):
+                 refine_steps=0, vertex_normals=False, keep_components=None, decimate_method="cluster", **kw):
         super().__init__(**kw)
         # keep_components: drop the floaters of the extracted mesh on the device (components.keep_components_dev, DESIGN 5.12) after the
         # refinement and before everything else, so that eval_pc, the fewer-than-10-vertices rule, the decimation and the PLY see the
@@ -120,8 +130,9 @@ class VisSparseRecon3D(VisCallback):
         # unchanged (compute_batch then stores no `dense` code grid either)
         self.refine_steps, self.vertex_normals = int(refine_steps), bool(vertex_normals)
         # decimate_face: the mesh that is written and returned is decimated to that many faces on the device before the copy to the
-        # host (simplify.decimate_dev); eval_pc keeps sampling the undecimated mesh.  None: off, unchanged
-        self.decimate_face = decimate_face
+        # host (simplify.decimate_dev); eval_pc keeps sampling the undecimated mesh.  None: off, unchanged.
+        # decimate_method: "cluster" (that, the default) or "collapse" (collapse.decimate_collapse_dev, DESIGN 5.25: edge collapse)
+        self.decimate_face, self.decimate_method = decimate_face, _decimate_choice(decimate_method)
         self.Xct_as_Xbd, self.quant_grid_depth, self.decoder_resolution = Xct_as_Xbd, quant_grid_depth, decoder_resolution
         self.vocab_size, self.max_length, self.end_tokens, self.thresh = vocab_size, max_length, tuple(end_tokens), thresh
 
@@ -171,8 +182,7 @@ class VisSparseRecon3D(VisCallback):
         vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
         full = (vert, face)                                                                # what eval_pc samples
         if self.decimate_face is not None:
-            from .simplify import decimate_dev
-            v, f, voff = decimate_dev(v, f, voff, toff, self.decimate_face)[:3]
+            v, f, voff = _decimate(self.decimate_method, v, f, voff, toff, self.decimate_face)[:3]
             vert, face = v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
         normal = None
         if self.vertex_normals and len(vert) >= 10:                                        # (write_mesh replaces smaller results by a dummy)
@@ -200,7 +210,7 @@ class VisShapeFormer(VisCallback):
                  force_keep_c_indices=False, sort_prob=True, partial_radius=0.02, camPos=(2, 2, 2), resolution=(512, 512),
                  thresh=0.5, keep_logits_history=False, seed=0, shard_sample_n=None, eval_metrics=False, eval_tau=0.01,
                  eval_points=10 ** 5, sparse_decode=False, sparse_coarse=33, sparse_margin=1, decimate_face=None, refine_steps=0,
-                 vertex_normals=False, keep_components=None, clean_context=None, **kw):
+                 vertex_normals=False, keep_components=None, clean_context=None, decimate_method="cluster", **kw):
         super().__init__(**kw)
         # clean_context: a dict of scan.clean_cloud_dev keyword arguments (k, std_ratio, seed, voxel, resample, remove_planes, keep_cluster): compute_batch removes the
         # statistical outliers of Xct on the device before encode_cloud, resampled back to Xct's point count, and records the kept
@@ -219,8 +229,9 @@ class VisShapeFormer(VisCallback):
         self.refine_steps, self.vertex_normals = int(refine_steps), bool(vertex_normals)
         # decimate_face: the meshes that are written to meshes/*.ply and returned are decimated to that many faces on the device before
         # the copy to the host (simplify.decimate_dev), on the dense and the sparse_decode route alike; eval_pc, recon_<i>
-        # and eval_metrics keep sampling the undecimated meshes (the reference's vis_ind evaluates with if_decimate=False).  None: off
-        self.decimate_face = decimate_face
+        # and eval_metrics keep sampling the undecimated meshes (the reference's vis_ind evaluates with if_decimate=False).  None: off.
+        # decimate_method: as VisSparseRecon3D's
+        self.decimate_face, self.decimate_method = decimate_face, _decimate_choice(decimate_method)
         # sparse_decode: visualize_batch meshes through VQDIF.decode_index_mesh (coarse-to-fine) at decode_res =
         # (sparse_coarse-1) 2^L + 1 instead of decoding the dense decode_res^3 lattice; off: the dense route, unchanged
         self.sparse_decode, self.sparse_coarse, self.sparse_margin = sparse_decode, sparse_coarse, sparse_margin
@@ -336,8 +347,7 @@ class VisShapeFormer(VisCallback):
             out.update(self._score(computed, sets, vd, fd, voff, toff, input_name, data_dir, report))
         v, f = vd.cpu().numpy().astype(np.float64), fd.cpu().numpy().astype(int)
         if self.decimate_face is not None:
-            from .simplify import decimate_dev
-            wd, gd, woff, goff = decimate_dev(vd, fd, voff, toff, self.decimate_face)[:4]
+            wd, gd, woff, goff = _decimate(self.decimate_method, vd, fd, voff, toff, self.decimate_face)[:4]
             w, g = wd.cpu().numpy().astype(np.float64), gd.cpu().numpy().astype(int)
         else:
             wd, w, g, woff, goff = vd, v, f, voff, toff

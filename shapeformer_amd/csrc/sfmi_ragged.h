@@ -1,5 +1,5 @@
 // Shared pieces of the mesh and scan tools: what csrc/pointdist.hip, meshsdf.hip, meshtree.hip, hpr.hip, iso_sparse.hip, simplify.hip,
-// components.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip, global_register.hip, posegraph.hip, tangent.hip and emd.hip need
+// components.hip, collapse.hip, morph.hip, knn.hip, downsample.hip, poisson.hip, segment.hip, register.hip, features.hip, global_register.hip, posegraph.hip, tangent.hip and emd.hip need
 // for ragged batches (the split nearest-neighbour search of the scan tools is sfmi_search.h, which includes this file).  A ragged batch
 // is B sets stored back to back with (B+1) nondecreasing offsets, off[0] = 0 and off[B] = the item count: item x belongs to the set b
 // with off[b] <= x < off[b+1].  Everything here is inlined into its caller.  The host one-liners at the end hold SfmiCarver, through

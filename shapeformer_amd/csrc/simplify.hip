@@ -16,6 +16,7 @@
 // Integer atomicOr / atomicAdd only.  The solve walks each cell's records in a stably sorted order with lane l taking entries
 // l, l+64, ... and reduces with a fixed butterfly, so a cell's vertex depends on its shape alone and is the same bits every run.
 #include "sfmi_ragged.h"   // the ragged-batch helpers the mesh tools share: DESIGN.md §5.5a
+#include "sfmi_quadric.h"  // the 3x3 Cholesky solve, shared with csrc/collapse.hip
 
 // the f32 cell expression and the f64 plane terms are written once, here and in numpy: no contraction into fused multiply-adds
 #pragma clang fp contract(off)
@@ -184,19 +185,7 @@ __global__ __launch_bounds__(256) void simp_solve_kernel(const float* __restrict
   const double tr = a00 + a11 + a22;
   if (tr > 0.0) {
     // (A + lam I) x = -b + lam m, symmetric positive definite with condition <= 1 + 1/reg: Cholesky L L^T
-    const double lam = reg * tr;
-    const double r0 = lam * m[0] - b0, r1 = lam * m[1] - b1, r2 = lam * m[2] - b2;
-    const double l00 = sqrt(a00 + lam);
-    const double l10 = a01 / l00, l20 = a02 / l00;
-    const double l11 = sqrt(a11 + lam - l10 * l10);
-    const double l21 = (a12 - l20 * l10) / l11;
-    const double l22 = sqrt(a22 + lam - l20 * l20 - l21 * l21);
-    const double y0 = r0 / l00;
-    const double y1 = (r1 - l10 * y0) / l11;
-    const double y2 = (r2 - l20 * y0 - l21 * y1) / l22;
-    x[2] = y2 / l22;
-    x[1] = (y1 - l21 * x[2]) / l11;
-    x[0] = (y0 - l10 * x[1] - l20 * x[2]) / l00;
+    sfmi_quadric_solve(a00, a01, a02, a11, a12, a22, b0, b1, b2, reg * tr, m, x);
   }
 #pragma unroll
   for (int d = 0; d < 3; ++d) {

@@ -54,12 +54,21 @@ def _smooth_choice(gaussian_sigma=None, smooth=None):
     return smooth, {}
 
 
+def _decimate_choice(method):
+    """the `decimate_method` keyword of array2mesh and of the callbacks: checked on the host, before any device work"""
+    if method not in ("cluster", "collapse"):
+        raise L.SfmiError(f"decimate_method = {method!r} must be 'cluster' or 'collapse'")
+    return method
+
+
 def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)), device="cuda:0", if_decimate=False,
-               decimate_face=4096, keep_components=None, gaussian_sigma=None, smooth=None):
+               decimate_face=4096, keep_components=None, gaussian_sigma=None, smooth=None, decimate_method="cluster"):
     """geoutil.array2mesh(array, thresh, dim=3, coords=..., if_decimate=..., decimate_face=..., gaussian_sigma=...) for ONE flattened or
     cubic grid -> (verts (V,3) float64, faces (T,3) int) numpy, like the reference returns (`verts*(bbmax-bbmin)+bbmin`,
     faces.astype(int)).
     if_decimate: a mesh with more than `decimate_face` faces is decimated on the device, over the same box, before the copy.
+    decimate_method: "cluster" (default: simplify.decimate_dev, at most `decimate_face` faces) or "collapse" (collapse.decimate_collapse_dev,
+    DESIGN 5.25: edge collapse to `decimate_face` faces or one fewer, topology kept).
     keep_components: "largest", an int k, a float in (0, 1] or a dict of components.keep_components_dev's keyword arguments: the mesh's
     connected components are filtered on the device before the decimation; None: off.
     gaussian_sigma / smooth (_smooth_choice above; both None: off, the mesh of the grid as it is): the grid is binarised at `> thresh`,
@@ -67,6 +76,7 @@ def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.
     0.  The one deviation from the reference, which binarises at `> 0` and marches the smoothed field at `thresh`: there, an occupancy
     grid in [0, 1] becomes all set but for its exact zeros, and a level of 0.5 lies off the smoothed surface."""
     choice = _smooth_choice(gaussian_sigma, smooth)
+    decimate_method = _decimate_choice(decimate_method)
     a = torch.as_tensor(occupancy, dtype=torch.float32)
     if a.dim() != 3:
         Q = round(a.numel() ** (1.0 / 3))
@@ -83,7 +93,10 @@ def array2mesh(occupancy, thresh=0.5, coords=None, bbox=((-1.0, -1.0, -1.0), (1.
     if keep_components is not None:
         from .components import keep_components_dev, parse_keep
         v, f, voff, toff = keep_components_dev(v, f, voff, toff, **parse_keep(keep_components))[:4]
-    if if_decimate:
+    if if_decimate and decimate_method == "collapse":
+        from .collapse import decimate_collapse_dev
+        v, f = decimate_collapse_dev(v, f, voff, toff, decimate_face)[:2]
+    elif if_decimate:
         from .simplify import decimate_dev
         v, f = decimate_dev(v, f, voff, toff, decimate_face, bbox)[:2]
     return v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(int)
